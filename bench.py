@@ -8,7 +8,9 @@ torch.distributed.run, one rank per GPU.  One "step" = one pass of the hot path 
 HBM.  Images shard across ranks with no data-path collective (weak scaling: B images per GPU); the
 only collective is the one-off RCCL broadcast of the frozen weights (outside the timed region).
 
-Rank 0 prints ONE JSON line.  ``roofline``: the dominant kernel is the persistent layer kernel
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last step's output when
+``--dump-outputs DIR`` is given, and prints the line; ``roofline``, ``power``, ``trained_like``, ``cpu_baseline`` and
+``parity`` are measured only with ``--full`` (null otherwise).  ``roofline``: the dominant kernel is the persistent layer kernel
 (b3::k_layer: output_proj + LN0, FFN fc1 + GELU + fc2 + LN1 + FiLM, and the next layer's value /
 sampling projections in one launch = 89 % of the loop's flops; in the default bf16x3 engine every
 fp32 product is 6 bf16 MFMA products with fp32 accumulation, so the bound is the dense bf16 MFMA
@@ -73,6 +75,7 @@ FP32_MFMA_PEAK_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md: v_m
 BF16_MFMA_PEAK_TFLOPS = 2500.0     # same guide: dense bf16 MFMA peak (v_mfma_f32_32x32x16_bf16, 32 cycles/SIMD)
 B3_PRODUCTS = 6                    # bf16 MFMA products per fp32-equivalent product in the bf16x3 engine
 TAG_FC2_LN = 7
+DUMP_LIMIT_BYTES = 48 << 20        # --dump-outputs: larger outputs are written as a fixed sample of pixel positions
 
 
 def flops_per_token_step(num_layers, num_classes, cx=256):
@@ -164,6 +167,26 @@ def gather_rank_stats(elapsed, step_ms, images_per_rank_step, steps, dev):
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return per_rank, float(t.item())
+
+
+def dump_outputs(out, dirname, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: ``out`` (B, C, H, W) as the caller of the timed path receives it -> DIR/*.npy, float32; -> the file names.
+    Above ``limit`` bytes: the same fixed, seeded set of pixel positions of every image and channel (sorted flat H*W indices,
+    stored beside the sample as float64), so that two builds run with the same arguments can be compared value for value."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    o = out.detach().float()
+    if o.numel() * 4 <= limit:
+        np.save(os.path.join(dirname, 'out.npy'), o.cpu().numpy())
+        return ['out.npy']
+    B, Cc = o.shape[0], o.shape[1]
+    n_pix = o[0, 0].numel()
+    keep = max(1, min(n_pix, limit // (4 * B * Cc)))
+    idx = torch.randperm(n_pix, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    sample = o.reshape(B, Cc, n_pix)[:, :, idx.to(o.device)]
+    np.save(os.path.join(dirname, 'out_sample.npy'), sample.cpu().numpy())
+    np.save(os.path.join(dirname, 'out_sample_index.npy'), idx.double().numpy())
+    return ['out_sample.npy', 'out_sample_index.npy']
 
 
 def _gpu_numa_nodes(world, sysfs_root='', bdfs=None):
@@ -657,6 +680,14 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='ade_swin_t_k3_8x512x1024', choices=sorted(WORKLOADS))
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the legs that are not needed for the headline figure: power / clock, '
+                         'roofline (+ vendor GEMM), the trained_like sub-record, CPU baseline + parity against the oracle.  '
+                         'Without it those sub-records are null; the --no-* switches below drop single legs of a --full run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned in its last timed step to DIR/<name>.npy (float32; rank 0): '
+                         'out.npy when it fits in %d MB, else a fixed seeded sample of pixel positions (all channels) as '
+                         'out_sample.npy with the positions in out_sample_index.npy' % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-images', type=int, default=2, help='images timed on the CPU oracle (bounded sample)')
     ap.add_argument('--no-roofline', action='store_true')
@@ -810,6 +841,8 @@ def main():
     images_per_s = B * calls_per_step * world * args.steps / elapsed
     if dry and per_rank is not None:
         per_rank['images_per_s'] = None          # (clocks of a stub: the ranks' elapsed / step times stay, as plumbing evidence)
+    # `out` still holds the last timed step's result: written before any leg below launches the engine again
+    dumped = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0 and not dry) else None
 
     # ---- power leg (rank 0): the same loop back to back for a couple of seconds with package power and shader clock
     # sampled beside it; also gives the SUSTAINED rate (the timed region above is a fraction of a second)
@@ -817,6 +850,8 @@ def main():
         args.no_power = args.no_roofline = args.no_trained_like = args.no_cpu_baseline = True
         args.next_rows = args.host_leg = False
         args.size_stream = 0
+    if not args.full:                            # a plain run carries the headline figure only
+        args.no_power = args.no_roofline = args.no_trained_like = args.no_cpu_baseline = True
     power = None
     if rank == 0 and not args.no_power:
         ps = PowerSampler(local_rank)
@@ -1129,7 +1164,7 @@ def main():
             'scaling': args.scaling, 'vs_baseline': None,
             'dtype': 'f32 (bf16x3-split MFMA products, fp32 accumulate)' if eng.gemm == 'bf16x3' else 'f32',
             'data': 'synthetic' if not dry else 'none (--dry-run-world: control-flow rehearsal on CPU / gloo, no kernel ran)',
-            'dry_run': dry,
+            'dry_run': dry, 'full': args.full, 'dumped_outputs': dumped,
             'config': {'workload': args.workload + (' (ADE20K Swin-T DDP decode head, 3-step DDIM, batch 8x512x1024 '
                                                     'per GPU; x (8,256,128,256), random-init weights)'
                                                     if args.workload == 'ade_swin_t_k3_8x512x1024' else

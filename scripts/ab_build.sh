@@ -3,7 +3,7 @@
 # gpurun), next to the working tree's ddp_amd/lib/.  Then compare inside ONE gpurun call (box-to-box spread is +-3 %):
 #   scripts/ab_build.sh HEAD~1 exp/gather-t8
 #   gpurun --timeout 300 -- 'for v in lib lib_HEAD_1 lib_exp_gather-t8 lib lib_HEAD_1 lib_exp_gather-t8; do \
-#       DDP_LIB_PATH=$PWD/ddp_amd/$v/libddp_mi355x.so python bench.py --steps 10 --warmup 3 --no-cpu-baseline | \
+#       DDP_LIB_PATH=$PWD/ddp_amd/$v/libddp_mi355x.so python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline | \
 #       python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d[\"value\"], d[\"roofline\"][\"avg_launch_ms\"])"; done'
 # (remove the lib_* directories afterwards; DDP_LIB_PATH is honoured by ddp_amd/_lib.py)
 set -e

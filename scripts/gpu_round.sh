@@ -22,10 +22,10 @@ fi
 PYTEST_ORDER="python -m pytest tests -m gpu -q -s"
 run_tests() { $PYTEST_ORDER ${KSEL:+"$KSEL"} 2>&1 | grep -v "amdgpu.ids\|^$" > $OUT/pytest_gpu.txt; tail -3 $OUT/pytest_gpu.txt; }
 [ "$QUICK" = quick ] || run_tests
-python bench.py --steps 10 --warmup 2 --next-rows --size-stream 50 --host-leg > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 10 --warmup 2 --next-rows --size-stream 50 --host-leg > $OUT/bench.json 2> $OUT/bench.err
 cut -c1-2500 $OUT/bench.json; tail -3 $OUT/bench.err
 # the strong-scaling shard of the headline configuration (one image per GPU at 8 GPUs), with kernel stats
-python bench.py --workload ade_swin_t_k3_1x512x1024 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_ade_swin_t_k3_1x512x1024.json 2> $OUT/bench_b1.err
+python bench.py --full --workload ade_swin_t_k3_1x512x1024 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_ade_swin_t_k3_1x512x1024.json 2> $OUT/bench_b1.err
 cut -c1-400 $OUT/bench_ade_swin_t_k3_1x512x1024.json
 REPO=$PWD
 # (--no-trained-like: the default line also times an engine with the trained_like weight profile, whose gather launches - same kernel
@@ -63,7 +63,7 @@ done
 cd $REPO
 # the other BASELINE configurations as plain bench lines: throughput, roofline, CPU baseline and full-size parity of one image
 for wl in $WLS; do
-  timeout 400 python bench.py --workload $wl --steps 3 --warmup 1 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
+  timeout 400 python bench.py --full --workload $wl --steps 3 --warmup 1 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
   tail -1 $OUT/bench_$wl.json | cut -c1-200
 done
 # round 6: the fused step boundaries of the depth / BEV samplers against the round-5 launches (DDP_TAIL_FUSED=0), per-call HIP-event
@@ -71,7 +71,7 @@ done
 if [ "$QUICK" != quick ]; then
   timeout 400 python scripts/call_times.py --workload bev_fusion_k3_8x200x200 fused= unfused=DDP_TAIL_FUSED=0 --calls 30 --blocks 2 > $OUT/call_times_bev.jsonl 2> $OUT/call_times_bev.err
   timeout 400 python scripts/call_times.py --workload kitti_depth_k20_16x352x1216 fused= unfused=DDP_TAIL_FUSED=0 --calls 6 --blocks 2 > $OUT/call_times_kitti.jsonl 2> $OUT/call_times_kitti.err
-  timeout 300 python bench.py --workload bev_fusion_k3_r4_2x200x200 --steps 5 --warmup 1 > $OUT/bench_bev_fusion_k3_r4_2x200x200.json 2> $OUT/bench_bev_r4.err
+  timeout 300 python bench.py --full --workload bev_fusion_k3_r4_2x200x200 --steps 5 --warmup 1 > $OUT/bench_bev_fusion_k3_r4_2x200x200.json 2> $OUT/bench_bev_r4.err
   python - $OUT <<'PY'
 import json, sys
 for wl in ('bev', 'kitti'):
@@ -92,7 +92,7 @@ tail -1 $OUT/force_dist_rccl_world1.json | cut -c1-300
 # strong scaling at N = 1 (what `--scaling strong --gpus 1` reports: the configuration's total batch in calls of the workload's batch)
 for wl in ade_swin_t_k3_8x512x1024 city_swin_l_k10_4x1024x2048 bev_fusion_k3_8x200x200; do
   [ "$QUICK" = quick ] && [ $wl != ade_swin_t_k3_8x512x1024 ] && continue
-  timeout 300 python bench.py --workload $wl --scaling strong --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-power > $OUT/${wl}_scaling_strong_n1.json 2> $OUT/strong_$wl.err
+  timeout 300 python bench.py --full --workload $wl --scaling strong --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-power > $OUT/${wl}_scaling_strong_n1.json 2> $OUT/strong_$wl.err
 done
 # FCN-head sampler: the loop-invariant kernels run once per engine, not per call (ddp_prepare_fcn)
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_fcn -o fcn -- python $REPO/scripts/fcn_launch_count.py > $REPO/$OUT/fcn_calls.log 2>&1 )

@@ -19,7 +19,7 @@ def test_stdout_is_one_json_line_under_the_launcher():
     env = dict(os.environ, MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', '29531', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-           '--workload', 'ade_swin_t_k3_1x512x1024', '--no-cpu-baseline', '--no-power', '--force-dist']
+           '--workload', 'ade_swin_t_k3_1x512x1024', '--full', '--no-cpu-baseline', '--no-power', '--force-dist']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -63,3 +63,29 @@ def test_bench_gpus_2_on_a_one_gpu_box_fails_loudly():
     assert r.returncode != 0
     assert '2 device(s) required' in (r.stderr + r.stdout)
     assert '"n_gpus"' not in r.stdout
+
+
+@pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a HIP device')
+def test_plain_run_times_its_steps_and_dumps_the_last_output(tmp_path):
+    """A plain run (no --full) prints the headline line with the measurement legs null, `steps` timed steps and
+    ms_per_step; --dump-outputs writes the last timed step's output, and the same arguments give the same values."""
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d_out = tmp_path / f'dump{k}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                            '--workload', 'ade_swin_t_k1_1x512x512', '--dump-outputs', str(d_out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:500]
+        d = json.loads(lines[0])
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['full'] is False and d['ms_per_step'] > 0 and d['value'] > 0
+        assert abs(d['value'] - 1 * 1e3 / d['ms_per_step']) < 0.01 * d['value']
+        for k2 in ('roofline', 'power', 'trained_like', 'cpu_baseline', 'parity'):
+            assert d[k2] is None, k2
+        assert d['dumped_outputs'] == ['out.npy']
+        a = np.load(d_out / 'out.npy')
+        assert a.dtype == np.float32 and a.ndim == 4 and a.shape[:2] == (1, 150) and np.isfinite(a).all()
+        outs.append(a)
+    assert np.array_equal(outs[0], outs[1])

@@ -18,7 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, 'golden'))
 import ref_shim  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason='reference tree not present (build container only)')
+# the three probes build the reference's own registries and configs; the vendored-package test below needs neither
+needs_reference = pytest.mark.skipif(not ref_shim.available(), reason='reference tree not present (build container only)')
 
 
 def _probe(task):
@@ -27,6 +28,7 @@ def _probe(task):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
 
 
+@needs_reference
 def test_ade_config_builds_to_ddp_amd_classes_in_mmseg_registry():
     d = _probe('seg')
     assert d['touched'] == ['mmseg']
@@ -40,6 +42,7 @@ def test_ade_config_builds_to_ddp_amd_classes_in_mmseg_registry():
     assert 'simple_test' in d['called']['feature_given'] and 'ddim_sample' in d['called']['feature_given']
 
 
+@needs_reference
 def test_kitti_config_builds_to_ddp_amd_classes_in_depth_registry():
     d = _probe('depth')
     assert d['touched'] == ['depth']
@@ -51,6 +54,7 @@ def test_kitti_config_builds_to_ddp_amd_classes_in_depth_registry():
     assert 'aug_test' in d['called']['feature_given'] and d['called']['feature_given'][-1] == 'sample'
 
 
+@needs_reference
 def test_controlnet_mmseg_copy_builds_to_ddp_amd_classes():
     """VERDICT r05 missing #5: the ControlNet demo ships its own copy of the toolbox (controlnet/annotator/ddp/mmseg, imported as
     top-level ``mmseg``: controlnet/annotator/ddp/__init__.py:2; used by controlnet/gradio_seg2image_ddp.py:2,24,35).

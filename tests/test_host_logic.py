@@ -644,3 +644,24 @@ def test_docs_and_profiles_describe_the_shipped_kernel_sources():
     tags = [os.path.basename(p) for p in glob.glob(os.path.join(root, 'profiles', '*_pmc_summary.json'))
             if json.load(open(p)).get('_meta', {}).get('source_sha') == sha]
     assert tags, f'no profiles/*_pmc_summary.json was taken on the current kernel sources {sha}'
+
+
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: an output that fits is written whole; a larger one as the same seeded pixel sample every time,
+    float32 values with their positions, under the size limit."""
+    import numpy as np
+    import torch
+    import bench
+    out = torch.arange(2 * 3 * 4 * 5, dtype=torch.float32).reshape(2, 3, 4, 5)
+    assert bench.dump_outputs(out, str(tmp_path / 'a')) == ['out.npy']
+    a = np.load(tmp_path / 'a' / 'out.npy')
+    assert a.dtype == np.float32 and np.array_equal(a, out.numpy())
+    limit = 2 * 3 * 4 * 7                                    # room for 7 of the 20 pixel positions
+    names = bench.dump_outputs(out, str(tmp_path / 'b'), limit=limit)
+    assert names == ['out_sample.npy', 'out_sample_index.npy']
+    bench.dump_outputs(out, str(tmp_path / 'c'), limit=limit)
+    s, idx = np.load(tmp_path / 'b' / 'out_sample.npy'), np.load(tmp_path / 'b' / 'out_sample_index.npy')
+    assert s.dtype == np.float32 and s.shape == (2, 3, 7) and s.nbytes <= limit and idx.dtype == np.float64
+    assert np.all(np.diff(idx) > 0) and np.array_equal(s, out.numpy().reshape(2, 3, 20)[:, :, idx.astype(np.int64)])
+    assert np.array_equal(s, np.load(tmp_path / 'c' / 'out_sample.npy'))
+    assert np.array_equal(idx, np.load(tmp_path / 'c' / 'out_sample_index.npy'))
