@@ -10,13 +10,15 @@ from . import build as _build
 
 MAX_LAYERS = 12
 MAX_STEPS = 64
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 TASK_SEG, TASK_DEPTH, TASK_BEV = 0, 1, 2
 SAMPLER_DDIM, SAMPLER_DDPM = 0, 1
 GEMM_F32_MFMA, GEMM_BF16X3 = 0, 1
 FLAG_UNFUSED_LAYER, FLAG_UNFUSED_PROLOGUE, FLAG_RECORD_X0, FLAG_GATHER_GUESS_ZERO, FLAG_FCN_PREPARED, FLAG_FORCE_X0, FLAG_UNFUSED_TAIL, FLAG_SB_HEAD = 1, 2, 4, 8, 16, 32, 64, 128
 FLAG_DEPTH_SCALE_UP, FLAG_DEPTH_NO_EPS = 256, 512
+DEPTH_NORM_LINEAR, DEPTH_NORM_SOFTMAX, DEPTH_NORM_SIGMOID = 0, 1, 2
+MAX_DEPTH_BINS = 256
 NECK_WEIGHTS_READY = 1
 
 _fp = C.c_void_p  # device pointers travel as raw addresses
@@ -33,6 +35,7 @@ class DdpCfg(C.Structure):
         ('bev_in_min', C.c_float * 2), ('bev_in_max', C.c_float * 2),
         ('bev_out_first', C.c_float * 2), ('bev_out_step', C.c_float * 2),
         ('gemm_mode', C.c_int32), ('flags', C.c_int32),
+        ('depth_n_bins', C.c_int32), ('depth_norm', C.c_int32), ('head_min_depth', C.c_float), ('head_max_depth', C.c_float),
     ]
 
 
@@ -50,7 +53,7 @@ TOP_FIELDS = ['transform_w', 'transform_b', 'time_freq', 'time1_w', 'time1_b', '
 
 
 class DdpWeights(C.Structure):
-    _fields_ = [(n, _fp) for n in TOP_FIELDS] + [('layers', DdpLayerWeights * MAX_LAYERS)]
+    _fields_ = [(n, _fp) for n in TOP_FIELDS] + [('layers', DdpLayerWeights * MAX_LAYERS), ('depth_bins', _fp)]
 
 
 class DdpStep(C.Structure):

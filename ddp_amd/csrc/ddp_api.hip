@@ -112,6 +112,12 @@ struct Layout {
   float* tail4_bias;                                    //             conv_seg bias | layer 0's value_proj bias at [1024, 1280)
   unsigned char* tail_stream;                           // seg tail: conv_seg stage images (2 per 64 classes)
   float* tail_bias;                                     //           conv_seg bias, zero padded
+  // binned depth head (cfg->depth_n_bins > 0): conv_depth to n_bins channels + k_depth_bins
+  int nbins, bins_ld, bins_guard;
+  float *bins_tab, *bins_bias, *bins_wpack;             // bin centres, conv bias (256, zero padded), weights tap-major (256, 2304)
+  unsigned short* bins_wsplit;                          // bf16x3: split planes of bins_wpack
+  unsigned char* bins_stream;                           // bf16x3: the 72 stage images of the implicit 3x3 GEMM
+  float *bins_in, *bins_logits;                         // fp32 engine: zero-bordered grid of the layer output; logits (see carve)
   size_t const_bytes;   // region A (model constants): a prefix of the workspace that does not depend on the geometry
   size_t total;
 };
@@ -166,6 +172,22 @@ int validate(const ddp_cfg* c) {
     set_error("DDP_FLAG_RECORD_X0 / DDP_FLAG_FORCE_X0 exist for the segmentation sampler only (task %d)", c->task);
     return DDP_E_BADCFG;
   }
+  if (c->depth_n_bins != 0 && c->task != DDP_TASK_DEPTH) {
+    set_error("depth_n_bins configures the depth head only (task %d)", c->task);
+    return DDP_E_BADCFG;
+  }
+  if (c->depth_n_bins < 0 || c->depth_n_bins > DDP_MAX_DEPTH_BINS) {
+    set_error("depth_n_bins %d out of range [0,%d]", c->depth_n_bins, DDP_MAX_DEPTH_BINS);
+    return DDP_E_BADCFG;
+  }
+  if (c->depth_norm < DDP_DEPTH_NORM_LINEAR || c->depth_norm > DDP_DEPTH_NORM_SIGMOID || (c->depth_norm && !c->depth_n_bins)) {
+    set_error("depth_norm %d: DDP_DEPTH_NORM_* of a binned depth head", c->depth_norm);
+    return DDP_E_BADCFG;
+  }
+  if ((c->head_min_depth != 0.f || c->head_max_depth != 0.f) && c->task != DDP_TASK_DEPTH) {
+    set_error("head_min_depth / head_max_depth configure the depth head only (task %d)", c->task);
+    return DDP_E_BADCFG;
+  }
   if ((c->flags & (DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS)) && c->task != DDP_TASK_DEPTH) {
     set_error("DDP_FLAG_DEPTH_* configure the depth head only (task %d)", c->task);
     return DDP_E_BADCFG;
@@ -218,6 +240,10 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   o->wx = cv.take(size_t(256) * o->Cx);
   o->wm = cv.take(size_t(256) * o->Cm);
   o->wtap = cv.take(size_t(9) * 256);
+  o->nbins = c->task == DDP_TASK_DEPTH ? c->depth_n_bins : 0;
+  o->bins_tab = o->nbins ? cv.take(DDP_MAX_DEPTH_BINS) : nullptr;
+  o->bins_bias = o->nbins ? cv.take(256) : nullptr;
+  o->bins_wpack = o->nbins ? cv.take(size_t(256) * 2304) : nullptr;
   for (int l = 0; l < DDP_MAX_LAYERS; ++l) {
     const bool on = l < o->L;
     o->wcat[l] = on ? cv.take(96 * 256) : nullptr;
@@ -265,6 +291,8 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->tlut = cv.take(segp ? size_t(o->Kc + 1) * 256 : bev_tab ? (size_t(1) << o->Kc) * 256 : 0);
     o->lut64 = bev_tab ? cv.take((size_t(1) << o->Kc) * 256) : nullptr;
     o->wvs = c->task == DDP_TASK_DEPTH ? cv.take(512) : nullptr;
+    o->bins_wsplit = o->nbins ? reinterpret_cast<unsigned short*>(cv.take(size_t(256) * 2304 * 3 / 2)) : nullptr;
+    o->bins_stream = o->nbins ? reinterpret_cast<unsigned char*>(cv.take(size_t(72) * 48 * 1024 / sizeof(float))) : nullptr;
   } else {
     o->tail_stream = nullptr;
     o->tail_bias = nullptr;
@@ -278,6 +306,8 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->tlut = nullptr;
     o->lut64 = nullptr;
     o->wvs = nullptr;
+    o->bins_wsplit = nullptr;
+    o->bins_stream = nullptr;
   }
   o->const_bytes = cv.off * sizeof(float);
   // ---- region B: everything that depends on the geometry (batch, r, map size): positional tables, activations
@@ -307,6 +337,21 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   o->logits = cv.take(o->M * o->ldl > pfl ? o->M * o->ldl : pfl);
   o->prob = cv.take(o->M * o->ldl > pfl ? o->M * o->ldl : pfl);
   o->snoise = cv.take(c->sampler == DDP_SAMPLER_DDPM ? o->M0 * 256 : 0);
+  // binned depth head: bf16x3 - the stream GEMM writes the logits fp32 fragment-major with 256 channels (rows padded to 256);
+  // fp32 engine - the layer output on a zero-bordered grid (+ guard rows: the nine taps are row offsets of up to w + 3) and the
+  // logits on that grid, rows of bins_ld floats
+  o->bins_ld = (o->nbins + 3) / 4 * 4;
+  o->bins_guard = o->w + 3;
+  o->bins_in = o->bins_logits = nullptr;
+  if (o->nbins) {
+    const size_t padded = size_t(o->R) * (o->h + 2) * (o->w + 2);
+    if (o->b3) {
+      o->bins_logits = cv.take(Mp * 256);
+    } else {
+      o->bins_in = cv.take((padded + 2 * size_t(o->bins_guard)) * 256);
+      o->bins_logits = cv.take(padded * o->bins_ld);
+    }
+  }
   o->x0_trace = reinterpret_cast<unsigned char*>(
       cv.take((c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) && c->task == DDP_TASK_SEG
                   ? ((c->flags & DDP_FLAG_FORCE_X0 ? 2 : 1) * size_t(o->K) * o->M + 3) / 4
@@ -387,6 +432,7 @@ int check_weights(const ddp_cfg* c, const ddp_weights* w) {
   DDP_TRY(check_ptr(w->head_w, "head_w"));
   DDP_TRY(check_ptr(w->head_b, "head_b"));
   if (c->task != DDP_TASK_DEPTH) DDP_TRY(check_ptr(w->embedding, "embedding"));
+  if (c->task == DDP_TASK_DEPTH && c->depth_n_bins) DDP_TRY(check_ptr(w->depth_bins, "depth_bins"));
   for (int l = 0; l < c->num_layers; ++l) {
     const ddp_layer_weights& lw = w->layers[l];
     const void* ps[] = {lw.sampling_offsets_w, lw.sampling_offsets_b, lw.attention_weights_w, lw.attention_weights_b,
@@ -452,6 +498,23 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
   DDP_TRY(launch_pack_cols(w->transform_w, o.Cx + o.Cm, o.Cx, 256, o.Cm, o.wm, st));
   if (c->task == DDP_TASK_SEG) DDP_TRY(launch_build_lut(w->embedding, o.lut, o.Kc + 1, c->bit_scale, st));
   if (c->task == DDP_TASK_DEPTH) DDP_TRY(launch_pack_conv3x3(w->head_w, o.wtap, st));
+  if (o.nbins) {
+    // binned depth head: conv_depth (n_bins,256,3,3) tap-major, output rows zero-padded to the stream GEMM's 256 columns; bias and
+    // bin centres zero-padded likewise
+    if (hipMemsetAsync(o.bins_wpack, 0, size_t(256) * 2304 * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(o.bins_bias, 0, 256 * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(o.bins_tab, 0, DDP_MAX_DEPTH_BINS * sizeof(float), st) != hipSuccess ||
+        hipMemcpyAsync(o.bins_bias, w->head_b, size_t(o.nbins) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(o.bins_tab, w->depth_bins, size_t(o.nbins) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      set_error("depth bins: weight copy failed");
+      return DDP_E_LAUNCH;
+    }
+    DDP_TRY(launch_pack_conv3x3_scaled(w->head_w, nullptr, o.bins_wpack, o.nbins, 256, st));
+    if (o.b3) {   // the implicit 3x3 GEMM's 72 stage images (as FCNHeadWithTime's convolutions)
+      DDP_TRY(launch_split_weights(o.bins_wpack, 2304, 256, 2304, o.bins_wsplit, st));
+      DDP_TRY(launch_build_stages(o.bins_wsplit, size_t(256) * 2304, 2304, 256, 0, 1, 72, 0, 2, 1, 0, o.bins_stream, st));
+    }
+  }
   for (int l = 0; l < o.L; ++l) {
     const ddp_layer_weights& lw = w->layers[l];
     DDP_TRY(launch_pack_rows(lw.sampling_offsets_w, 64, lw.attention_weights_w, 32, o.wcat[l], 256, st));
@@ -596,6 +659,65 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
 int publish_q(const Layout& o, const float* row_major, hipStream_t st) {
   if (o.b3 && !o.fused_layer) return launch_row_to_sb(row_major, 256, o.q_sb, int(o.M), 256, st);
   return launch_row_to_blk(row_major, o.q, int(o.M), st);     // the layer kernels (and the fp32 engine) take q as fp32 fragments
+}
+
+// binned depth head (decode_head.py:233-250) on the encoder output: conv_depth to n_bins channels (3x3, padding 1, bias), then
+// k_depth_bins -> the metric prediction `pred` (M).  bf16x3: the implicit 3x3 GEMM of the stream engine (k_layer MODE 5, 72 stages,
+// bias in the epilogue, no activation) on the fp32 fragment-major layer output; fp32 engine: the exact-product GEMM as nine shifted
+// GEMMs over the zero-bordered grid, accumulated in place.
+int depth_bins_head(const ddp_cfg* c, const Layout& o, float* pred, hipStream_t st) {
+  const int M = int(o.M);
+  DepthBinsArgs a;
+  a.bins = o.bins_tab;
+  a.n_bins = o.nbins;
+  a.norm = c->depth_norm;
+  a.pred = pred;
+  a.R = o.R;
+  a.h = o.h;
+  a.w = o.w;
+  if (o.b3) {
+    if (!o.fused_layer) {     // the tile-GEMM layers leave their output as SB only
+      DDP_TRY(launch_sb_to_row(o.q_sb, o.s, M, 256, st));
+      DDP_TRY(launch_row_to_blk(o.s, o.q, M, st));
+    }
+    SgemmProblem pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.A = o.q;
+    pr.out = o.bins_logits;
+    pr.stream = o.bins_stream;
+    pr.M = M;
+    pr.ns = 72;
+    pr.conv_h = o.h;
+    pr.conv_w = o.w;
+    pr.bias = o.bins_bias;
+    prof_begin(TAG_HEAD, st);
+    DDP_TRY(launch_b3_sgemm(&pr, 1, 0, 1, st));
+    prof_end(TAG_HEAD, st);
+    a.logits = o.bins_logits;
+    a.layout = 0;
+    a.ld = 256;
+  } else {
+    DDP_TRY(launch_blk_to_pad(o.q, o.bins_in, o.R, o.h, o.w, o.bins_guard, st));
+    const int rows = o.R * (o.h + 2) * (o.w + 2);
+    for (int t = 0; t < 9; ++t) {
+      const int off = (t / 3 - 1) * (o.w + 2) + (t % 3 - 1);
+      DDP_TRY(launch_linear(o.bins_in + size_t(o.bins_guard + off) * 256, 256, false, o.bins_wpack + t * 256, 2304,
+                            t == 0 ? o.bins_bias : nullptr, t == 0 ? nullptr : o.bins_logits, o.bins_ld, 0, 0, o.bins_logits,
+                            o.bins_ld, rows, o.nbins, 256, 0, st));
+    }
+    a.logits = o.bins_logits;
+    a.layout = 1;
+    a.ld = o.bins_ld;
+  }
+  return launch_depth_bins(a, st);
+}
+
+// eps of the regression head's depth_pred: the HEAD's depth range (decode_head.py:258-266; 0 / 0 = the depther's)
+float depth_head_eps(const ddp_cfg* c) {
+  const bool own = c->head_min_depth != 0.f || c->head_max_depth != 0.f;
+  const float lo = own ? c->head_min_depth : c->min_depth, hi = own ? c->head_max_depth : c->max_depth;
+  const bool su = (c->flags & DDP_FLAG_DEPTH_SCALE_UP) != 0;
+  return (c->flags & DDP_FLAG_DEPTH_NO_EPS) ? (su ? 1.0f : 0.0f) : (su ? hi : lo);
 }
 
 // DetrTransformerEncoder over the fragment-major q (in/out); aff (L,512) = norms.1 affine x FiLM
@@ -899,7 +1021,9 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
   // noisy map is carried as u = W_m m (o.feat0, row-major at the map size) and follows the DDIM update through the 2^K-row table
   // T = LUT64 . W_m^T - per step: u update, q = rx + resample(u), layer 0's projections; no GEMM at the map size after u_0.
   const bool lt_other = o.b3 && o.fused_layer && o.fused_pro && o.lt_stream && !(cfg->flags & DDP_FLAG_UNFUSED_TAIL);
-  const bool depth_lt = cfg->task == DDP_TASK_DEPTH && lt_other;
+  // (the binned depth head takes the route of DDP_FLAG_UNFUSED_TAIL: MODE 3 step head, a plain last layer, conv_depth + k_depth_bins,
+  // k_depth_update)
+  const bool depth_lt = cfg->task == DDP_TASK_DEPTH && lt_other && !o.nbins;
   // depth chain (one noisy map per image, >= 2 layers): the step head without a GEMM.  Loop invariant, once per sample: xproj
   // fragment-major (layer 0's residual operand), rvpad = W_v0 xproj + b_v0 as a padded map (layer 0's projection kernel run on xproj
   // itself), rs0 = W_cat0 xproj; per step k_depth_head adds the rank-1 terms in the noisy depth (and runs the previous step's update)
@@ -935,7 +1059,7 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
   unsigned char* bev_code = reinterpret_cast<unsigned char*>(o.logits);            // (M) the step's x0 code per head-grid token
   auto depth_update_args = [&](const ddp_step& stp) {
     DepthUpdateArgs a;
-    a.taps = o.logits;
+    a.taps = o.nbins ? nullptr : o.logits;
     a.bias = 0.f;
     a.bias_ptr = weights->head_b;
     a.depth_t = o.mask;
@@ -947,7 +1071,7 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     a.max_depth = cfg->max_depth;
     a.bit_scale = cfg->bit_scale;
     a.scale_up = (cfg->flags & DDP_FLAG_DEPTH_SCALE_UP) ? 1 : 0;      // decode_head.py:252-262
-    a.eps_depth = (cfg->flags & DDP_FLAG_DEPTH_NO_EPS) ? (a.scale_up ? 1.0f : 0.0f) : (a.scale_up ? cfg->max_depth : cfg->min_depth);
+    a.eps_depth = depth_head_eps(cfg);
     a.st = stp;
     return a;
   };
@@ -1119,7 +1243,9 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
       tl.x0_idx = bev_chain ? bev_code : nullptr;
       tl.ldl = 32;
     }
-    DDP_TRY(encoder_forward(weights, o, aff, st, pro_fused || depth_head, !(seg_tail || lt_fused), lt_fused ? &tl : nullptr, depth_chain));
+    // (the binned depth head reads the fp32 layer output: no SB copy from the fused layers)
+    DDP_TRY(encoder_forward(weights, o, aff, st, pro_fused || depth_head, !(seg_tail || lt_fused || (o.nbins && o.fused_layer)),
+                            lt_fused ? &tl : nullptr, depth_chain));
     if (lt_fused && cfg->task == DDP_TASK_BEV) {
       // (probabilities accumulated and the step's x0 codes written by the fused tail; the next step's head updates u from them)
     } else if (seg_tail) {
@@ -1156,6 +1282,8 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     } else if (cfg->task == DDP_TASK_DEPTH) {
       if (depth_lt) {
         // (the nine taps were written by the last layer's tail: k_layer MODE 9)
+      } else if (o.nbins) {
+        DDP_TRY(depth_bins_head(cfg, o, o.pred, st));
       } else if (o.b3) {
         DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, st, TAG_HEAD));
       } else {
@@ -1250,6 +1378,8 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
       DDP_TRY(launch_linear(o.q, 256, true, weights->head_w, 256, weights->head_b, nullptr, 0, 0, 0, o.logits, o.ldl, M, o.Kc,
                             256, 0, st, TAG_HEAD));
     DDP_TRY(launch_finalize_nchw(o.logits, o.ldl, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st));
+  } else if (cfg->task == DDP_TASK_DEPTH && o.nbins) {
+    DDP_TRY(depth_bins_head(cfg, o, d_out, st));     // (R,1,h,w) == (R*N)
   } else if (cfg->task == DDP_TASK_DEPTH) {
     if (o.b3) DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, st, TAG_HEAD));
     else DDP_TRY(launch_linear(o.q, 256, true, o.wtap, 256, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, 0, st, TAG_HEAD));
@@ -1266,7 +1396,7 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
     a.max_depth = cfg->max_depth;
     a.bit_scale = cfg->bit_scale;
     a.scale_up = (cfg->flags & DDP_FLAG_DEPTH_SCALE_UP) ? 1 : 0;      // decode_head.py:252-262
-      a.eps_depth = (cfg->flags & DDP_FLAG_DEPTH_NO_EPS) ? (a.scale_up ? 1.0f : 0.0f) : (a.scale_up ? cfg->max_depth : cfg->min_depth);
+    a.eps_depth = depth_head_eps(cfg);
     DDP_TRY(launch_depth_update(a, st));
   } else {
     if (o.b3)

@@ -317,7 +317,7 @@ int launch_finalize_nchw(const float* prob, int ldl, float* out, int B, int r, i
 int launch_feat_depth(const float* xproj, const float* wm, const float* d, float* q, int B, int r, int N,
                       hipStream_t st);
 struct DepthUpdateArgs {
-  const float* taps;   // (M, 32) 9 per-tap partial dots of conv_depth
+  const float* taps;   // (M, 32) 9 per-tap partial dots of conv_depth; nullptr: pred already holds the prediction (binned head)
   float bias;
   const float* bias_ptr;
   float* depth_t;      // (M) in/out noisy depth
@@ -328,6 +328,21 @@ struct DepthUpdateArgs {
   ddp_step st;
 };
 int launch_depth_update(const DepthUpdateArgs& a, hipStream_t st);
+// binned depth head (decode_head.py:233-250): per pixel, the n_bins logits of conv_depth -> normalised weights -> expectation over the
+// bin centres, written to pred (M) in the layout k_depth_update reads.  layout 0: logits fp32 fragment-major with 256 channels (the
+// stream GEMM's output, rows = tokens); 1: row-major rows of `ld` floats on the zero-bordered grid (R, h+2, w+2) (the fp32 engine)
+struct DepthBinsArgs {
+  const float* logits;
+  int layout, ld;
+  const float* bins;   // (n_bins) bin centres
+  int n_bins, norm;    // DDP_DEPTH_NORM_*
+  float* pred;         // (R*h*w)
+  int R, h, w;
+};
+int launch_depth_bins(const DepthBinsArgs& a, hipStream_t st);
+// fragment-major (R*h*w, 256) -> row-major zero-bordered grid (R, h+2, w+2, 256) with `guard` zero rows before and after (the fp32
+// engine's 3x3 convolution as nine shifted GEMMs)
+int launch_blk_to_pad(const float* in_blk, float* out, int R, int h, int w, int guard, hipStream_t st);
 int launch_mean_r(const float* pred, float* out, int B, int r, int N, hipStream_t st);
 // the depth step head of the chain path WITHOUT a GEMM (ddp_kernels.hip: k_depth_head): layer 0's value map and sample table from their
 // loop-invariant parts + a rank-1 term in the noisy depth, and - upd != nullptr - the previous step's DDIM update in front

@@ -1829,6 +1829,10 @@ __global__ void __launch_bounds__(256) k_depth_update(DepthUpdateArgs a) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   const int N = a.h * a.w;
   if (m >= a.B_r * N) return;
+  float pred;
+  if (!a.taps) {
+    pred = a.pred[m];       // binned head: k_depth_bins wrote the prediction
+  } else {
   const int img = m / N, n = m - img * N;
   const int i = n / a.w, j = n - i * a.w;
   // (branch-free: nine loads in flight, taps outside the map selected to zero - a conditional load each costs a serial round trip)
@@ -1846,8 +1850,9 @@ __global__ void __launch_bounds__(256) k_depth_update(DepthUpdateArgs a) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) s += tv[t];
   s += a.bias_ptr[0];
-  const float pred = a.scale_up ? a.eps_depth / (1.0f + expf(-s)) : fmaxf(s, 0.f) + a.eps_depth;
+  pred = a.scale_up ? a.eps_depth / (1.0f + expf(-s)) : fmaxf(s, 0.f) + a.eps_depth;
   a.pred[m] = pred;
+  }
   if (!a.depth_t) return;   // head-only call: no sampler update
   float x0 = (pred - a.min_depth) / (a.max_depth - a.min_depth);
   x0 = (x0 * 2.0f - 1.0f) * a.bit_scale;
@@ -1855,6 +1860,80 @@ __global__ void __launch_bounds__(256) k_depth_update(DepthUpdateArgs a) {
   const float xt = a.depth_t[m];
   const float eps = a.st.sigma * (xt - a.st.alpha * x0);   // sigma field = 1/sqrt(1-gamma_now)
   a.depth_t[m] = a.st.alpha_next * x0 + a.st.sigma_next * eps;
+}
+
+// Binned depth head (depth/depth/models/decode_heads/decode_head.py:233-250): one thread per pixel streams the pixel's n_bins logits
+// (16 B per load; the 32 pixels of a fragment-major group read 512 contiguous bytes per channel quad) and keeps three running sums -
+// sum w_k, sum w_k bin_k and, for softmax, the running maximum (w_k = exp(l_k - max), both sums rescaled when the maximum grows).
+// The bin table sits in LDS.  pred = sum w_k bin_k / sum w_k: the expectation over the bin centres.  Byte-streaming, HBM-bound.
+__device__ __forceinline__ void depth_bin_acc(float x, float bin, int norm, float& mx, float& s, float& t) {
+  if (norm == DDP_DEPTH_NORM_SOFTMAX) {
+    if (x > mx) {
+      const float sc = expf(mx - x);          // (mx = -inf on the first logit: sc = 0)
+      s *= sc;
+      t *= sc;
+      mx = x;
+    }
+    const float e = expf(x - mx);
+    s += e;
+    t = fmaf(e, bin, t);
+  } else {
+    const float v = norm == DDP_DEPTH_NORM_LINEAR ? fmaxf(x, 0.f) + 0.1f : 1.0f / (1.0f + expf(-x));
+    s += v;
+    t = fmaf(v, bin, t);
+  }
+}
+__global__ void __launch_bounds__(256) k_depth_bins(DepthBinsArgs a) {
+  __shared__ float bins_s[DDP_MAX_DEPTH_BINS];
+  for (int k = threadIdx.x; k < DDP_MAX_DEPTH_BINS; k += blockDim.x) bins_s[k] = k < a.n_bins ? a.bins[k] : 0.f;
+  __syncthreads();
+  const int N = a.h * a.w;
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= a.R * N) return;
+  const float* p;
+  if (a.layout == 0) {
+    p = a.logits + size_t(m >> 5) * 8192 + (m & 31) * 4;
+  } else {
+    const int img = m / N, n = m - img * N;
+    const int i = n / a.w, j = n - i * a.w;
+    p = a.logits + (size_t(img) * (a.h + 2) * (a.w + 2) + size_t(i + 1) * (a.w + 2) + (j + 1)) * a.ld;
+  }
+  float mx = -INFINITY, s = 0.f, t = 0.f;
+  const int nq = (a.n_bins + 3) >> 2;
+  for (int q0 = 0; q0 < nq; q0 += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {           // eight 16-B loads in flight
+      const int q = q0 + u < nq ? q0 + u : nq - 1;
+      const size_t off = a.layout == 0 ? size_t(q >> 3) * 1024 + ((q >> 1) & 3) * 256 + (q & 1) * 128 : size_t(q) * 4;
+      v[u] = *reinterpret_cast<const f32x4*>(p + off);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k0 = (q0 + u) * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (k0 + e < a.n_bins) depth_bin_acc(v[u][e], bins_s[k0 + e], a.norm, mx, s, t);
+    }
+  }
+  a.pred[m] = t / s;
+}
+
+// fragment-major (R*h*w, 256) -> zero-bordered row-major grid: one wave per padded row (guard rows included), lane = 4 channels
+__global__ void __launch_bounds__(256) k_blk_to_pad(const float* __restrict__ in, float* __restrict__ out, int R, int h, int w,
+                                                    int guard, long rows) {
+  const int lane = threadIdx.x & 63;
+  const long r = long(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const long pr = r - guard;
+  const long per = long(h + 2) * (w + 2);
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (pr >= 0 && pr < long(R) * per) {
+    const int img = int(pr / per), rem = int(pr - img * per);
+    const int i = rem / (w + 2) - 1, j = rem % (w + 2) - 1;
+    if (i >= 0 && i < h && j >= 0 && j < w) v = *reinterpret_cast<const f32x4*>(in + blk_off256((img * h + i) * w + j, lane * 4));
+  }
+  *reinterpret_cast<f32x4*>(out + size_t(r) * 256 + lane * 4) = v;
 }
 
 // The depth step head on the chain path, WITHOUT a GEMM.  The concat-conv over cat[x, depth_t] has ONE noisy-map channel
@@ -2400,6 +2479,19 @@ int launch_feat_depth(const float* xproj, const float* wm, const float* d, float
 int launch_depth_update(const DepthUpdateArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_depth_update, dim3(cdiv(long(a.B_r) * a.h * a.w, 256)), dim3(256), 0, st, a);
   return check_launch("k_depth_update");
+}
+int launch_depth_bins(const DepthBinsArgs& a, hipStream_t st) {
+  if (a.n_bins < 1 || a.n_bins > DDP_MAX_DEPTH_BINS || (a.layout == 1 && (a.ld & 3))) {
+    set_error("depth bins: n_bins %d / ld %d", a.n_bins, a.ld);
+    return DDP_E_BADCFG;
+  }
+  hipLaunchKernelGGL(k_depth_bins, dim3(cdiv(long(a.R) * a.h * a.w, 256)), dim3(256), 0, st, a);
+  return check_launch("k_depth_bins");
+}
+int launch_blk_to_pad(const float* in_blk, float* out, int R, int h, int w, int guard, hipStream_t st) {
+  const long rows = long(R) * (h + 2) * (w + 2) + 2L * guard;
+  hipLaunchKernelGGL(k_blk_to_pad, dim3(cdiv(rows, 4)), dim3(256), 0, st, in_blk, out, R, h, w, guard, rows);
+  return check_launch("k_blk_to_pad");
 }
 int launch_depth_head(const DepthHeadArgs& a, hipStream_t st) {
   DepthHeadDev d;

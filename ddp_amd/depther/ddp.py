@@ -10,7 +10,7 @@ import torch.nn as nn
 from ..decode_heads.deformable_head_with_time import DeformableHeadWithTime as _SegHead
 from ..registry import DEPTHER, HEADS, build_backbone, build_head
 from ..segmentors.ddp import LearnedSinusoidalPosEmb, _Conv1x1, _SamplerMixin, _build_neck
-from .. import schedule
+from .. import _lib, schedule
 
 
 @HEADS.register_module(name='DepthDeformableHeadWithTime')
@@ -18,22 +18,40 @@ class DepthDeformableHeadWithTime(_SegHead):
     task = 'depth'
     head_conv = 'conv_depth'
 
-    def __init__(self, min_depth=1e-3, max_depth=None, scale_up=False, classify=False, use_eps=True, n_bins=None,
-                 init_inputs=False, **kwargs):
-        if classify:
-            raise ValueError('the regression branches of depth_pred are implemented (relu + eps, and scale_up: sigmoid * eps; '
-                             'decode_head.py:252-262); classify=True (binned depth, :236-250) is not - no DDP config uses it')
+    def __init__(self, min_depth=1e-3, max_depth=None, scale_up=False, classify=False, use_eps=True, n_bins=256,
+                 bins_strategy='UD', norm_strategy='linear', init_inputs=False, **kwargs):
         self.min_depth, self.max_depth = min_depth, max_depth
         self.scale_up, self.classify, self.use_eps = scale_up, classify, use_eps
+        self.n_bins = n_bins
+        if classify:
+            # binned depth (decode_head.py:91-96,233-250): conv_depth to n_bins channels, expectation over the bin centres
+            assert bins_strategy in ["UD", "SID"], "Support bins_strategy: UD, SID"
+            assert norm_strategy in ["linear", "softmax", "sigmoid"], "Support norm_strategy: linear, softmax, sigmoid"
+            if not isinstance(n_bins, int) or not 1 <= n_bins <= _lib.MAX_DEPTH_BINS:
+                raise ValueError(f'libddp_mi355x supports 1..{_lib.MAX_DEPTH_BINS} depth bins, got n_bins={n_bins!r}')
+            self.bins_strategy, self.norm_strategy = bins_strategy, norm_strategy
         kwargs.setdefault('num_classes', 1)
         super().__init__(**kwargs)
 
     def _make_head_conv(self):
-        self.conv_depth = nn.Conv2d(self.channels, 1, kernel_size=3, padding=1, stride=1)
+        self.conv_depth = nn.Conv2d(self.channels, self.n_bins if self.classify else 1, kernel_size=3, padding=1, stride=1)
+
+    def depth_bins(self):
+        """The bin centres of a binned head, by the reference's own torch call (decode_head.py:238-241; CPU fp32): 'UD' linspace,
+        'SID' logspace - base-10 exponents taken literally, as the reference does."""
+        if not self.classify:
+            return None
+        if self.bins_strategy == 'UD':
+            return torch.linspace(self.min_depth, self.max_depth, self.n_bins)
+        return torch.logspace(self.min_depth, self.max_depth, self.n_bins)
 
     def _engine_kwargs(self):
-        return dict(min_depth=self.min_depth, max_depth=self.max_depth if self.max_depth is not None else 80.0,
-                    depth_scale_up=bool(self.scale_up), depth_use_eps=bool(self.use_eps))
+        # the head alone: its own range is both the eps range and (unused by a head call) the x0 normalisation
+        hmax = self.max_depth if self.max_depth is not None else 80.0
+        kw = dict(min_depth=self.min_depth, max_depth=hmax, depth_scale_up=bool(self.scale_up), depth_use_eps=bool(self.use_eps))
+        if self.classify:
+            kw.update(depth_bins=self.depth_bins(), depth_norm=self.norm_strategy)
+        return kw
 
 
 @DEPTHER.register_module(name='DepthDDP')
@@ -86,20 +104,27 @@ class DDP(nn.Module, _SamplerMixin):
 
         head = self.decode_head
         su, ue = bool(getattr(head, 'scale_up', False)), bool(getattr(head, 'use_eps', True))
-        # the library takes ONE (min_depth, max_depth): the head's eps of depth_pred (decode_head.py:252-262) and the depther's x0
-        # normalisation (depther/ddp.py:239) read the same pair in every shipped config
-        hmin, hmax = getattr(head, 'min_depth', self.min_depth), getattr(head, 'max_depth', None)
-        if ue and ((not su and hmin != self.min_depth) or (su and hmax is not None and hmax != self.max_depth)):
-            raise ValueError(f'decode_head min / max depth ({hmin}, {hmax}) differ from the depther\'s ({self.min_depth}, {self.max_depth})')
+        # two depth ranges: the depther's normalises x0 (depther/ddp.py:240-241); the head's gives the regression head its eps and
+        # the binned head its bins (decode_head.py:239-241,258-266).  A head built without max_depth: the depther's stands in (its
+        # eps reads max_depth only with scale_up, where the reference would fail on None)
+        hmin = getattr(head, 'min_depth', self.min_depth)
+        hmax = getattr(head, 'max_depth', None)
+        hmin = self.min_depth if hmin is None else hmin
+        hmax = self.max_depth if hmax is None else hmax
+        classify = bool(getattr(head, 'classify', False))
+        bins = head.depth_bins() if classify else None
+        norm = head.norm_strategy if classify else 'linear'
 
         def factory():
             from ..engine import DDPEngine
             return DDPEngine(self.hot_path_state_dict(), 'depth', h=h, w=w, batch=b, randsteps=self.randsteps,
                              timesteps=self.timesteps, bit_scale=self.bit_scale, time_difference=self.time_difference,
-                             min_depth=self.min_depth, max_depth=self.max_depth, depth_scale_up=su, depth_use_eps=ue, device=x.device)
+                             min_depth=self.min_depth, max_depth=self.max_depth, depth_scale_up=su, depth_use_eps=ue,
+                             head_min_depth=hmin, head_max_depth=hmax, depth_bins=bins, depth_norm=norm, device=x.device)
         # keyed without the geometry: a new (b, h, w) re-uses the engine through set_geometry (no weight repacking)
+        bins_key = None if bins is None else (getattr(head, 'bins_strategy', None), head.n_bins, norm)
         eng = self._get_engine(('depth', str(x.device), self.timesteps, self.randsteps, self.bit_scale, self.time_difference,
-                                self.min_depth, self.max_depth, su, ue), factory, geometry=(b, h, w))
+                                self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key), factory, geometry=(b, h, w))
         return eng.sample(x.contiguous().float(), noise.contiguous().float())
 
     def _decode_head_forward_test(self, x, t, img_metas=None):

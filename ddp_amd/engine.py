@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from . import schedule
 
+DEPTH_NORMS = {'linear': _lib.DEPTH_NORM_LINEAR, 'softmax': _lib.DEPTH_NORM_SOFTMAX, 'sigmoid': _lib.DEPTH_NORM_SIGMOID}
 TASKS = {'seg': _lib.TASK_SEG, 'depth': _lib.TASK_DEPTH, 'bev': _lib.TASK_BEV}
 SAMPLERS = {'ddim': _lib.SAMPLER_DDIM, 'ddpm': _lib.SAMPLER_DDPM}
 GEMM_MODES = {'f32': _lib.GEMM_F32_MFMA, 'bf16x3': _lib.GEMM_BF16X3}
@@ -61,8 +62,14 @@ class PackedWeights:
     """All hot-path parameters in ONE flat fp32 device buffer (256-byte aligned sub-tensors): a
     single allocation, a single RCCL broadcast, and stable pointers for the ``ddp_weights`` table."""
 
-    def __init__(self, state_dict, task, num_layers, device, head_prefix='decode_head.'):
+    def __init__(self, state_dict, task, num_layers, device, head_prefix='decode_head.', depth_bins=None):
+        """``depth_bins``: (n_bins) bin centres of a binned depth head (``classify=True``), stored after the parameters."""
         top, layers = hot_path_keys(task, num_layers, head_prefix)
+        if depth_bins is not None:
+            if task != 'depth':
+                raise ValueError('depth_bins belong to a depth head')
+            state_dict = dict(state_dict, **{'<depth_bins>': torch.as_tensor(depth_bins, dtype=torch.float32).reshape(-1)})
+            top = top + [('depth_bins', '<depth_bins>')]
         entries = []
         for f, k in top:
             entries.append((None, f, k))
@@ -85,6 +92,7 @@ class PackedWeights:
         self.offsets = offs
         self.task = task
         self.num_layers = num_layers
+        self.n_bins = state_dict['<depth_bins>'].numel() if depth_bins is not None else 0
         self.struct = self._build_struct()
 
     def _build_struct(self):
@@ -111,7 +119,11 @@ class DDPEngine:
                  head_hw=None, bev_input_scope=None, bev_output_scope=None, device=None, head_prefix='decode_head.',
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
-                 depth_use_eps=True):
+                 depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None):
+        """depth: ``min_depth`` / ``max_depth`` are the depther's range (x0 normalisation); ``head_min_depth`` / ``head_max_depth``
+        the decode head's (eps of the regression head; default: the depther's).  ``depth_bins`` (n_bins) = the bin centres of a
+        binned head (``classify=True``: conv_depth has n_bins outputs, ``depth_norm`` in 'linear' / 'softmax' / 'sigmoid'); with
+        ``weights`` given, the bins are the ones packed there."""
         self.lib = _lib.load(lib_path)
         if not torch.cuda.is_available():
             raise _lib.DdpError('no HIP device visible: ddp_amd has no CPU path')
@@ -119,7 +131,9 @@ class DDPEngine:
         self.task = task
         num_layers = count_layers(state_dict, head_prefix) if weights is None else weights.num_layers
         self.weights = weights if weights is not None else PackedWeights(state_dict, task, num_layers, self.device,
-                                                                        head_prefix)
+                                                                        head_prefix, depth_bins=depth_bins)
+        if depth_norm not in DEPTH_NORMS:
+            raise ValueError(f'depth_norm must be one of {sorted(DEPTH_NORMS)}, got {depth_norm!r}')
         cfg = _lib.DdpCfg()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.task = TASKS[task]
@@ -155,8 +169,13 @@ class DDPEngine:
             nchw_head = os.environ.get('DDP_NCHW_HEAD', '1') != '0'
         cfg.flags = ((0 if fused_layer else _lib.FLAG_UNFUSED_LAYER) | (0 if fused_prologue else _lib.FLAG_UNFUSED_PROLOGUE) |
                      (0 if fused_tail else _lib.FLAG_UNFUSED_TAIL) | (0 if nchw_head else _lib.FLAG_SB_HEAD))
-        if task == 'depth':        # head variants of depth_pred (decode_head.py:252-262)
+        if task == 'depth' and self.weights.n_bins:   # binned head (decode_head.py:233-250): scale_up / use_eps play no part
+            cfg.depth_n_bins, cfg.depth_norm = self.weights.n_bins, DEPTH_NORMS[depth_norm]
+        elif task == 'depth':      # head variants of depth_pred (decode_head.py:252-262)
             cfg.flags |= (_lib.FLAG_DEPTH_SCALE_UP if depth_scale_up else 0) | (0 if depth_use_eps else _lib.FLAG_DEPTH_NO_EPS)
+        if task == 'depth':        # the head's own depth range (eps); the depther's pair below normalises x0
+            cfg.head_min_depth = min_depth if head_min_depth is None else head_min_depth
+            cfg.head_max_depth = max_depth if head_max_depth is None else head_max_depth
         if record_x0:
             cfg.flags |= _lib.FLAG_RECORD_X0
         if force_x0:               # test instrument (seg): teacher forcing, see set_x0_decisions()

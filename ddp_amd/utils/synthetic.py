@@ -100,7 +100,7 @@ def time_mlp_state(gen, sd):
     sd['time_mlp.3.bias'] = _uniform(gen, (TIME_DIM,), 1.0 / math.sqrt(TIME_DIM))
 
 
-def make_state_dict(task='seg', num_classes=150, num_layers=6, feat_channels=256, seed=2, profile='init'):
+def make_state_dict(task='seg', num_classes=150, num_layers=6, feat_channels=256, seed=2, profile='init', n_bins=None):
     """Hot-path ``state_dict`` (CPU fp32) for ``task`` in {'seg', 'depth', 'bev'}.
 
     seg  : segmentation/mmseg/models/segmentors/ddp.py:78,92-112 + decode head
@@ -124,7 +124,12 @@ def make_state_dict(task='seg', num_classes=150, num_layers=6, feat_channels=256
         sd['embedding_table.weight'] = _normal(gen, (num_classes + 1, EMBED))
     for l in range(num_layers):
         encoder_layer_state(gen, f'decode_head.encoder.layers.{l}.', sd, profile)
-    if task == 'depth':
+    if task == 'depth' and n_bins:
+        # binned head (classify=True, decode_head.py:91-96): conv_depth to n_bins channels - logits of a few units, so that every
+        # normalisation strategy sees a non-trivial distribution over the bins
+        sd['decode_head.conv_depth.weight'] = _xavier(gen, n_bins, EMBED, 3, 3) * 4.0
+        sd['decode_head.conv_depth.bias'] = _normal(gen, (n_bins,), std=0.5)
+    elif task == 'depth':
         sd['decode_head.conv_depth.weight'] = _xavier(gen, 1, EMBED, 3, 3) * 4.0
         sd['decode_head.conv_depth.bias'] = _normal(gen, (1,), mean=2.0, std=0.1)
     else:

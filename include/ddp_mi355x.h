@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define DDP_ABI_VERSION 5
+#define DDP_ABI_VERSION 6
 #define DDP_MAX_LAYERS 12
 #define DDP_MAX_STEPS 64
 #define DDP_EMBED 256
@@ -59,6 +59,10 @@ enum { DDP_SAMPLER_DDIM = 0, DDP_SAMPLER_DDPM = 1 };
  *                       products run on the bf16 matrix cores with fp32 accumulation (error <= ~3 * 2^-24 per
  *                       product, i.e. fp32 round-off class), 417 TFLOP/s fp32-equivalent ceiling */
 enum { DDP_GEMM_F32_MFMA = 0, DDP_GEMM_BF16X3 = 1 };
+/* Binned depth head (ddp_cfg.depth_n_bins > 0; depth/depth/models/decode_heads/decode_head.py:233-250): how the n_bins logits of a
+ * pixel become the weights of the bin centres.  LINEAR: relu(l) + 0.1, / sum;  SOFTMAX: softmax;  SIGMOID: sigmoid(l), / sum. */
+enum { DDP_DEPTH_NORM_LINEAR = 0, DDP_DEPTH_NORM_SOFTMAX = 1, DDP_DEPTH_NORM_SIGMOID = 2 };
+#define DDP_MAX_DEPTH_BINS 256
 /* ddp_cfg.flags (diagnostics, bf16x3 engine): run the decoder layer / the head of a step as the separate tile GEMMs they
  * were fused from (identical arithmetic per contraction; used by same-box A/B runs and by the parity tests that keep
  * the unfused kernels covered).  UNFUSED_LAYER implies the unfused step head and seg tail as well.
@@ -110,6 +114,13 @@ typedef struct ddp_cfg {
   float bev_in_min[2], bev_in_max[2], bev_out_first[2], bev_out_step[2];
   int32_t gemm_mode;          /* DDP_GEMM_* */
   int32_t flags;              /* DDP_FLAG_* (0 = the product path) */
+  /* ---- ABI 6 (depth only; a zeroed field keeps the behaviour of ABI 5) ---- */
+  int32_t depth_n_bins;       /* 0: regression head (conv_depth to 1 channel); 1..DDP_MAX_DEPTH_BINS: binned head (classify=True):
+                                 conv_depth to n_bins channels, normalised over the bins (depth_norm), expectation over the bin
+                                 centres ddp_weights.depth_bins.  DDP_FLAG_DEPTH_SCALE_UP / _NO_EPS play no part there */
+  int32_t depth_norm;         /* DDP_DEPTH_NORM_* (binned head) */
+  float head_min_depth, head_max_depth; /* the decode head's depth range: eps of the regression head (decode_head.py:258-266).
+                                           0 / 0: the same as min_depth / max_depth, which keep normalising x0 (depther/ddp.py:240) */
 } ddp_cfg;
 
 typedef struct ddp_layer_weights {            /* decode_head.encoder.layers.<l>.* */
@@ -129,8 +140,11 @@ typedef struct ddp_weights {
   const float *time1_w, *time1_b;         /* (1024,17),(1024) time_mlp.1 */
   const float *time3_w, *time3_b;         /* (1024,1024),(1024) time_mlp.3 */
   const float *embedding;                 /* (K_cls+1,256) embedding_table.weight; NULL for depth */
-  const float *head_w, *head_b;           /* seg/bev conv_seg (K_cls,256),(K_cls); depth conv_depth (1,256,3,3),(1) */
+  const float *head_w, *head_b;           /* seg/bev conv_seg (K_cls,256),(K_cls); depth conv_depth (1,256,3,3),(1), binned depth
+                                             (n_bins,256,3,3),(n_bins) */
   ddp_layer_weights layers[DDP_MAX_LAYERS];
+  const float* depth_bins;                /* (n_bins) bin centres of the binned depth head (the caller evaluates the reference's
+                                             torch.linspace / torch.logspace); NULL otherwise */
 } ddp_weights;
 
 /* Host-computed per-step schedule scalars.  The cosine log-SNR is ill-conditioned at t = 1, so the
