@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "ddp_internal.h"
 
 namespace ddp {
@@ -81,43 +83,47 @@ struct Layout {
   size_t M0, M;   // tokens at (h,w) and at the head grid, over all B*r maps
   int ldl;        // row stride of logits / prob buffers
   // constants
-  float *tin, *u, *hid, *temb, *film, *aff, *lut, *wx, *wm, *wtap;
-  float *wcat[DDP_MAX_LAYERS], *bcat[DDP_MAX_LAYERS], *py[DDP_MAX_LAYERS], *px[DDP_MAX_LAYERS];
+  float *tin = nullptr, *u = nullptr, *hid = nullptr, *temb = nullptr, *film = nullptr, *aff = nullptr, *lut = nullptr,
+        *wx = nullptr, *wm = nullptr, *wtap = nullptr;
+  float *wcat[DDP_MAX_LAYERS] = {}, *bcat[DDP_MAX_LAYERS] = {}, *py[DDP_MAX_LAYERS] = {}, *px[DDP_MAX_LAYERS] = {};
   // activations
-  float *xproj, *mask, *pred, *feat0, *q, *q1, *v, *s, *samp, *hbuf, *logits, *prob, *snoise, *xtok;
+  float *xproj = nullptr, *mask = nullptr, *pred = nullptr, *feat0 = nullptr, *q = nullptr, *q1 = nullptr, *v = nullptr,
+        *s = nullptr, *samp = nullptr, *hbuf = nullptr, *logits = nullptr, *prob = nullptr, *snoise = nullptr, *xtok = nullptr;
   // bf16x3 mode: split weights and split fragment-major activations
   int b3;
-  unsigned char* x0_trace;       // DDP_FLAG_RECORD_X0: (K, M) argmax class of every step
+  unsigned char* x0_trace = nullptr;   // DDP_FLAG_RECORD_X0: (K, M) argmax class of every step
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
       wp_f1[DDP_MAX_LAYERS];
-  unsigned short *q_sb, *q1_sb, *s_sb, *h_sb, *in_sb;   // in_sb: mask / x / feat staging (row-major producers)
-  float* vpad;                                          // zero-padded value maps (R, hh+2, wh+2, 256) written by the layer kernel
-  size_t vpad_floats;
-  unsigned char* wstream[DDP_MAX_LAYERS];               // layer kernel: weight stream (stage images) per layer
-  float* bias_ext[DDP_MAX_LAYERS];                      //               fc1 bias | next value_proj bias | zeros
-  unsigned char* pro_stream;                            // step prologue: W_m (8 wide) + layer 0's value / sampling proj (11 tall)
-  float* pro_bias;                                      //                layer 0's value_proj bias at [1024, 1280)
-  float* ubuf;                                          // u = W_m . m_t, fp32 fragment-major (fused seg tails)
-  float* tlut;                                          // seg: (Kc + 1, 256) = LUT . W_m^T; bev (<= 8 classes): (2^Kc, 256) = LUT64 . W_m^T
-  float* lut64;                                         // bev (<= 8 classes): the 2^Kc x0 vectors of a pixel
-  float* wvs;                                           // depth: W_v0 w_m (256) | W_cat0 w_m (96): the rank-1 terms of the GEMM-free step head
-  float *xproj_f, *rs0, *rvpad;                         // depth chain (inside hbuf, unused by the bf16x3 engine otherwise): xproj fragment-major,
-                                                        // W_cat0 xproj (M, 96), zero-padded map of W_v0 xproj + b_v0; nullptr: does not fit
-  unsigned char* tail4_stream;                          // fused tail: conv_seg images + layer 0's 11 projection images
-  unsigned char* head7_stream;                          // first step's head from NCHW (k_layer MODE 7): W_m 8 wide + W_x 8 wide + 11
-  unsigned char* lt_stream;                             // last layer + tail (k_layer MODE 6): 72 stages of layer L-1 + tail4_stream
-  float* lt_bias;                                       //   fc1 bias of layer L-1 | layer 0's value_proj bias at [1024, 1280)
-  float* tail4_bias;                                    //             conv_seg bias | layer 0's value_proj bias at [1024, 1280)
-  unsigned char* tail_stream;                           // seg tail: conv_seg stage images (2 per 64 classes)
-  float* tail_bias;                                     //           conv_seg bias, zero padded
+  unsigned short *q_sb = nullptr, *q1_sb = nullptr, *s_sb = nullptr, *h_sb = nullptr,
+                 *in_sb = nullptr;                      // in_sb: mask / x / feat staging (row-major producers)
+  float* vpad = nullptr;                                // zero-padded value maps (R, hh+2, wh+2, 256) written by the layer kernel
+  size_t vpad_floats = 0;
+  unsigned char* wstream[DDP_MAX_LAYERS] = {};          // layer kernel: weight stream (stage images) per layer
+  float* bias_ext[DDP_MAX_LAYERS] = {};                 //               fc1 bias | next value_proj bias | zeros
+  unsigned char* pro_stream = nullptr;                  // step prologue: W_m (8 wide) + layer 0's value / sampling proj (11 tall)
+  float* pro_bias = nullptr;                            //                layer 0's value_proj bias at [1024, 1280)
+  float* ubuf = nullptr;                                // u = W_m . m_t, fp32 fragment-major (fused seg tails)
+  float* tlut = nullptr;                                // seg: (Kc + 1, 256) = LUT . W_m^T; bev (<= 8 classes): (2^Kc, 256) = LUT64 . W_m^T
+  float* lut64 = nullptr;                               // bev (<= 8 classes): the 2^Kc x0 vectors of a pixel
+  float* wvs = nullptr;                                 // depth: W_v0 w_m (256) | W_cat0 w_m (96): the rank-1 terms of the GEMM-free step head
+  float *xproj_f = nullptr, *rs0 = nullptr,             // depth chain (inside hbuf, unused by the bf16x3 engine otherwise): xproj fragment-major,
+        *rvpad = nullptr;                               // W_cat0 xproj (M, 96), zero-padded map of W_v0 xproj + b_v0; nullptr: does not fit
+  unsigned char* tail4_stream = nullptr;                // fused tail: conv_seg images + layer 0's 11 projection images
+  unsigned char* head7_stream = nullptr;                // first step's head from NCHW (k_layer MODE 7): W_m 8 wide + W_x 8 wide + 11
+  unsigned char* lt_stream = nullptr;                   // last layer + tail (k_layer MODE 6): 72 stages of layer L-1 + tail4_stream
+  float* lt_bias = nullptr;                             //   fc1 bias of layer L-1 | layer 0's value_proj bias at [1024, 1280)
+  float* tail4_bias = nullptr;                          //             conv_seg bias | layer 0's value_proj bias at [1024, 1280)
+  unsigned char* tail_stream = nullptr;                 // seg tail: conv_seg stage images (2 per 64 classes)
+  float* tail_bias = nullptr;                           //           conv_seg bias, zero padded
   // binned depth head (cfg->depth_n_bins > 0): conv_depth to n_bins channels + k_depth_bins
   int nbins, bins_ld, bins_guard;
-  float *bins_tab, *bins_bias, *bins_wpack;             // bin centres, conv bias (256, zero padded), weights tap-major (256, 2304)
-  unsigned short* bins_wsplit;                          // bf16x3: split planes of bins_wpack
-  unsigned char* bins_stream;                           // bf16x3: the 72 stage images of the implicit 3x3 GEMM
-  float *bins_in, *bins_logits;                         // fp32 engine: zero-bordered grid of the layer output; logits (see carve)
+  float *bins_tab = nullptr, *bins_bias = nullptr,      // bin centres, conv bias (256, zero padded),
+        *bins_wpack = nullptr;                          // weights tap-major (256, 2304)
+  unsigned short* bins_wsplit = nullptr;                // bf16x3: split planes of bins_wpack
+  unsigned char* bins_stream = nullptr;                 // bf16x3: the 72 stage images of the implicit 3x3 GEMM
+  float *bins_in = nullptr, *bins_logits = nullptr;     // fp32 engine: zero-bordered grid of the layer output; logits (see carve)
   size_t const_bytes;   // region A (model constants): a prefix of the workspace that does not depend on the geometry
   size_t total;
 };
@@ -293,21 +299,6 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->wvs = c->task == DDP_TASK_DEPTH ? cv.take(512) : nullptr;
     o->bins_wsplit = o->nbins ? reinterpret_cast<unsigned short*>(cv.take(size_t(256) * 2304 * 3 / 2)) : nullptr;
     o->bins_stream = o->nbins ? reinterpret_cast<unsigned char*>(cv.take(size_t(72) * 48 * 1024 / sizeof(float))) : nullptr;
-  } else {
-    o->tail_stream = nullptr;
-    o->tail_bias = nullptr;
-    o->pro_stream = nullptr;
-    o->pro_bias = nullptr;
-    o->tail4_stream = nullptr;
-    o->tail4_bias = nullptr;
-    o->head7_stream = nullptr;
-    o->lt_stream = nullptr;
-    o->lt_bias = nullptr;
-    o->tlut = nullptr;
-    o->lut64 = nullptr;
-    o->wvs = nullptr;
-    o->bins_wsplit = nullptr;
-    o->bins_stream = nullptr;
   }
   o->const_bytes = cv.off * sizeof(float);
   // ---- region B: everything that depends on the geometry (batch, r, map size): positional tables, activations
@@ -342,7 +333,6 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   // logits on that grid, rows of bins_ld floats
   o->bins_ld = (o->nbins + 3) / 4 * 4;
   o->bins_guard = o->w + 3;
-  o->bins_in = o->bins_logits = nullptr;
   if (o->nbins) {
     const size_t padded = size_t(o->R) * (o->h + 2) * (o->w + 2);
     if (o->b3) {
@@ -376,14 +366,8 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
       in_c = o->Cx;
     }
     o->in_sb = takesb(in_rows, in_c);
-  } else {
-    o->q_sb = o->q1_sb = o->s_sb = o->h_sb = o->in_sb = nullptr;
-    o->vpad = nullptr;
-    o->vpad_floats = 0;
-    o->ubuf = nullptr;
   }
   // depth chain: three loop-invariant tensors in the FFN scratch of the fp32 engine (Mp x 1024 floats, idle on the bf16x3 engine)
-  o->xproj_f = o->rs0 = o->rvpad = nullptr;
   if (o->b3 && c->task == DDP_TASK_DEPTH && o->r == 1) {
     const size_t need = Mp * 256 + align64(o->M * 96) + o->vpad_floats;
     if (need <= Mp * DDP_FFN && base) {                 // (a one-row map does not fit: its padded map is 3x the map - the GEMM head stays)
@@ -492,6 +476,30 @@ int prepare_geometry(const Layout& o, hipStream_t st) {
   return DDP_OK;
 }
 
+// a bias table of the layer kernel: b3_layer_bias_floats() zeros, then each segment copied in at its offset (src nullptr: stays zero)
+struct BiasSeg {
+  int at;
+  const float* src;
+  int n;
+};
+int bias_table(float* dst, std::initializer_list<BiasSeg> segs, const char* what, hipStream_t st) {
+  bool ok = hipMemsetAsync(dst, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) == hipSuccess;
+  for (const BiasSeg& s : segs)
+    ok = ok && (!s.src || hipMemcpyAsync(dst + s.at, s.src, size_t(s.n) * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess);
+  if (!ok) {
+    set_error("%s: bias table copy failed", what);
+    return DDP_E_LAUNCH;
+  }
+  return DDP_OK;
+}
+
+// layer l's value / sampling projections as 11 stage images from image `base` on: [Wv: 8 tall][Wcat: 2 tall + 1 split-K]
+int build_proj_images(const Layout& o, int l, unsigned char* stream, int base, hipStream_t st) {
+  DDP_TRY(launch_build_stages(o.wp_v[l].p, o.wp_v[l].comp_stride, 256, 256, 1, 4, 2, base, 0, 1, 2, stream, st));
+  DDP_TRY(launch_build_stages(o.wp_cat[l].p, o.wp_cat[l].comp_stride, 256, 96, 1, 1, 2, base + 8, 0, 1, 2, stream, st));
+  return launch_build_stages(o.wp_cat[l].p, o.wp_cat[l].comp_stride, 256, 96, 2, 1, 1, base + 10, 64, 0, 0, stream, st);
+}
+
 // model constants that do not depend on the schedule (region A)
 int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipStream_t st) {
   DDP_TRY(launch_pack_cols(w->transform_w, o.Cx + o.Cm, 0, 256, o.Cx, o.wx, st));
@@ -534,47 +542,25 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
       DDP_TRY(launch_split_weights(lw.ffn0_w, 256, DDP_FFN, 256, wr(o.wp_f0[l]), st));
       DDP_TRY(launch_split_weights(lw.ffn1_w, DDP_FFN, 256, DDP_FFN, wr(o.wp_f1[l]), st));
     }
-    if (c->task == DDP_TASK_SEG) {      // seg tail: conv_seg as tall stages of 64 classes, bias table
+    if (c->task == DDP_TASK_SEG) {
+      // seg tail: conv_seg as tall stages of 64 classes, bias table; fused tail (k_layer MODE 4): [conv_seg: 2 tall per 64 classes]
+      // [layer 0's Wv: 8 tall][Wcat: 2 tall + 1 split-K]
       const int nch = (o.Kc + 63) / 64;
       DDP_TRY(launch_build_stages(o.wp_head.p, o.wp_head.comp_stride, 256, o.Kc, 1, nch, 2, 0, 0, 1, 2, o.tail_stream, st));
-      if (hipMemsetAsync(o.tail_bias, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          (w->head_b && hipMemcpyAsync(o.tail_bias, w->head_b, size_t(o.Kc) * sizeof(float), hipMemcpyDeviceToDevice, st) !=
-                            hipSuccess)) {
-        set_error("tail bias copy failed");
-        return DDP_E_LAUNCH;
-      }
-    }
-    if (c->task == DDP_TASK_SEG) {      // fused tail (k_layer MODE 4): [conv_seg: 2 tall per 64 classes][layer 0's Wv: 8 tall][Wcat: 2 tall + 1 split-K]
-      const int nch = (o.Kc + 63) / 64;
+      DDP_TRY(bias_table(o.tail_bias, {{0, w->head_b, o.Kc}}, "seg tail", st));
       DDP_TRY(launch_build_stages(o.wp_head.p, o.wp_head.comp_stride, 256, o.Kc, 1, nch, 2, 0, 0, 1, 2, o.tail4_stream, st));
-      DDP_TRY(launch_build_stages(o.wp_v[0].p, o.wp_v[0].comp_stride, 256, 256, 1, 4, 2, 2 * nch, 0, 1, 2, o.tail4_stream, st));
-      DDP_TRY(launch_build_stages(o.wp_cat[0].p, o.wp_cat[0].comp_stride, 256, 96, 1, 1, 2, 2 * nch + 8, 0, 1, 2, o.tail4_stream, st));
-      DDP_TRY(launch_build_stages(o.wp_cat[0].p, o.wp_cat[0].comp_stride, 256, 96, 2, 1, 1, 2 * nch + 10, 64, 0, 0, o.tail4_stream, st));
-      if (hipMemsetAsync(o.tail4_bias, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          (w->head_b && hipMemcpyAsync(o.tail4_bias, w->head_b, size_t(o.Kc) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) ||
-          hipMemcpyAsync(o.tail4_bias + DDP_FFN, w->layers[0].value_proj_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, st) !=
-              hipSuccess) {
-        set_error("fused tail bias copy failed");
-        return DDP_E_LAUNCH;
-      }
+      DDP_TRY(build_proj_images(o, 0, o.tail4_stream, 2 * nch, st));
+      DDP_TRY(bias_table(o.tail4_bias, {{0, w->head_b, o.Kc}, {DDP_FFN, w->layers[0].value_proj_b, 256}}, "fused tail", st));
       // T = LUT . W_m^T: the noisy-map half of the concat-conv applied to each of the K + 1 possible x0 vectors (exact
       // fp32 products: the f32-input MFMA GEMM)
       DDP_TRY(launch_linear(o.lut, 256, false, o.wm, 256, nullptr, nullptr, 0, 0, 0, o.tlut, 256, o.Kc + 1, 256, 256, 0, st));
     }
-    {                                   // step prologue: [W_m: 8 wide stages][layer 0's Wv: 8 tall][layer 0's Wcat: 2 tall + 1 split-K]
-      // (depth has no W_m GEMM - one input channel - and uses images 8..18 only: k_layer MODE 3)
-      if (c->task != DDP_TASK_DEPTH)
-        DDP_TRY(launch_build_stages(o.wp_m.p, o.wp_m.comp_stride, 256, 256, 0, 1, 8, 0, 2, 1, 0, o.pro_stream, st));
-      DDP_TRY(launch_build_stages(o.wp_v[0].p, o.wp_v[0].comp_stride, 256, 256, 1, 4, 2, 8, 0, 1, 2, o.pro_stream, st));
-      DDP_TRY(launch_build_stages(o.wp_cat[0].p, o.wp_cat[0].comp_stride, 256, 96, 1, 1, 2, 16, 0, 1, 2, o.pro_stream, st));
-      DDP_TRY(launch_build_stages(o.wp_cat[0].p, o.wp_cat[0].comp_stride, 256, 96, 2, 1, 1, 18, 64, 0, 0, o.pro_stream, st));
-      if (hipMemsetAsync(o.pro_bias, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          hipMemcpyAsync(o.pro_bias + DDP_FFN, w->layers[0].value_proj_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, st) !=
-              hipSuccess) {
-        set_error("prologue bias copy failed");
-        return DDP_E_LAUNCH;
-      }
-    }
+    // step prologue: [W_m: 8 wide stages][layer 0's Wv: 8 tall][layer 0's Wcat: 2 tall + 1 split-K]
+    // (depth has no W_m GEMM - one input channel - and uses images 8..18 only: k_layer MODE 3)
+    if (c->task != DDP_TASK_DEPTH)
+      DDP_TRY(launch_build_stages(o.wp_m.p, o.wp_m.comp_stride, 256, 256, 0, 1, 8, 0, 2, 1, 0, o.pro_stream, st));
+    DDP_TRY(build_proj_images(o, 0, o.pro_stream, 8, st));
+    DDP_TRY(bias_table(o.pro_bias, {{DDP_FFN, w->layers[0].value_proj_b, 256}}, "prologue", st));
     if (o.head7_stream) {               // first step's head from NCHW (k_layer MODE 7): [W_m: 8 wide][W_x: 8 wide][layer 0's Wv, Wcat as above]
       DDP_TRY(launch_build_stages(o.wp_m.p, o.wp_m.comp_stride, 256, 256, 0, 1, 8, 0, 2, 1, 0, o.head7_stream, st));
       DDP_TRY(launch_build_stages(o.wp_x.p, o.wp_x.comp_stride, 256, 256, 0, 1, 8, 8, 2, 1, 0, o.head7_stream, st));
@@ -591,17 +577,10 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
       DDP_TRY(launch_build_stages(o.wp_o[l].p, o.wp_o[l].comp_stride, 256, 256, 0, 1, 8, 0, 2, 1, 0, sp, st));
       DDP_TRY(launch_build_stages(o.wp_f0[l].p, o.wp_f0[l].comp_stride, 256, DDP_FFN, 1, 16, 2, 8, 0, 1, 4, sp, st));
       DDP_TRY(launch_build_stages(o.wp_f1[l].p, o.wp_f1[l].comp_stride, DDP_FFN, 256, 0, 1, 32, 10, 4, 1, 0, sp, st));
-      if (hipMemsetAsync(o.bias_ext[l], 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          hipMemcpyAsync(o.bias_ext[l], lw.ffn0_b, DDP_FFN * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        set_error("bias table copy failed");
-        return DDP_E_LAUNCH;
-      }
+      DDP_TRY(bias_table(o.bias_ext[l], {{0, lw.ffn0_b, DDP_FFN}}, "layer", st));
       if (l + 1 < o.L) {
-        const ddp_layer_weights& nw = w->layers[l + 1];
-        DDP_TRY(launch_build_stages(o.wp_v[l + 1].p, o.wp_v[l + 1].comp_stride, 256, 256, 1, 4, 2, 72, 0, 1, 2, sp, st));
-        DDP_TRY(launch_build_stages(o.wp_cat[l + 1].p, o.wp_cat[l + 1].comp_stride, 256, 96, 1, 1, 2, 80, 0, 1, 2, sp, st));
-        DDP_TRY(launch_build_stages(o.wp_cat[l + 1].p, o.wp_cat[l + 1].comp_stride, 256, 96, 2, 1, 1, 82, 64, 0, 0, sp, st));
-        if (hipMemcpyAsync(o.bias_ext[l] + DDP_FFN, nw.value_proj_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, st) !=
+        DDP_TRY(build_proj_images(o, l + 1, sp, 72, st));
+        if (hipMemcpyAsync(o.bias_ext[l] + DDP_FFN, w->layers[l + 1].value_proj_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, st) !=
             hipSuccess) {
           set_error("bias table copy failed");
           return DDP_E_LAUNCH;
@@ -615,16 +594,13 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
       const size_t sb = size_t(48) * 1024;
       const int rows = c->task == DDP_TASK_DEPTH ? 9 : o.Kc;
       DDP_TRY(launch_build_stages(o.wp_head.p, o.wp_head.comp_stride, 256, rows, 1, 1, 2, 0, 0, 1, 2, o.tail_stream, st));
-      if (hipMemsetAsync(o.tail_bias, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          (c->task == DDP_TASK_BEV && w->head_b &&
-           hipMemcpyAsync(o.tail_bias, w->head_b, size_t(o.Kc) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) ||
-          hipMemcpyAsync(o.lt_stream, o.wstream[o.L - 1], 72 * sb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(o.lt_stream + 72 * sb, o.tail_stream, 2 * sb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemsetAsync(o.lt_bias, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          hipMemcpyAsync(o.lt_bias, w->layers[o.L - 1].ffn0_b, DDP_FFN * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      DDP_TRY(bias_table(o.tail_bias, {{0, c->task == DDP_TASK_BEV ? w->head_b : nullptr, o.Kc}}, "head tail", st));
+      if (hipMemcpyAsync(o.lt_stream, o.wstream[o.L - 1], 72 * sb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+          hipMemcpyAsync(o.lt_stream + 72 * sb, o.tail_stream, 2 * sb, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("layer + tail stream copy failed");
         return DDP_E_LAUNCH;
       }
+      DDP_TRY(bias_table(o.lt_bias, {{0, w->layers[o.L - 1].ffn0_b, DDP_FFN}}, "layer + tail", st));
     }
     if (o.wvs) {
       // depth chain: the rank-1 terms of the GEMM-free step head, W_v0 w_m and W_cat0 w_m (fp32 dot products)
@@ -643,13 +619,12 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
       const int nch = (o.Kc + 63) / 64;
       const size_t sb = size_t(48) * 1024;
       if (hipMemcpyAsync(o.lt_stream, o.wstream[o.L - 1], 72 * sb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(o.lt_stream + 72 * sb, o.tail4_stream, size_t(2 * nch + 11) * sb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemsetAsync(o.lt_bias, 0, size_t(b3_layer_bias_floats()) * sizeof(float), st) != hipSuccess ||
-          hipMemcpyAsync(o.lt_bias, w->layers[o.L - 1].ffn0_b, DDP_FFN * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(o.lt_bias + DDP_FFN, w->layers[0].value_proj_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+          hipMemcpyAsync(o.lt_stream + 72 * sb, o.tail4_stream, size_t(2 * nch + 11) * sb, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("layer + tail stream copy failed");
         return DDP_E_LAUNCH;
       }
+      DDP_TRY(bias_table(o.lt_bias, {{0, w->layers[o.L - 1].ffn0_b, DDP_FFN}, {DDP_FFN, w->layers[0].value_proj_b, 256}}, "layer + tail",
+                         st));
     }
   }
   return DDP_OK;
@@ -680,8 +655,7 @@ int depth_bins_head(const ddp_cfg* c, const Layout& o, float* pred, hipStream_t 
       DDP_TRY(launch_sb_to_row(o.q_sb, o.s, M, 256, st));
       DDP_TRY(launch_row_to_blk(o.s, o.q, M, st));
     }
-    SgemmProblem pr;
-    memset(&pr, 0, sizeof(pr));
+    SgemmProblem pr{};
     pr.A = o.q;
     pr.out = o.bins_logits;
     pr.stream = o.bins_stream;
@@ -720,6 +694,105 @@ float depth_head_eps(const ddp_cfg* c) {
   return (c->flags & DDP_FLAG_DEPTH_NO_EPS) ? (su ? 1.0f : 0.0f) : (su ? hi : lo);
 }
 
+// layer 0's value / sampling projections of the fragment-major Q (k_layer MODE 3 on the step prologue's 11 projection images), value
+// map to v_out.  The depth step head also sets the concat-conv fields (res, wm, dvec) and the fused update (upd).
+L0ProjLaunch l0proj_launch(const Layout& o, float* Q, int M, float* v_out) {
+  L0ProjLaunch pj{};
+  pj.Q = Q;
+  pj.stream = o.pro_stream + size_t(8) * 48 * 1024;
+  pj.bias_ext = o.pro_bias;
+  pj.M = M;
+  pj.v_out = v_out;
+  pj.samp_out = o.samp;
+  pj.py = o.py[0];
+  pj.px = o.px[0];
+  pj.n_tok = o.Nh;
+  pj.w = o.wh;
+  return pj;
+}
+
+// k_depth_update (decode_head.py:252-262): taps == nullptr when pred already holds the binned head's prediction
+DepthUpdateArgs depth_update_args(const ddp_cfg* c, const ddp_weights* w, const Layout& o, const float* taps, float* depth_t,
+                                  float* pred, const ddp_step& stp) {
+  DepthUpdateArgs a{};
+  a.taps = taps;
+  a.bias_ptr = w->head_b;
+  a.depth_t = depth_t;
+  a.pred = pred;
+  a.B_r = o.R;
+  a.h = o.h;
+  a.w = o.w;
+  a.min_depth = c->min_depth;
+  a.max_depth = c->max_depth;
+  a.bit_scale = c->bit_scale;
+  a.scale_up = (c->flags & DDP_FLAG_DEPTH_SCALE_UP) ? 1 : 0;
+  a.eps_depth = depth_head_eps(c);
+  a.st = stp;
+  return a;
+}
+
+// k_bev_update on the head GEMM's logits: probabilities set (first) or accumulated; mask == nullptr: no DDIM update
+BevUpdateArgs bev_update_args(const ddp_cfg* c, const ddp_weights* w, const Layout& o, float* mask, bool first, const ddp_step& stp) {
+  BevUpdateArgs a{};
+  a.logits = o.logits;
+  a.num_classes = o.Kc;
+  a.emb = w->embedding;
+  a.mask = mask;
+  a.prob = o.prob;
+  a.first = first;
+  a.R = o.R;
+  a.g = bev_geom(c);
+  a.threshold = c->threshold;
+  a.bit_scale = c->bit_scale;
+  a.st = stp;
+  return a;
+}
+
+// k_seg_update without DDPM step noise or x0 trace (the sampler adds them where it has them)
+SegUpdateArgs seg_update_args(const float* logits, int ldl, int num_classes, const float* lut, float* mask, float* prob, int prob_mode,
+                              int sampler, const ddp_step& stp, int rows) {
+  SegUpdateArgs a{};
+  a.logits = logits;
+  a.ldl = ldl;
+  a.num_classes = num_classes;
+  a.lut = lut;
+  a.mask = mask;
+  a.prob = prob;
+  a.prob_mode = prob_mode;
+  a.sampler = sampler;
+  a.st = stp;
+  a.rows = rows;
+  return a;
+}
+
+// the x0 trace of seg step s.  FORCE_X0: [0] = the caller's decisions (read), [1] = the step's own argmax (written); RECORD_X0
+// alone: [0] written
+struct X0Trace {
+  unsigned char* idx = nullptr;
+  const unsigned char* force = nullptr;
+};
+X0Trace x0_trace_of(const ddp_cfg* c, const Layout& o, int s) {
+  X0Trace t;
+  if (c->flags & DDP_FLAG_FORCE_X0) {
+    t.force = o.x0_trace + size_t(s) * o.M;
+    t.idx = o.x0_trace + size_t(o.K + s) * o.M;
+  } else if (c->flags & DDP_FLAG_RECORD_X0) {
+    t.idx = o.x0_trace + size_t(s) * o.M;
+  }
+  return t;
+}
+
+// the head convolution as a GEMM of the encoder output into o.logits: conv_seg (seg: rows of ldl, bev: of 32) or the nine taps of
+// the 3x3 conv_depth (rows of 32, no bias: k_depth_update adds it once per pixel)
+int head_gemm(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipStream_t st) {
+  const bool depth = c->task == DDP_TASK_DEPTH;
+  const int M = int(o.M), ld = c->task == DDP_TASK_SEG ? o.ldl : 32, n = depth ? 9 : o.Kc;
+  const float* bias = depth ? nullptr : w->head_b;
+  if (o.b3) return launch_b3_linear(o.q_sb, o.wp_head, bias, nullptr, 0, 0, 0, o.logits, ld, M, n, 256, st, TAG_HEAD);
+  return launch_linear(o.q, 256, true, depth ? o.wtap : w->head_w, 256, bias, nullptr, 0, 0, 0, o.logits, ld, M, n, 256, 0, st,
+                       TAG_HEAD);
+}
+
 // DetrTransformerEncoder over the fragment-major q (in/out); aff (L,512) = norms.1 affine x FiLM
 // `tail` (seg, u chain): the step's tail is fused into the LAST layer's kernel (k_layer MODE 6) - the caller launches no tail
 int encoder_forward(const ddp_weights* w, const Layout& o, const float* aff, hipStream_t st, bool l0_projected = false,
@@ -736,23 +809,7 @@ int encoder_forward(const ddp_weights* w, const Layout& o, const float* aff, hip
       if (own_proj && fused) {
         // layer 0 of a path without a fused step head (bev after its grid resampling, ddp_head_forward): the value /
         // sampling projections of the SB q as ONE launch of the layer kernel's P3 (k_layer MODE 3), padded value map out
-        L0ProjLaunch pj;
-        pj.Q = o.q;
-        pj.stream = o.pro_stream + size_t(8) * 48 * 1024;
-        pj.bias_ext = o.pro_bias;
-        pj.res = nullptr;
-        pj.res_rn = 0;
-        pj.wm = nullptr;
-        pj.dvec = nullptr;
-        pj.upd = nullptr;
-        pj.M = M;
-        pj.v_out = o.vpad;
-        pj.samp_out = o.samp;
-        pj.py = o.py[0];
-        pj.px = o.px[0];
-        pj.n_tok = o.Nh;
-        pj.w = o.wh;
-        DDP_TRY(launch_b3_l0proj(pj, st));
+        DDP_TRY(launch_b3_l0proj(l0proj_launch(o, o.q, M, o.vpad), st));
         own_proj = false;
       }
       if (own_proj) {
@@ -823,6 +880,305 @@ int encoder_forward(const ddp_weights* w, const Layout& o, const float* aff, hip
                                      st));
   }
   return DDP_OK;
+}
+
+// Which launches a ddp_sample call runs, resolved once from (cfg, Layout).  The conditions lean on facts established elsewhere:
+// validate() makes the head grid equal (h, w) for seg and depth; fused_pro implies fused_layer implies b3; carve gives
+// head7_stream, lt_stream, lut64 and rvpad only to the configs whose path can use them.
+struct Plan {
+  // seg + DDIM, one noisy map per image, 256 feature channels (head7_stream): the first step's head reads the caller's NCHW x and
+  // start noise directly (k_layer MODE 7) and writes xproj itself - no NCHW -> SB conversions, no x-projection GEMM
+  bool head7 = false;
+  // seg + DDIM on the layer kernel: conv_seg, argmax, softmax accumulation, x0 LUT and the DDIM update run as the "tail" mode of
+  // the layer kernel, which leaves m_{t_next} as the SB operand of the next step's concat-conv
+  bool seg_tail = false;
+  // seg tail + step prologue: the noisy map enters the loop only through u = W_m . m_t and its update is affine in (m_t, x0) with
+  // x0 one of K + 1 table rows, so steps 1 .. K-1 run NO concat-conv GEMM and keep no 256-channel map: the tail of step s updates
+  // u (u' = ua u + uc (W_m . LUT)[argmax]) and is at the same time the head of step s + 1 (q = W_x x + b + u', layer 0's
+  // projections): k_layer MODE 4.  Step 0 starts from the noise with the step-prologue kernel, the last step's tail has nothing
+  // to update.
+  bool u_chain = false;
+  // u chain: the step's tail runs inside the LAST layer's kernel (k_layer MODE 6) - the layer output never leaves the registers
+  bool lt_fused = false;
+  // depth (regression head) on the fused path: the step's last layer runs with the nine taps of conv_depth as its tail (k_layer
+  // MODE 9) - no head GEMM, no SB copy of the layer output - and the step's update runs in front of the next step's head.  (The
+  // binned head takes the route of DDP_FLAG_UNFUSED_TAIL: MODE 3 step head, a plain last layer, conv_depth + k_depth_bins,
+  // k_depth_update.)
+  bool depth_lt = false;
+  // depth chain (one noisy map per image - rvpad fits -, >= 2 layers): the step head without a GEMM.  Loop invariant, once per
+  // sample: xproj fragment-major (layer 0's residual operand), rvpad = W_v0 xproj + b_v0 as a padded map (layer 0's projection
+  // kernel run on xproj itself), rs0 = W_cat0 xproj; per step k_depth_head adds the rank-1 terms in the noisy depth (and runs the
+  // previous step's update)
+  bool depth_chain = false;
+  // bev (<= 8 classes: lut64) on the fused path: the last layer carries conv_seg as its tail (k_layer MODE 8), and the u chain runs:
+  // the grid transform and the concat-conv are linear, so resample(W_x x + b) is hoisted out of the loop (rx, row-major in o.s: the
+  // fused layers never touch that buffer), the noisy map is carried as u = W_m m (o.feat0, row-major at the map size) and follows
+  // the DDIM update through the 2^K-row table T = LUT64 . W_m^T - per step: u update, q = rx + resample(u), layer 0's projections;
+  // no GEMM at the map size after u_0
+  bool bev_chain = false;
+};
+
+Plan plan_of(const ddp_cfg* c, const Layout& o) {
+  const bool seg_ddim = c->task == DDP_TASK_SEG && c->sampler == DDP_SAMPLER_DDIM;
+  // the step's last layer with the head convolution as its tail (k_layer MODE 6 / 8 / 9)
+  const bool lt = o.fused_pro && o.lt_stream && !(c->flags & DDP_FLAG_UNFUSED_TAIL);
+  Plan p;
+  p.head7 = seg_ddim && o.fused_pro && o.r == 1 && o.head7_stream && !(c->flags & DDP_FLAG_SB_HEAD) && !((size_t(o.M) * 256) >> 32);
+  p.seg_tail = seg_ddim && o.fused_layer;
+  p.u_chain = p.seg_tail && o.fused_pro;
+  p.lt_fused = p.u_chain && lt;
+  p.depth_lt = c->task == DDP_TASK_DEPTH && lt && !o.nbins;
+  p.depth_chain = p.depth_lt && o.rvpad && o.L >= 2;
+  p.bev_chain = c->task == DDP_TASK_BEV && lt && o.lut64;
+  return p;
+}
+
+// the segmentation sampler after the xproj hoist: noise staging, K steps, reduction
+int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, const Plan& p, const Layout& o, const float* d_x,
+               const float* d_noise, const float* d_step_noise, float* d_out, hipStream_t st) {
+  const int M = int(o.M), M0 = int(o.M0);
+  if (p.head7) {
+    // (the first step's head reads d_noise itself)
+  } else if (p.seg_tail) {
+    DDP_TRY(launch_nchw_to_sb(d_noise, o.in_sb, o.R, 256, o.N, st));    // the noisy map only ever exists as SB on this path
+  } else {
+    DDP_TRY(launch_nchw_to_tok(d_noise, o.mask, o.R, 256, o.N, st));
+  }
+  for (int s = 0; s < o.K; ++s) {
+    const ddp_step& sp = steps[s];
+    const float* aff = o.aff + size_t(s) * o.L * 512;
+    // feat = transform(cat[x, mask_t])
+    if (o.b3 && !p.seg_tail) DDP_TRY(launch_row_to_sb(o.mask, 256, o.in_sb, M0, 256, st));
+    if (p.u_chain && s > 0) {
+      // the previous step's fused tail already wrote q (SB) and layer 0's value map / sampling table
+    } else if (o.fused_pro) {
+      // q = W_m m_t + xproj -> SB, layer 0's value / sampling projections: one persistent kernel
+      PrologueLaunch pl{};
+      pl.mask_sb = o.in_sb;
+      pl.Q = o.q;
+      pl.stream = o.pro_stream;
+      pl.bias_ext = o.pro_bias;
+      pl.res = o.xproj;
+      pl.res_rn = o.r > 1 ? o.r * o.N : 0;
+      pl.ubuf = p.u_chain && o.K > 1 ? o.ubuf : nullptr;
+      pl.M = M0;
+      pl.v_out = o.vpad;
+      pl.samp_out = o.samp;
+      pl.py = o.py[0];
+      pl.px = o.px[0];
+      pl.n_tok = o.Nh;
+      pl.w = o.wh;
+      if (p.head7) {
+        pl.mask_sb = nullptr;
+        pl.res_frag = 1;
+        pl.stream = o.head7_stream;
+        DDP_TRY(launch_b3_head_nchw(pl, d_noise, d_x, w->transform_b, st));
+      } else {
+        DDP_TRY(launch_b3_prologue(pl, st));
+      }
+    } else if (o.b3) {
+      // separate concat-conv GEMM: SB for the tile-GEMM layers, and fp32 fragments for the layer kernels
+      DDP_TRY(launch_b3_linear_sb(o.in_sb, o.wp_m, nullptr, o.xproj, 256, o.r * o.N, o.N, o.q_sb, o.fused_layer ? o.q : nullptr, M0,
+                                  256, 256, 0, st, TAG_FEAT));
+    } else {
+      DDP_TRY(launch_linear_blk(o.mask, 256, false, o.wm, 256, nullptr, o.xproj, 256, o.r * o.N, o.N, o.q, M0, 256, 256, 0, st));
+    }
+    const X0Trace x0 = x0_trace_of(c, o, s);
+    TailLaunch tl{};
+    if (p.seg_tail) {
+      tl.Q = o.q;
+      tl.stream = o.tail_stream;
+      tl.bias_ext = o.tail_bias;
+      tl.lut = o.lut;
+      // accumulation: softmax summed over the steps; otherwise the last step's scores are the output
+      tl.prob = c->accumulation ? o.prob : o.logits;
+      tl.prob_mode = c->accumulation ? (s == 0 ? 1 : 2) : (s == o.K - 1 ? 3 : 0);
+      tl.mask_sb = p.u_chain ? nullptr : o.in_sb;
+      tl.fuse_next = p.u_chain && s + 1 < o.K;
+      if (tl.fuse_next) {
+        tl.stream = o.tail4_stream;
+        tl.bias_ext = o.tail4_bias;
+        tl.ubuf = o.ubuf;
+        tl.tlut = o.tlut;
+        tl.res = o.xproj;
+        tl.res_rn = o.r > 1 ? o.r * o.N : 0;
+        // written fragment-major by the first step's head (k_layer MODE 7): one coalesced 1-KiB load per (t, g) in the tail instead of
+        // 32 rows x 32 B (same box: head 0.62 -> 0.59 ms, tail -0.006 ms, +0.15 % on the batch; profiles/r05h_ab_xproj_frag.txt)
+        tl.res_frag = p.head7 ? 1 : 0;
+        tl.v_out = o.vpad;
+        tl.samp_out = o.samp;
+        tl.py = o.py[0];
+        tl.px = o.px[0];
+        tl.n_tok = o.Nh;
+        tl.w = o.wh;
+      }
+      tl.x0_force = x0.force;
+      tl.x0_idx = x0.idx;
+      tl.M = M;
+      tl.num_classes = o.Kc;
+      tl.ldl = o.ldl;
+      tl.alpha = sp.alpha;
+      tl.sigma = sp.sigma;
+      tl.alpha_next = sp.alpha_next;
+      tl.sigma_next = sp.sigma_next;
+    }
+    // layer 0's projections come from the step head on the prologue path; the tail reads the fp32 layer output, a head GEMM its SB copy
+    DDP_TRY(encoder_forward(w, o, aff, st, /*l0_projected=*/o.fused_pro, /*sb_out=*/!p.seg_tail, p.lt_fused ? &tl : nullptr));
+    if (p.seg_tail) {
+      if (!p.lt_fused) DDP_TRY(launch_b3_tail(tl, st));
+      continue;
+    }
+    DDP_TRY(head_gemm(c, w, o, st));
+    SegUpdateArgs a = seg_update_args(o.logits, o.ldl, o.Kc, o.lut, o.mask, o.prob, c->accumulation ? (s == 0 ? 1 : 2) : 0, c->sampler,
+                                      sp, M);
+    a.x0_force = x0.force;
+    a.x0_idx = x0.idx;
+    if (c->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
+      DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
+      a.step_noise = o.snoise;
+    }
+    DDP_TRY(launch_seg_update(a, st));
+  }
+  // reduction over (steps x r) and token-major -> NCHW (ddp.py:243-245); the layer kernel's tails leave the scores fragment-major
+  const int frag_nch = p.seg_tail ? (o.Kc + 63) / 64 : 0;
+  if (c->accumulation) return launch_finalize_nchw(o.prob, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st, frag_nch);
+  return launch_finalize_nchw(o.logits, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r), st, frag_nch);
+}
+
+// the depth sampler after the xproj hoist: noise staging, loop invariants of the chain, K steps, mean over r
+int sample_depth(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, const Plan& p, const Layout& o, const float* d_noise,
+                 float* d_out, hipStream_t st) {
+  const int M0 = int(o.M0);
+  if (hipMemcpyAsync(o.mask, d_noise, size_t(M0) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    set_error("noise copy failed");
+    return DDP_E_LAUNCH;
+  }
+  DepthHeadArgs ha{};
+  if (p.depth_chain) {
+    DDP_TRY(launch_row_to_blk(o.xproj, o.xproj_f, M0, st));
+    // (its sample table, that of a zero depth, is overwritten by the first step's head)
+    DDP_TRY(launch_b3_l0proj(l0proj_launch(o, o.xproj_f, M0, o.rvpad), st));
+    DDP_TRY(launch_row_to_sb(o.xproj, 256, o.in_sb, M0, 256, st));
+    DDP_TRY(launch_b3_linear(o.in_sb, o.wp_cat[0], nullptr, nullptr, 0, 0, 0, o.rs0, 96, M0, 96, 256, st, TAG_SAMP));
+    ha.rvpad = o.rvpad;
+    ha.rs = o.rs0;
+    ha.wv = o.wvs;
+    ha.ws = o.wvs + 256;
+    ha.py = o.py[0];
+    ha.px = o.px[0];
+    ha.dvec = o.mask;
+    ha.v_out = o.vpad;
+    ha.samp_out = o.samp;
+    ha.R = o.R;
+    ha.h = o.h;
+    ha.w = o.w;
+  }
+  // the last layer's tail (depth_lt): the nine per-tap dot products of conv_depth, rows of 32, which k_depth_update sums
+  TailLaunch tl{};
+  tl.Q = o.q;
+  tl.M = int(o.M);
+  tl.num_classes = 9;
+  tl.kind = 2;
+  tl.prob = o.logits;
+  tl.prob_mode = 3;
+  tl.threshold = c->threshold;
+  tl.ldl = 32;
+  auto update_args = [&](const ddp_step& stp) { return depth_update_args(c, w, o, o.nbins ? nullptr : o.logits, o.mask, o.pred, stp); };
+  for (int s = 0; s < o.K; ++s) {
+    const float* aff = o.aff + size_t(s) * o.L * 512;
+    // fused step boundary: the PREVIOUS step's DDIM update (from the taps its last layer's tail left) runs in front of this head
+    DepthUpdateArgs prev;
+    const DepthUpdateArgs* upd = nullptr;
+    if (p.depth_lt && s > 0) {
+      prev = update_args(steps[s - 1]);
+      upd = &prev;
+    }
+    if (p.depth_chain) {
+      ha.upd = upd;
+      DDP_TRY(launch_depth_head(ha, st));
+    } else if (o.fused_pro) {
+      // down conv over cat[x, depth_t] (depther/ddp.py:236-237) = hoisted x half + ONE depth column: q is formed inside
+      // the layer-0 projection kernel (k_layer MODE 3): no feat / SB-conversion / VALUE / SAMP launches
+      L0ProjLaunch pj = l0proj_launch(o, o.q, M0, o.vpad);
+      pj.res = o.xproj;
+      pj.res_rn = o.r > 1 ? o.r * o.N : 0;
+      pj.wm = o.wm;
+      pj.dvec = o.mask;
+      pj.upd = upd;
+      DDP_TRY(launch_b3_l0proj(pj, st));
+    } else {
+      DDP_TRY(launch_feat_depth(o.xproj, o.wm, o.mask, o.s, o.B, o.r, o.N, st));
+      DDP_TRY(publish_q(o, o.s, st));
+    }
+    // the step head projects layer 0 on the fused path; the fused tail and the binned head read the fp32 layer output, a head GEMM SB
+    DDP_TRY(encoder_forward(w, o, aff, st, /*l0_projected=*/o.fused_pro, /*sb_out=*/!(p.depth_lt || o.nbins), p.depth_lt ? &tl : nullptr,
+                            p.depth_chain));
+    if (p.depth_lt) {
+      // (the nine taps were written by the last layer's tail: k_layer MODE 9)
+    } else if (o.nbins) {
+      DDP_TRY(depth_bins_head(c, o, o.pred, st));
+    } else {
+      DDP_TRY(head_gemm(c, w, o, st));
+    }
+    // the update of every step but the last runs inside the next step's head (k_layer MODE 3) on the fused path; the last step's
+    // (and every step's on the other paths) here: it also leaves the metric depth prediction the output is made of
+    if (!(p.depth_lt && s + 1 < o.K)) DDP_TRY(launch_depth_update(update_args(steps[s]), st));
+  }
+  return launch_mean_r(o.pred, d_out, o.B, o.r, o.N, st);
+}
+
+// the BEV sampler after the xproj hoist: noise staging (u_0 on the chain), K steps, reduction
+int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, const Plan& p, const Layout& o, const float* d_noise,
+               float* d_out, hipStream_t st) {
+  const int M0 = int(o.M0);
+  const BevGeom geom = bev_geom(c);
+  unsigned char* code = reinterpret_cast<unsigned char*>(o.logits);            // (M) the step's x0 code per head-grid token
+  if (p.bev_chain) {
+    DDP_TRY(launch_bev_resample(o.xproj, o.s, o.B, geom, st));                  // rx = resample(W_x x + b), B maps
+    DDP_TRY(launch_nchw_to_sb(d_noise, o.in_sb, o.R, 256, o.N, st));
+    DDP_TRY(launch_b3_linear(o.in_sb, o.wp_m, nullptr, nullptr, 0, 0, 0, o.feat0, 256, M0, 256, 256, st, TAG_FEAT));   // u_0 = W_m . noise
+  } else {
+    DDP_TRY(launch_nchw_to_tok(d_noise, o.mask, o.R, 256, o.N, st));
+  }
+  // the last layer's tail (bev_chain): conv_seg + sigmoid, the probabilities accumulated and the step's x0 codes written
+  TailLaunch tl{};
+  tl.Q = o.q;
+  tl.M = int(o.M);
+  tl.num_classes = o.Kc;
+  tl.kind = 1;
+  tl.prob = o.prob;
+  tl.threshold = c->threshold;
+  tl.x0_idx = code;
+  tl.ldl = 32;
+  for (int s = 0; s < o.K; ++s) {
+    const ddp_step& sp = steps[s];
+    const float* aff = o.aff + size_t(s) * o.L * 512;
+    if (p.bev_chain) {
+      if (s > 0) {
+        // m' = alpha' x0 + sigma' (m - alpha x0) / max(sigma, 1e-8) (fusion_models/ddp.py:296-297) under W_m, with the PREVIOUS step's scalars
+        const ddp_step& pp = steps[s - 1];
+        const float ua = pp.sigma_next / (pp.sigma > 1e-8f ? pp.sigma : 1e-8f);
+        DDP_TRY(launch_bev_u_update(o.feat0, code, o.tlut, o.R, geom, ua, pp.alpha_next - pp.alpha * ua, st));
+      }
+      DDP_TRY(launch_bev_q(o.feat0, o.s, o.q, o.R, o.r, geom, st));
+    } else {
+      // feat = transform(cat[x, mask_t]) on the map, then the grid transform to the head grid
+      if (o.b3) {
+        DDP_TRY(launch_row_to_sb(o.mask, 256, o.in_sb, M0, 256, st));
+        DDP_TRY(launch_b3_linear(o.in_sb, o.wp_m, nullptr, o.xproj, 256, o.r * o.N, o.N, o.feat0, 256, M0, 256, 256, st, TAG_XPROJ));
+      } else {
+        DDP_TRY(launch_linear(o.mask, 256, false, o.wm, 256, nullptr, o.xproj, 256, o.r * o.N, o.N, o.feat0, 256, M0, 256, 256, 0, st));
+      }
+      DDP_TRY(launch_bev_resample(o.feat0, o.s, o.R, geom, st));
+      DDP_TRY(publish_q(o, o.s, st));
+    }
+    tl.prob_mode = s == 0 ? 1 : 2;
+    DDP_TRY(encoder_forward(w, o, aff, st, /*l0_projected=*/false, /*sb_out=*/!p.bev_chain, p.bev_chain ? &tl : nullptr));
+    if (p.bev_chain) continue;     // (the next step's head updates u from the codes the tail wrote)
+    DDP_TRY(head_gemm(c, w, o, st));
+    DDP_TRY(launch_bev_update(bev_update_args(c, w, o, o.mask, s == 0, sp), st));
+  }
+  return launch_finalize_nchw(o.prob, 32, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st);
 }
 
 }  // namespace
@@ -966,16 +1322,9 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout o;
   carve(cfg, static_cast<float*>(d_workspace), &o);
-  const int M = int(o.M), M0 = int(o.M0);
-  const BevGeom geom = bev_geom(cfg);
-
-  // seg + DDIM u chain with one noisy map per image: the first step's head reads the caller's NCHW x and start noise directly
-  // (k_layer MODE 7) and writes xproj itself - no NCHW -> SB conversions, no x-projection GEMM
-  const bool head7 = o.b3 && o.fused_layer && o.fused_pro && cfg->task == DDP_TASK_SEG && cfg->sampler == DDP_SAMPLER_DDIM &&
-                     o.h == o.hh && o.w == o.wh && o.r == 1 && o.head7_stream && !(cfg->flags & DDP_FLAG_SB_HEAD) &&
-                     !((size_t(o.M) * 256) >> 32);
+  const Plan p = plan_of(cfg, o);
   // loop-invariant half of the concat-conv: xproj = W_x x + b  (ddp.py:223-224 with the x columns hoisted)
-  if (head7) {
+  if (p.head7) {
     // (inside the first step's head)
   } else if (o.b3) {
     DDP_TRY(launch_nchw_to_sb(d_x, o.in_sb, o.B, o.Cx, o.N, st));       // NCHW -> split fragments in one pass
@@ -986,345 +1335,9 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     DDP_TRY(launch_linear(o.xtok, o.Cx, false, o.wx, o.Cx, weights->transform_b, nullptr, 0, 0, 0, o.xproj, 256, o.B * o.N,
                           256, o.Cx, 0, st, TAG_XPROJ));
   }
-  // seg + DDIM on the bf16x3 engine: conv_seg, argmax, softmax accumulation, x0 LUT and the DDIM update run as the
-  // "tail" mode of the layer kernel, which leaves m_{t_next} as the SB operand of the next step's concat-conv
-  const bool seg_tail = o.fused_layer && cfg->task == DDP_TASK_SEG && cfg->sampler == DDP_SAMPLER_DDIM &&
-                        o.h == o.hh && o.w == o.wh;
-  if (cfg->task == DDP_TASK_DEPTH) {
-    if (hipMemcpyAsync(o.mask, d_noise, size_t(M0) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      set_error("noise copy failed");
-      return DDP_E_LAUNCH;
-    }
-  } else if (head7) {
-    // (the first step's head reads d_noise itself)
-  } else if (seg_tail) {
-    DDP_TRY(launch_nchw_to_sb(d_noise, o.in_sb, o.R, 256, o.N, st));    // the noisy map only ever exists as SB on this path
-  } else if (cfg->task == DDP_TASK_BEV && o.b3 && o.fused_layer && o.fused_pro && o.lt_stream && o.lut64 &&
-             !(cfg->flags & DDP_FLAG_UNFUSED_TAIL)) {
-    // (bev u chain - the condition `bev_chain` below: the start noise goes straight into u_0 = W_m . noise)
-  } else {
-    DDP_TRY(launch_nchw_to_tok(d_noise, o.mask, o.R, 256, o.N, st));
-  }
-
-  // tasks whose concat-conv feeds the encoder directly (seg): the head of the step is one kernel with layer 0's projections
-  const bool pro_fused = o.fused_pro && cfg->task == DDP_TASK_SEG && o.h == o.hh &&
-                         o.w == o.wh;
-  // seg + DDIM with both fusions on: the noisy map enters the loop only through u = W_m . m_t and its update is affine in
-  // (m_t, x0) with x0 one of K + 1 table rows, so steps 1 .. K-1 run NO concat-conv GEMM and keep no 256-channel map:
-  // the tail of step s updates u (u' = ua u + uc (W_m . LUT)[argmax]) and is at the same time the head of step s + 1
-  // (q = W_x x + b + u', layer 0's projections): k_layer MODE 4.  Step 0 starts from the noise with the step-prologue
-  // kernel, the last step's tail has nothing to update.
-  const bool u_chain = seg_tail && pro_fused;
-  // bev / depth on the fused path: the step's LAST layer runs with the head convolution as its tail (k_layer MODE 8 / 9) - no head GEMM,
-  // no SB copy of the layer output.  bev with <= 8 classes additionally runs the u chain: the grid transform and the concat-conv are
-  // linear, so resample(W_x x + b) is hoisted out of the loop (rx, row-major in o.s: the fused layers never touch that buffer), the
-  // noisy map is carried as u = W_m m (o.feat0, row-major at the map size) and follows the DDIM update through the 2^K-row table
-  // T = LUT64 . W_m^T - per step: u update, q = rx + resample(u), layer 0's projections; no GEMM at the map size after u_0.
-  const bool lt_other = o.b3 && o.fused_layer && o.fused_pro && o.lt_stream && !(cfg->flags & DDP_FLAG_UNFUSED_TAIL);
-  // (the binned depth head takes the route of DDP_FLAG_UNFUSED_TAIL: MODE 3 step head, a plain last layer, conv_depth + k_depth_bins,
-  // k_depth_update)
-  const bool depth_lt = cfg->task == DDP_TASK_DEPTH && lt_other && !o.nbins;
-  // depth chain (one noisy map per image, >= 2 layers): the step head without a GEMM.  Loop invariant, once per sample: xproj
-  // fragment-major (layer 0's residual operand), rvpad = W_v0 xproj + b_v0 as a padded map (layer 0's projection kernel run on xproj
-  // itself), rs0 = W_cat0 xproj; per step k_depth_head adds the rank-1 terms in the noisy depth (and runs the previous step's update)
-  const bool depth_chain = depth_lt && o.rvpad && o.L >= 2;
-  if (depth_chain) {
-    DDP_TRY(launch_row_to_blk(o.xproj, o.xproj_f, M0, st));
-    L0ProjLaunch pj;
-    pj.Q = o.xproj_f;
-    pj.stream = o.pro_stream + size_t(8) * 48 * 1024;
-    pj.bias_ext = o.pro_bias;
-    pj.res = nullptr;
-    pj.res_rn = 0;
-    pj.wm = nullptr;
-    pj.dvec = nullptr;
-    pj.upd = nullptr;
-    pj.M = M0;
-    pj.v_out = o.rvpad;
-    pj.samp_out = o.samp;                                  // (the table of a zero depth: overwritten by the first step's head)
-    pj.py = o.py[0];
-    pj.px = o.px[0];
-    pj.n_tok = o.Nh;
-    pj.w = o.wh;
-    DDP_TRY(launch_b3_l0proj(pj, st));
-    DDP_TRY(launch_row_to_sb(o.xproj, 256, o.in_sb, M0, 256, st));
-    DDP_TRY(launch_b3_linear(o.in_sb, o.wp_cat[0], nullptr, nullptr, 0, 0, 0, o.rs0, 96, M0, 96, 256, st, TAG_SAMP));
-  }
-  const bool bev_chain = cfg->task == DDP_TASK_BEV && lt_other && o.lut64;
-  if (bev_chain) {
-    DDP_TRY(launch_bev_resample(o.xproj, o.s, o.B, geom, st));                      // rx = resample(W_x x + b), B maps
-    DDP_TRY(launch_nchw_to_sb(d_noise, o.in_sb, o.R, 256, o.N, st));
-    DDP_TRY(launch_b3_linear(o.in_sb, o.wp_m, nullptr, nullptr, 0, 0, 0, o.feat0, 256, M0, 256, 256, st, TAG_FEAT));   // u_0 = W_m . noise
-  }
-  unsigned char* bev_code = reinterpret_cast<unsigned char*>(o.logits);            // (M) the step's x0 code per head-grid token
-  auto depth_update_args = [&](const ddp_step& stp) {
-    DepthUpdateArgs a;
-    a.taps = o.nbins ? nullptr : o.logits;
-    a.bias = 0.f;
-    a.bias_ptr = weights->head_b;
-    a.depth_t = o.mask;
-    a.pred = o.pred;
-    a.B_r = o.R;
-    a.h = o.h;
-    a.w = o.w;
-    a.min_depth = cfg->min_depth;
-    a.max_depth = cfg->max_depth;
-    a.bit_scale = cfg->bit_scale;
-    a.scale_up = (cfg->flags & DDP_FLAG_DEPTH_SCALE_UP) ? 1 : 0;      // decode_head.py:252-262
-    a.eps_depth = depth_head_eps(cfg);
-    a.st = stp;
-    return a;
-  };
-  for (int s = 0; s < o.K; ++s) {
-    const ddp_step& sp = steps[s];
-    const float* aff = o.aff + size_t(s) * o.L * 512;
-    // feat = transform(cat[x, mask_t])
-    bool depth_head = false;
-    if (depth_chain) {
-      DepthHeadArgs ha;
-      ha.rvpad = o.rvpad;
-      ha.rs = o.rs0;
-      ha.wv = o.wvs;
-      ha.ws = o.wvs + 256;
-      ha.py = o.py[0];
-      ha.px = o.px[0];
-      ha.dvec = o.mask;
-      ha.v_out = o.vpad;
-      ha.samp_out = o.samp;
-      ha.R = o.R;
-      ha.h = o.h;
-      ha.w = o.w;
-      DepthUpdateArgs prev;
-      ha.upd = nullptr;
-      if (s > 0) {
-        prev = depth_update_args(steps[s - 1]);
-        ha.upd = &prev;
-      }
-      DDP_TRY(launch_depth_head(ha, st));
-      depth_head = true;
-    } else if (cfg->task == DDP_TASK_DEPTH && o.fused_pro) {
-      // down conv over cat[x, depth_t] (depther/ddp.py:236-237) = hoisted x half + ONE depth column: q is formed inside
-      // the layer-0 projection kernel (k_layer MODE 3): no feat / SB-conversion / VALUE / SAMP launches
-      L0ProjLaunch pj;
-      pj.Q = o.q;
-      pj.stream = o.pro_stream + size_t(8) * 48 * 1024;
-      pj.bias_ext = o.pro_bias;
-      pj.res = o.xproj;
-      pj.res_rn = o.r > 1 ? o.r * o.N : 0;
-      pj.wm = o.wm;
-      pj.dvec = o.mask;
-      pj.M = M0;
-      pj.v_out = o.vpad;
-      pj.samp_out = o.samp;
-      pj.py = o.py[0];
-      pj.px = o.px[0];
-      pj.n_tok = o.Nh;
-      pj.w = o.wh;
-      // fused step boundary: the PREVIOUS step's DDIM update (from the taps its last layer's tail left) runs in front of this head
-      DepthUpdateArgs prev;
-      pj.upd = nullptr;
-      if (depth_lt && s > 0) {
-        prev = depth_update_args(steps[s - 1]);
-        pj.upd = &prev;
-      }
-      DDP_TRY(launch_b3_l0proj(pj, st));
-      depth_head = true;
-    } else if (cfg->task == DDP_TASK_DEPTH) {
-      DDP_TRY(launch_feat_depth(o.xproj, o.wm, o.mask, o.s, o.B, o.r, o.N, st));
-      DDP_TRY(publish_q(o, o.s, st));
-    } else {
-      if (o.b3 && !seg_tail && !bev_chain) DDP_TRY(launch_row_to_sb(o.mask, 256, o.in_sb, M0, 256, st));
-      if (bev_chain) {
-        if (s > 0) {
-          // m' = alpha' x0 + sigma' (m - alpha x0) / max(sigma, 1e-8) (fusion_models/ddp.py:296-297) under W_m, with the PREVIOUS step's scalars
-          const ddp_step& pp = steps[s - 1];
-          const float ua = pp.sigma_next / (pp.sigma > 1e-8f ? pp.sigma : 1e-8f);
-          DDP_TRY(launch_bev_u_update(o.feat0, bev_code, o.tlut, o.R, geom, ua, pp.alpha_next - pp.alpha * ua, st));
-        }
-        DDP_TRY(launch_bev_q(o.feat0, o.s, o.q, o.R, o.r, geom, st));
-      } else if (cfg->task == DDP_TASK_BEV) {
-        if (o.b3)
-          DDP_TRY(launch_b3_linear(o.in_sb, o.wp_m, nullptr, o.xproj, 256, o.r * o.N, o.N, o.feat0, 256, M0, 256, 256, st,
-                                   TAG_XPROJ));
-        else
-          DDP_TRY(launch_linear(o.mask, 256, false, o.wm, 256, nullptr, o.xproj, 256, o.r * o.N, o.N, o.feat0, 256, M0, 256,
-                                256, 0, st));
-        DDP_TRY(launch_bev_resample(o.feat0, o.s, o.R, geom, st));
-        DDP_TRY(publish_q(o, o.s, st));
-      } else if (u_chain && s > 0) {
-        // the previous step's fused tail already wrote q (SB) and layer 0's value map / sampling table
-      } else if (o.b3 && pro_fused) {
-        // q = W_m m_t + xproj -> SB, layer 0's value / sampling projections: one persistent kernel
-        PrologueLaunch pl;
-        pl.mask_sb = o.in_sb;
-        pl.Q = o.q;
-        pl.stream = o.pro_stream;
-        pl.bias_ext = o.pro_bias;
-        pl.res = o.xproj;
-        pl.res_rn = o.r > 1 ? o.r * o.N : 0;
-        pl.ubuf = u_chain && o.K > 1 ? o.ubuf : nullptr;
-        pl.M = M0;
-        pl.v_out = o.vpad;
-        pl.samp_out = o.samp;
-        pl.py = o.py[0];
-        pl.px = o.px[0];
-        pl.n_tok = o.Nh;
-        pl.w = o.wh;
-        pl.res_frag = 0;
-        if (head7) {
-          pl.mask_sb = nullptr;
-          pl.res_frag = 1;
-          pl.stream = o.head7_stream;
-          DDP_TRY(launch_b3_head_nchw(pl, d_noise, d_x, weights->transform_b, st));
-        } else {
-          DDP_TRY(launch_b3_prologue(pl, st));
-        }
-      } else if (o.b3) {
-        // separate concat-conv GEMM: SB for the tile-GEMM layers, and fp32 fragments for the layer kernels
-        DDP_TRY(launch_b3_linear_sb(o.in_sb, o.wp_m, nullptr, o.xproj, 256, o.r * o.N, o.N, o.q_sb, o.fused_layer ? o.q : nullptr, M0,
-                                    256, 256, 0, st, TAG_FEAT));
-      } else {
-        DDP_TRY(launch_linear_blk(o.mask, 256, false, o.wm, 256, nullptr, o.xproj, 256, o.r * o.N, o.N, o.q, M0, 256, 256, 0,
-                                  st));
-      }
-    }
-    TailLaunch tl;
-    memset(&tl, 0, sizeof(tl));
-    if (seg_tail) {
-      tl.Q = o.q;
-      tl.stream = o.tail_stream;
-      tl.bias_ext = o.tail_bias;
-      tl.lut = o.lut;
-      // accumulation: softmax summed over the steps; otherwise the last step's scores are the output
-      tl.prob = cfg->accumulation ? o.prob : o.logits;
-      tl.prob_mode = cfg->accumulation ? (s == 0 ? 1 : 2) : (s == o.K - 1 ? 3 : 0);
-      tl.mask_sb = u_chain ? nullptr : o.in_sb;
-      tl.fuse_next = u_chain && s + 1 < o.K;
-      if (tl.fuse_next) {
-        tl.stream = o.tail4_stream;
-        tl.bias_ext = o.tail4_bias;
-        tl.ubuf = o.ubuf;
-        tl.tlut = o.tlut;
-        tl.res = o.xproj;
-        tl.res_rn = o.r > 1 ? o.r * o.N : 0;
-        // written fragment-major by the first step's head (k_layer MODE 7): one coalesced 1-KiB load per (t, g) in the tail instead of
-        // 32 rows x 32 B (same box: head 0.62 -> 0.59 ms, tail -0.006 ms, +0.15 % on the batch; profiles/r05h_ab_xproj_frag.txt)
-        tl.res_frag = head7 ? 1 : 0;
-        tl.v_out = o.vpad;
-        tl.samp_out = o.samp;
-        tl.py = o.py[0];
-        tl.px = o.px[0];
-        tl.n_tok = o.Nh;
-        tl.w = o.wh;
-      }
-      // FORCE_X0: [0] = the caller's decisions (read), [1] = the step's own argmax (written); RECORD_X0 alone: [0] written
-      tl.x0_force = (cfg->flags & DDP_FLAG_FORCE_X0) ? o.x0_trace + size_t(s) * o.M : nullptr;
-      tl.x0_idx = (cfg->flags & DDP_FLAG_FORCE_X0)   ? o.x0_trace + size_t(o.K + s) * o.M
-                  : (cfg->flags & DDP_FLAG_RECORD_X0) ? o.x0_trace + size_t(s) * o.M
-                                                      : nullptr;
-      tl.M = M;
-      tl.num_classes = o.Kc;
-      tl.ldl = o.ldl;
-      tl.alpha = sp.alpha;
-      tl.sigma = sp.sigma;
-      tl.alpha_next = sp.alpha_next;
-      tl.sigma_next = sp.sigma_next;
-    }
-    // u chain: the step's tail runs inside the LAST layer's kernel (k_layer MODE 6) - the layer output never leaves the registers
-    const bool lt_fused = (seg_tail && u_chain && o.lt_stream && !(cfg->flags & DDP_FLAG_UNFUSED_TAIL)) || depth_lt || bev_chain;
-    if (lt_fused && !seg_tail) {
-      tl.Q = o.q;
-      tl.M = M;
-      tl.num_classes = cfg->task == DDP_TASK_DEPTH ? 9 : o.Kc;
-      tl.kind = cfg->task == DDP_TASK_DEPTH ? 2 : 1;
-      tl.prob = cfg->task == DDP_TASK_DEPTH ? o.logits : o.prob;      // depth: the nine taps (rows of 32) k_depth_update sums
-      tl.prob_mode = cfg->task == DDP_TASK_DEPTH ? 3 : (s == 0 ? 1 : 2);
-      tl.threshold = cfg->threshold;
-      tl.x0_idx = bev_chain ? bev_code : nullptr;
-      tl.ldl = 32;
-    }
-    // (the binned depth head reads the fp32 layer output: no SB copy from the fused layers)
-    DDP_TRY(encoder_forward(weights, o, aff, st, pro_fused || depth_head, !(seg_tail || lt_fused || (o.nbins && o.fused_layer)),
-                            lt_fused ? &tl : nullptr, depth_chain));
-    if (lt_fused && cfg->task == DDP_TASK_BEV) {
-      // (probabilities accumulated and the step's x0 codes written by the fused tail; the next step's head updates u from them)
-    } else if (seg_tail) {
-      if (!lt_fused) DDP_TRY(launch_b3_tail(tl, st));
-    } else if (cfg->task == DDP_TASK_SEG) {
-      if (o.b3)
-        DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, weights->head_b, nullptr, 0, 0, 0, o.logits, o.ldl, M, o.Kc, 256, st,
-                                 TAG_HEAD));
-      else
-        DDP_TRY(launch_linear(o.q, 256, true, weights->head_w, 256, weights->head_b, nullptr, 0, 0, 0, o.logits, o.ldl, M,
-                              o.Kc, 256, 0, st, TAG_HEAD));
-      SegUpdateArgs a;
-      a.logits = o.logits;
-      a.ldl = o.ldl;
-      a.num_classes = o.Kc;
-      a.lut = o.lut;
-      a.mask = o.mask;
-      a.prob = o.prob;
-      a.prob_mode = cfg->accumulation ? (s == 0 ? 1 : 2) : 0;
-      a.step_noise = nullptr;
-      // FORCE_X0: [0] = the caller's decisions (read), [1] = the step's own argmax (written); RECORD_X0 alone: [0] written
-      a.x0_force = (cfg->flags & DDP_FLAG_FORCE_X0) ? o.x0_trace + size_t(s) * o.M : nullptr;
-      a.x0_idx = (cfg->flags & DDP_FLAG_FORCE_X0)   ? o.x0_trace + size_t(o.K + s) * o.M
-                  : (cfg->flags & DDP_FLAG_RECORD_X0) ? o.x0_trace + size_t(s) * o.M
-                                                      : nullptr;
-      a.sampler = cfg->sampler;
-      a.st = sp;
-      a.rows = M;
-      if (cfg->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
-        DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
-        a.step_noise = o.snoise;
-      }
-      DDP_TRY(launch_seg_update(a, st));
-    } else if (cfg->task == DDP_TASK_DEPTH) {
-      if (depth_lt) {
-        // (the nine taps were written by the last layer's tail: k_layer MODE 9)
-      } else if (o.nbins) {
-        DDP_TRY(depth_bins_head(cfg, o, o.pred, st));
-      } else if (o.b3) {
-        DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, st, TAG_HEAD));
-      } else {
-        DDP_TRY(launch_linear(o.q, 256, true, o.wtap, 256, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, 0, st, TAG_HEAD));
-      }
-      // the update of every step but the last runs inside the next step's head (k_layer MODE 3) on the fused path; the last step's
-      // (and every step's on the other paths) here: it also leaves the metric depth prediction the output is made of
-      if (!(depth_lt && s + 1 < o.K)) DDP_TRY(launch_depth_update(depth_update_args(sp), st));
-    } else {
-      if (o.b3)
-        DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, weights->head_b, nullptr, 0, 0, 0, o.logits, 32, M, o.Kc, 256, st, TAG_HEAD));
-      else
-        DDP_TRY(launch_linear(o.q, 256, true, weights->head_w, 256, weights->head_b, nullptr, 0, 0, 0, o.logits, 32, M, o.Kc,
-                              256, 0, st, TAG_HEAD));
-      BevUpdateArgs a;
-      a.logits = o.logits;
-      a.num_classes = o.Kc;
-      a.emb = weights->embedding;
-      a.mask = o.mask;
-      a.prob = o.prob;
-      a.first = (s == 0);
-      a.R = o.R;
-      a.g = geom;
-      a.threshold = cfg->threshold;
-      a.bit_scale = cfg->bit_scale;
-      a.st = sp;
-      DDP_TRY(launch_bev_update(a, st));
-    }
-  }
-  // reduction over (steps x r) and token-major -> NCHW (ddp.py:243-245)
-  if (cfg->task == DDP_TASK_SEG) {
-    if (cfg->accumulation)
-      DDP_TRY(launch_finalize_nchw(o.prob, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st, seg_tail ? (o.Kc + 63) / 64 : 0));
-    else
-      DDP_TRY(launch_finalize_nchw(o.logits, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r), st, seg_tail ? (o.Kc + 63) / 64 : 0));
-  } else if (cfg->task == DDP_TASK_DEPTH) {
-    DDP_TRY(launch_mean_r(o.pred, d_out, o.B, o.r, o.N, st));
-  } else {
-    DDP_TRY(launch_finalize_nchw(o.prob, 32, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st));
-  }
-  return DDP_OK;
+  if (cfg->task == DDP_TASK_SEG) return sample_seg(cfg, weights, steps, p, o, d_x, d_noise, d_step_noise, d_out, st);
+  if (cfg->task == DDP_TASK_DEPTH) return sample_depth(cfg, weights, steps, p, o, d_noise, d_out, st);
+  return sample_bev(cfg, weights, steps, p, o, d_noise, d_out, st);
 }
 
 int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_idx) {
@@ -1350,7 +1363,6 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout o;
   carve(cfg, static_cast<float*>(d_workspace), &o);
-  const int M = int(o.M);
   DDP_TRY(prepare_model(cfg, weights, o, st));
   DDP_TRY(prepare_geometry(o, st));
   const float* film = nullptr;
@@ -1371,55 +1383,13 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
   }
   DDP_TRY(publish_q(o, o.s, st));
   DDP_TRY(encoder_forward(weights, o, o.aff, st));
-  if (cfg->task == DDP_TASK_SEG) {
-    if (o.b3)
-      DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, weights->head_b, nullptr, 0, 0, 0, o.logits, o.ldl, M, o.Kc, 256, st, TAG_HEAD));
-    else
-      DDP_TRY(launch_linear(o.q, 256, true, weights->head_w, 256, weights->head_b, nullptr, 0, 0, 0, o.logits, o.ldl, M, o.Kc,
-                            256, 0, st, TAG_HEAD));
-    DDP_TRY(launch_finalize_nchw(o.logits, o.ldl, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st));
-  } else if (cfg->task == DDP_TASK_DEPTH && o.nbins) {
-    DDP_TRY(depth_bins_head(cfg, o, d_out, st));     // (R,1,h,w) == (R*N)
-  } else if (cfg->task == DDP_TASK_DEPTH) {
-    if (o.b3) DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, st, TAG_HEAD));
-    else DDP_TRY(launch_linear(o.q, 256, true, o.wtap, 256, nullptr, nullptr, 0, 0, 0, o.logits, 32, M, 9, 256, 0, st, TAG_HEAD));
-    DepthUpdateArgs a;
-    memset(&a, 0, sizeof(a));
-    a.taps = o.logits;
-    a.bias_ptr = weights->head_b;
-    a.depth_t = nullptr;
-    a.pred = d_out;  // (R,1,h,w) == (R*N)
-    a.B_r = o.R;
-    a.h = o.h;
-    a.w = o.w;
-    a.min_depth = cfg->min_depth;
-    a.max_depth = cfg->max_depth;
-    a.bit_scale = cfg->bit_scale;
-    a.scale_up = (cfg->flags & DDP_FLAG_DEPTH_SCALE_UP) ? 1 : 0;      // decode_head.py:252-262
-    a.eps_depth = depth_head_eps(cfg);
-    DDP_TRY(launch_depth_update(a, st));
-  } else {
-    if (o.b3)
-      DDP_TRY(launch_b3_linear(o.q_sb, o.wp_head, weights->head_b, nullptr, 0, 0, 0, o.logits, 32, M, o.Kc, 256, st, TAG_HEAD));
-    else
-      DDP_TRY(launch_linear(o.q, 256, true, weights->head_w, 256, weights->head_b, nullptr, 0, 0, 0, o.logits, 32, M, o.Kc, 256,
-                            0, st, TAG_HEAD));
-    BevUpdateArgs a;
-    memset(&a, 0, sizeof(a));
-    a.logits = o.logits;
-    a.num_classes = o.Kc;
-    a.emb = weights->embedding;
-    a.mask = nullptr;
-    a.prob = o.prob;
-    a.first = 1;
-    a.R = o.R;
-    a.g = bev_geom(cfg);
-    a.threshold = cfg->threshold;
-    a.bit_scale = cfg->bit_scale;
-    DDP_TRY(launch_bev_update(a, st));
-    DDP_TRY(launch_finalize_nchw(o.prob, 32, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st));
-  }
-  return DDP_OK;
+  // outputs (R,K,h,w) or, for depth, (R,1,h,w) == (R*N)
+  if (cfg->task == DDP_TASK_DEPTH && o.nbins) return depth_bins_head(cfg, o, d_out, st);
+  DDP_TRY(head_gemm(cfg, weights, o, st));
+  if (cfg->task == DDP_TASK_SEG) return launch_finalize_nchw(o.logits, o.ldl, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st);
+  if (cfg->task == DDP_TASK_DEPTH) return launch_depth_update(depth_update_args(cfg, weights, o, o.logits, nullptr, d_out, ddp_step{}), st);
+  DDP_TRY(launch_bev_update(bev_update_args(cfg, weights, o, nullptr, true, ddp_step{}), st));
+  return launch_finalize_nchw(o.prob, 32, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st);
 }
 
 int ddp_msda_forward(const float* d_value, const float* d_samp, float* d_out, int rows, int h, int w, void* stream) {
@@ -1586,21 +1556,8 @@ int ddp_ddim_update_seg(const float* d_logits, int ld_logits, int num_classes, c
     set_error("ddim_update_seg: bad arguments");
     return DDP_E_BADCFG;
   }
-  SegUpdateArgs a;
-  a.logits = d_logits;
-  a.ldl = ld_logits;
-  a.num_classes = num_classes;
-  a.lut = d_lut;
-  a.mask = d_mask;
-  a.prob = nullptr;
-  a.prob_mode = 0;
-  a.step_noise = nullptr;
-  a.x0_idx = nullptr;
-    a.x0_force = nullptr;
-  a.sampler = DDP_SAMPLER_DDIM;
-  a.st = *step;
-  a.rows = rows;
-  return launch_seg_update(a, static_cast<hipStream_t>(stream));
+  return launch_seg_update(seg_update_args(d_logits, ld_logits, num_classes, d_lut, d_mask, nullptr, 0, DDP_SAMPLER_DDIM, *step, rows),
+                           static_cast<hipStream_t>(stream));
 }
 
 int ddp_seg_x0_project(const float* d_scores, int batch, int num_classes, int n_pix, const float* d_embedding, float bit_scale,
@@ -2417,20 +2374,8 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
     const FcnPrepared prep = fcn_prepared_of(o, num_convs, s);
     DDP_TRY(fcn_head_tokens(convs, num_convs, dilation, weights->head_w, weights->head_b, Kc, o.temb + size_t(s) * DDP_TIME_DIM, R,
                             cfg->h, cfg->w, o.head, st, &prep));
-    SegUpdateArgs a;
-    a.logits = o.head.logits;
-    a.ldl = o.head.ldl;
-    a.num_classes = Kc;
-    a.lut = o.lut;
-    a.mask = o.mask;
-    a.prob = o.prob;
-    a.prob_mode = cfg->accumulation ? (s == 0 ? 1 : 2) : 0;
-    a.step_noise = nullptr;
-    a.x0_idx = nullptr;
-    a.x0_force = nullptr;
-    a.sampler = cfg->sampler;
-    a.st = sp;
-    a.rows = M;
+    SegUpdateArgs a = seg_update_args(o.head.logits, o.head.ldl, Kc, o.lut, o.mask, o.prob, cfg->accumulation ? (s == 0 ? 1 : 2) : 0,
+                                      cfg->sampler, sp, M);
     if (cfg->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
       DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M * 256, o.snoise, R, 256, N, st));
       a.step_noise = o.snoise;
