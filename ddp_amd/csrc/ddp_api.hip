@@ -360,8 +360,12 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->q1_sb = takesb(o->M, 256);
     o->s_sb = takesb(o->M, 256);
     o->h_sb = takesb(o->M, DDP_FFN);
+    // in_sb serves the noisy map / a layer input (max(M0, M) rows of 256) and x (B.N rows of Cx).  Both are written in whole 64-row
+    // blocks and read in whole 256-row GEMM tiles, so the PADDED sizes decide: with r >= 2 and 256 < Cx <= 256 r the smaller
+    // product can need the larger buffer (B.N = 100, r = 2, Cx = 512: 256 x 512 elements against 256 x 256)
+    auto rp256 = [](size_t rows) { return (rows + 255) / 256 * 256; };
     size_t in_rows = o->M0 > o->M ? o->M0 : o->M, in_c = 256;
-    if (size_t(o->B) * o->N * o->Cx > in_rows * in_c) {
+    if (rp256(size_t(o->B) * o->N) * o->Cx > rp256(in_rows) * in_c) {
       in_rows = size_t(o->B) * o->N;
       in_c = o->Cx;
     }

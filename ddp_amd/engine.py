@@ -130,6 +130,8 @@ class DDPEngine:
         self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
         self.task = task
         num_layers = count_layers(state_dict, head_prefix) if weights is None else weights.num_layers
+        if num_layers > _lib.MAX_LAYERS:     # (the weights table has DDP_MAX_LAYERS slots: refuse before packing, as validate() would)
+            raise _lib.DdpError(f'num_layers {num_layers} out of range: the library supports at most {_lib.MAX_LAYERS} encoder layers')
         self.weights = weights if weights is not None else PackedWeights(state_dict, task, num_layers, self.device,
                                                                         head_prefix, depth_bins=depth_bins)
         if depth_norm not in DEPTH_NORMS:

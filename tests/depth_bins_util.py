@@ -83,7 +83,7 @@ def depth_pred(mem, sd, head):
     """decode_head.py:233-266 on the encoder output (R,256,h,w)."""
     logit = F.conv2d(mem, sd['decode_head.conv_depth.weight'], sd['decode_head.conv_depth.bias'], padding=1)
     if head['classify']:
-        bins = bins_of(head).to(mem.device)
+        bins = bins_of(head).to(device=mem.device, dtype=mem.dtype)      # (fp64 evaluations: the bin centres follow the map's dtype)
         if head['norm_strategy'] == 'linear':
             p = torch.relu(logit) + 0.1
             p = p / p.sum(dim=1, keepdim=True)

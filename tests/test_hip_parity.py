@@ -347,11 +347,14 @@ def test_fused_and_unfused_step_boundary_depth_bev(dev, name):
         assert float(((a > 0.5) == (b > 0.5)).float().mean()) > 0.9995
 
 
-@pytest.mark.parametrize('task,h,w,r', [('depth', 5, 37, 1), ('depth', 9, 11, 2), ('bev', 12, 20, 1), ('bev', 16, 16, 2)])
+@pytest.mark.parametrize('task,h,w,r', [('depth', 5, 37, 1), ('depth', 9, 11, 2), ('bev', 12, 20, 1), ('bev', 16, 16, 2), ('depth', 1, 37, 1),
+                                        ('depth', 1, 37, 2)])
 def test_depth_bev_batch_equals_independent_runs(dev, task, h, w, r):
     """The round-6 step heads (k_depth_head, k_bev_q, k_bev_u_update, the tails of k_layer MODE 8 / 9, layer 0 as MODE 10) index
     tokens of ALL maps of a call; the reference-made fixtures are single-image.  Three images of an odd size in ONE call (token counts
-    that are no multiple of 32: groups straddle images) must give, image by image, the bits of three single-image calls."""
+    that are no multiple of 32: groups straddle images) must give, image by image, the bits of three single-image calls.
+    One-row maps included; the model here has 6 layers - the same check at L = 1 and L = 2, on one-column and one-pixel maps and with
+    the binned head is tests/test_config_space_gpu.py::test_batched_call_equals_single_image_calls."""
     from ddp_amd.engine import DDPEngine
     from ddp_amd.utils import synthetic
     B = 3
