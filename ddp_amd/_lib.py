@@ -10,7 +10,7 @@ from . import build as _build
 
 MAX_LAYERS = 12
 MAX_STEPS = 64
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 TASK_SEG, TASK_DEPTH, TASK_BEV = 0, 1, 2
 SAMPLER_DDIM, SAMPLER_DDPM = 0, 1
@@ -19,6 +19,7 @@ FLAG_UNFUSED_LAYER, FLAG_UNFUSED_PROLOGUE, FLAG_RECORD_X0, FLAG_GATHER_GUESS_ZER
 FLAG_DEPTH_SCALE_UP, FLAG_DEPTH_NO_EPS = 256, 512
 DEPTH_NORM_LINEAR, DEPTH_NORM_SOFTMAX, DEPTH_NORM_SIGMOID = 0, 1, 2
 MAX_DEPTH_BINS = 256
+BEV_MAX_PRESCALE_AREA = 16
 NECK_WEIGHTS_READY = 1
 
 _fp = C.c_void_p  # device pointers travel as raw addresses
@@ -36,6 +37,7 @@ class DdpCfg(C.Structure):
         ('bev_out_first', C.c_float * 2), ('bev_out_step', C.c_float * 2),
         ('gemm_mode', C.c_int32), ('flags', C.c_int32),
         ('depth_n_bins', C.c_int32), ('depth_norm', C.c_int32), ('head_min_depth', C.c_float), ('head_max_depth', C.c_float),
+        ('bev_prescale', C.c_float), ('bev_seg_kernel', C.c_int32),
     ]
 
 

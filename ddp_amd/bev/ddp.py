@@ -2,6 +2,8 @@
 head (bev/mmdet3d/models/heads/segm/deformable_head_with_time.py:57-235).  The reference class
 derives from BEVFusion (sensor encoders, out of scope); this one keeps only the diffusion members and
 ``ddim_sample(x: list[Tensor], head)``."""
+import math
+
 import torch
 import torch.nn as nn
 
@@ -18,20 +20,30 @@ class BEVDeformableHeadWithTime(_SegHead):
 
     def __init__(self, num_feature_levels=1, encoder=None, positional_encoding=None, classes=(), loss='focal',
                  grid_transform=None, in_channels=256, seg_conv_kernel=1, **kwargs):
-        if seg_conv_kernel != 1:
-            raise ValueError('only the 1x1 conv_seg of the DDP configs is implemented')
+        if seg_conv_kernel not in (1, 3):
+            # (the reference builds a 3x3 conv_seg for ANY value other than 1, reference :136-139; only 1 and 3 are accepted here)
+            raise ValueError(f'seg_conv_kernel must be 1 or 3, got {seg_conv_kernel!r}')
         self.classes = list(classes)
         self.loss = loss
         self.grid_transform = dict(grid_transform or {})
-        if self.grid_transform.get('prescale_factor', 1) != 1:
-            raise ValueError('prescale_factor != 1 is not implemented')
+        self.seg_conv_kernel = seg_conv_kernel
+        p = float(self.grid_transform.get('prescale_factor', 1))
+        if not (p > 0 and math.isfinite(p)):
+            raise ValueError(f'prescale_factor must be a positive float, got {p!r}')
+        self.prescale_factor = p
         super().__init__(num_feature_levels=num_feature_levels, encoder=encoder,
                          positional_encoding=positional_encoding, in_channels=[in_channels], channels=in_channels,
                          num_classes=len(self.classes), **kwargs)
 
+    def _make_head_conv(self):
+        # (reference :136-139; with 3 the parameter holder of a (K,256,3,3) checkpoint tensor)
+        k = self.seg_conv_kernel
+        self.conv_seg = nn.Conv2d(self.channels, self.num_classes, kernel_size=k, padding=k // 2)
+
     def _engine_kwargs(self):
         return dict(num_classes=self.num_classes, bev_input_scope=self.grid_transform['input_scope'],
-                    bev_output_scope=self.grid_transform['output_scope'])
+                    bev_output_scope=self.grid_transform['output_scope'], bev_prescale=self.prescale_factor,
+                    bev_seg_kernel=self.seg_conv_kernel)
 
     def forward(self, inputs, times, target=None):
         return super().forward(inputs, times)
@@ -80,7 +92,13 @@ class DDP(nn.Module, _SamplerMixin):
                              num_classes=self.num_classes, feat_channels=c, bit_scale=self.bit_scale,
                              time_difference=self.time_difference, noise_schedule=self.noise_schedule,
                              threshold=self.threshold, bev_input_scope=head.grid_transform['input_scope'],
-                             bev_output_scope=head.grid_transform['output_scope'], device=x0.device)
+                             bev_output_scope=head.grid_transform['output_scope'],
+                             bev_prescale=getattr(head, 'prescale_factor', 1.0),
+                             bev_seg_kernel=getattr(head, 'seg_conv_kernel', 1), device=x0.device)
         ver = sum(p._version for p in head.parameters())
-        eng = self._get_engine((b, c, h, w, str(x0.device), self.timesteps, self.randsteps, ver), factory)
+        # everything of the head that shapes the engine: its identity, grid transform (scopes, prescale) and conv_seg kernel
+        gt = head.grid_transform
+        hkey = (id(head), repr(gt['input_scope']), repr(gt['output_scope']), getattr(head, 'prescale_factor', 1.0),
+                getattr(head, 'seg_conv_kernel', 1))
+        eng = self._get_engine((b, c, h, w, str(x0.device), self.timesteps, self.randsteps, ver) + hkey, factory)
         return eng.sample(x0.contiguous().float(), noise.contiguous().float())

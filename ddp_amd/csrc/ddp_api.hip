@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <initializer_list>
 
 #include "ddp_internal.h"
@@ -124,9 +125,22 @@ struct Layout {
   unsigned short* bins_wsplit = nullptr;                // bf16x3: split planes of bins_wpack
   unsigned char* bins_stream = nullptr;                 // bf16x3: the 72 stage images of the implicit 3x3 GEMM
   float *bins_in = nullptr, *bins_logits = nullptr;     // fp32 engine: zero-bordered grid of the layer output; logits (see carve)
+  // bev head variants (ABI 7).  seg3: conv_seg is 3x3 - it shares the bins_* buffers of the binned depth head (the same implicit
+  // GEMM / nine shifted GEMMs, on the head grid).  prescale: the grid transform resamples the map prescaled to (hp, wp), which is
+  // materialised in `pre` (R maps, row-major) by k_bev_prescale
+  bool seg3 = false, prescale = false;
+  int hp = 0, wp = 0;
+  float pre_rscale = 1.f;
+  float* pre = nullptr;
   size_t const_bytes;   // region A (model constants): a prefix of the workspace that does not depend on the geometry
   size_t total;
 };
+
+// floor(in * p) as F.interpolate computes its output size (double arithmetic on the given scale factor).  p is the FLOAT field: a
+// caller whose factor is a double that float cannot hold (0.9: floor(10 * 0.9f) = 8, floor(10 * 0.9) = 9) must hand over a float
+// that gives the sizes of its double (include/ddp_mi355x.h; ddp_amd.engine.check_bev_head does)
+inline bool bev_prescaled(const ddp_cfg* c) { return c->bev_prescale != 0.f && c->bev_prescale != 1.f; }
+inline double bev_prescaled_len(const ddp_cfg* c, int in_len) { return std::floor(double(in_len) * double(c->bev_prescale)); }
 
 int validate(const ddp_cfg* c) {
   if (!c) {
@@ -198,6 +212,31 @@ int validate(const ddp_cfg* c) {
     set_error("DDP_FLAG_DEPTH_* configure the depth head only (task %d)", c->task);
     return DDP_E_BADCFG;
   }
+  if ((c->bev_prescale != 0.f || c->bev_seg_kernel != 0) && c->task != DDP_TASK_BEV) {
+    set_error("bev_prescale / bev_seg_kernel configure the bev head only (task %d)", c->task);
+    return DDP_E_BADCFG;
+  }
+  if (c->bev_seg_kernel != 0 && c->bev_seg_kernel != 1 && c->bev_seg_kernel != 3) {
+    set_error("bev_seg_kernel %d: conv_seg is 1x1 (0 / 1) or 3x3 (3)", c->bev_seg_kernel);
+    return DDP_E_BADCFG;
+  }
+  if (!(c->bev_prescale >= 0.f) || !std::isfinite(c->bev_prescale)) {
+    set_error("bev_prescale %g must be a positive factor (0 / 1: none)", double(c->bev_prescale));
+    return DDP_E_BADCFG;
+  }
+  if (bev_prescaled(c)) {
+    const double hp = bev_prescaled_len(c, c->h), wp = bev_prescaled_len(c, c->w);
+    if (hp < 1.0 || wp < 1.0) {
+      set_error("bev_prescale %g: prescaled map %.0f x %.0f is empty", double(c->bev_prescale), hp, wp);
+      return DDP_E_BADCFG;
+    }
+    if (hp * wp > double(DDP_BEV_MAX_PRESCALE_AREA) * c->h * c->w ||
+        double(c->batch) * c->randsteps * hp * wp > double(DDP_MAX_CALL_TOKENS)) {
+      set_error("bev_prescale %g: prescaled map %.0f x %.0f exceeds %d x the map (or the per-call limit of 1.5e9 / 1024 prescaled tokens)",
+                double(c->bev_prescale), hp, wp, DDP_BEV_MAX_PRESCALE_AREA);
+      return DDP_E_BADCFG;
+    }
+  }
   if (c->gemm_mode != DDP_GEMM_F32_MFMA && c->gemm_mode != DDP_GEMM_BF16X3) {
     set_error("unknown gemm_mode %d", c->gemm_mode);
     return DDP_E_BADCFG;
@@ -247,9 +286,12 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   o->wm = cv.take(size_t(256) * o->Cm);
   o->wtap = cv.take(size_t(9) * 256);
   o->nbins = c->task == DDP_TASK_DEPTH ? c->depth_n_bins : 0;
+  o->seg3 = c->task == DDP_TASK_BEV && c->bev_seg_kernel == 3;
+  o->prescale = c->task == DDP_TASK_BEV && bev_prescaled(c);
+  const bool conv3 = o->nbins || o->seg3;     // a 3x3 head convolution to more than one channel
   o->bins_tab = o->nbins ? cv.take(DDP_MAX_DEPTH_BINS) : nullptr;
-  o->bins_bias = o->nbins ? cv.take(256) : nullptr;
-  o->bins_wpack = o->nbins ? cv.take(size_t(256) * 2304) : nullptr;
+  o->bins_bias = conv3 ? cv.take(256) : nullptr;
+  o->bins_wpack = conv3 ? cv.take(size_t(256) * 2304) : nullptr;
   for (int l = 0; l < DDP_MAX_LAYERS; ++l) {
     const bool on = l < o->L;
     o->wcat[l] = on ? cv.take(96 * 256) : nullptr;
@@ -290,15 +332,16 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->tail4_bias = cv.take(segp ? size_t(b3_layer_bias_floats()) : 0);
     o->head7_stream = (segp && o->Cx == 256) ? reinterpret_cast<unsigned char*>(cv.take(size_t(8 + 8 + 11) * 48 * 1024 / sizeof(float))) : nullptr;
     // last layer + tail (k_layer MODE 6 / 8 / 9): seg 72 + 2 * chunks + 11 images, bev (<= 32 classes) and depth (9 taps) 72 + 2
-    const bool lt = o->L >= 1 && (segp ? b3_layer_tail_supported(o->Kc) : o->Kc <= 32);
+    // (not for the 3x3 conv_seg of the bev head: its last layer is a plain layer, no tail stream is built or read)
+    const bool lt = o->L >= 1 && (segp ? b3_layer_tail_supported(o->Kc) : o->Kc <= 32) && !o->seg3;
     o->lt_stream = lt ? reinterpret_cast<unsigned char*>(cv.take(size_t(segp ? 72 + 8 + 11 : 72 + 2) * 48 * 1024 / sizeof(float))) : nullptr;
     o->lt_bias = lt ? cv.take(size_t(b3_layer_bias_floats())) : nullptr;
     const bool bev_tab = c->task == DDP_TASK_BEV && o->Kc <= 8;
     o->tlut = cv.take(segp ? size_t(o->Kc + 1) * 256 : bev_tab ? (size_t(1) << o->Kc) * 256 : 0);
     o->lut64 = bev_tab ? cv.take((size_t(1) << o->Kc) * 256) : nullptr;
     o->wvs = c->task == DDP_TASK_DEPTH ? cv.take(512) : nullptr;
-    o->bins_wsplit = o->nbins ? reinterpret_cast<unsigned short*>(cv.take(size_t(256) * 2304 * 3 / 2)) : nullptr;
-    o->bins_stream = o->nbins ? reinterpret_cast<unsigned char*>(cv.take(size_t(72) * 48 * 1024 / sizeof(float))) : nullptr;
+    o->bins_wsplit = conv3 ? reinterpret_cast<unsigned short*>(cv.take(size_t(256) * 2304 * 3 / 2)) : nullptr;
+    o->bins_stream = conv3 ? reinterpret_cast<unsigned char*>(cv.take(size_t(72) * 48 * 1024 / sizeof(float))) : nullptr;
   }
   o->const_bytes = cv.off * sizeof(float);
   // ---- region B: everything that depends on the geometry (batch, r, map size): positional tables, activations
@@ -331,16 +374,24 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   // binned depth head: bf16x3 - the stream GEMM writes the logits fp32 fragment-major with 256 channels (rows padded to 256);
   // fp32 engine - the layer output on a zero-bordered grid (+ guard rows: the nine taps are row offsets of up to w + 3) and the
   // logits on that grid, rows of bins_ld floats
-  o->bins_ld = (o->nbins + 3) / 4 * 4;
-  o->bins_guard = o->w + 3;
-  if (o->nbins) {
-    const size_t padded = size_t(o->R) * (o->h + 2) * (o->w + 2);
+  // (3x3 conv_seg of the bev head: the same two buffers on the head grid, K_cls channels)
+  o->bins_ld = ((o->seg3 ? o->Kc : o->nbins) + 3) / 4 * 4;
+  o->bins_guard = o->wh + 3;
+  if (conv3) {
+    const size_t padded = size_t(o->R) * (o->hh + 2) * (o->wh + 2);
     if (o->b3) {
       o->bins_logits = cv.take(Mp * 256);
     } else {
       o->bins_in = cv.take((padded + 2 * size_t(o->bins_guard)) * 256);
       o->bins_logits = cv.take(padded * o->bins_ld);
     }
+  }
+  // prescaled map: R row-major maps of (hp, wp) x 256 floats, whole 4-token blocks as k_bev_prescale writes them
+  if (o->prescale) {
+    o->hp = int(bev_prescaled_len(c, c->h));
+    o->wp = int(bev_prescaled_len(c, c->w));
+    o->pre_rscale = float(1.0 / double(c->bev_prescale));
+    o->pre = cv.take((size_t(o->R) * o->hp * o->wp + 3) / 4 * 4 * 256);
   }
   o->x0_trace = reinterpret_cast<unsigned char*>(
       cv.take((c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) && c->task == DDP_TASK_SEG
@@ -383,10 +434,11 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   o->total = cv.off * sizeof(float);
 }
 
-BevGeom bev_geom(const ddp_cfg* c) {
+// `o` given: the geometry of the grid RESAMPLING, whose source is the prescaled map when there is one
+BevGeom bev_geom(const ddp_cfg* c, const Layout* o = nullptr) {
   BevGeom g;
-  g.h = c->h;
-  g.w = c->w;
+  g.h = o && o->prescale ? o->hp : c->h;
+  g.w = o && o->prescale ? o->wp : c->w;
   g.hh = c->head_h;
   g.wh = c->head_w;
   for (int a = 0; a < 2; ++a) {
@@ -510,6 +562,20 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
   DDP_TRY(launch_pack_cols(w->transform_w, o.Cx + o.Cm, o.Cx, 256, o.Cm, o.wm, st));
   if (c->task == DDP_TASK_SEG) DDP_TRY(launch_build_lut(w->embedding, o.lut, o.Kc + 1, c->bit_scale, st));
   if (c->task == DDP_TASK_DEPTH) DDP_TRY(launch_pack_conv3x3(w->head_w, o.wtap, st));
+  if (o.seg3) {
+    // 3x3 conv_seg (K_cls,256,3,3): packed tap-major like the binned conv_depth below, zero rows beyond K_cls, bias zero-padded
+    if (hipMemsetAsync(o.bins_wpack, 0, size_t(256) * 2304 * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(o.bins_bias, 0, 256 * sizeof(float), st) != hipSuccess ||
+        hipMemcpyAsync(o.bins_bias, w->head_b, size_t(o.Kc) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      set_error("bev 3x3 conv_seg: weight copy failed");
+      return DDP_E_LAUNCH;
+    }
+    DDP_TRY(launch_pack_conv3x3_scaled(w->head_w, nullptr, o.bins_wpack, o.Kc, 256, st));
+    if (o.b3) {
+      DDP_TRY(launch_split_weights(o.bins_wpack, 2304, 256, 2304, o.bins_wsplit, st));
+      DDP_TRY(launch_build_stages(o.bins_wsplit, size_t(256) * 2304, 2304, 256, 0, 1, 72, 0, 2, 1, 0, o.bins_stream, st));
+    }
+  }
   if (o.nbins) {
     // binned depth head: conv_depth (n_bins,256,3,3) tap-major, output rows zero-padded to the stream GEMM's 256 columns; bias and
     // bin centres zero-padded likewise
@@ -537,7 +603,7 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
     DDP_TRY(launch_split_weights(o.wx, o.Cx, 256, o.Cx, wr(o.wp_x), st));
     if (c->task != DDP_TASK_DEPTH) DDP_TRY(launch_split_weights(o.wm, 256, 256, 256, wr(o.wp_m), st));
     if (c->task == DDP_TASK_DEPTH) DDP_TRY(launch_split_weights(o.wtap, 256, 9, 256, wr(o.wp_head), st));
-    else DDP_TRY(launch_split_weights(w->head_w, 256, o.Kc, 256, wr(o.wp_head), st));
+    else if (!o.seg3) DDP_TRY(launch_split_weights(w->head_w, 256, o.Kc, 256, wr(o.wp_head), st));
     for (int l = 0; l < o.L; ++l) {
       const ddp_layer_weights& lw = w->layers[l];
       DDP_TRY(launch_split_weights(lw.value_proj_w, 256, 256, 256, wr(o.wp_v[l]), st));
@@ -591,7 +657,7 @@ int prepare_model(const ddp_cfg* c, const ddp_weights* w, const Layout& o, hipSt
         }
       }
     }
-    if (o.lt_stream && c->task != DDP_TASK_SEG) {
+    if (o.lt_stream && c->task != DDP_TASK_SEG && !o.seg3) {
       // last layer + bev / depth tail (k_layer MODE 8 / 9): [layer L-1: 72 stages][the head convolution: 2 tall stages of <= 32 rows]
       // (conv_seg of the bev head; the nine taps of the 3x3 conv_depth as nine output rows).  Bias table: fc1's; tail_bias: conv_seg's
       // (depth: zeros - conv_depth's bias is added once per pixel by k_depth_update).
@@ -640,20 +706,12 @@ int publish_q(const Layout& o, const float* row_major, hipStream_t st) {
   return launch_row_to_blk(row_major, o.q, int(o.M), st);     // the layer kernels (and the fp32 engine) take q as fp32 fragments
 }
 
-// binned depth head (decode_head.py:233-250) on the encoder output: conv_depth to n_bins channels (3x3, padding 1, bias), then
-// k_depth_bins -> the metric prediction `pred` (M).  bf16x3: the implicit 3x3 GEMM of the stream engine (k_layer MODE 5, 72 stages,
-// bias in the epilogue, no activation) on the fp32 fragment-major layer output; fp32 engine: the exact-product GEMM as nine shifted
-// GEMMs over the zero-bordered grid, accumulated in place.
-int depth_bins_head(const ddp_cfg* c, const Layout& o, float* pred, hipStream_t st) {
+// the 3x3 head convolution (padding 1, bias) of the encoder output on the head grid into o.bins_logits -> (layout, ld) as
+// DepthBinsArgs / BevSeg3Args read it.  bf16x3: the implicit 3x3 GEMM of the stream engine (k_layer MODE 5, 72 stages, bias in the
+// epilogue, no activation) on the fp32 fragment-major layer output; fp32 engine: the exact-product GEMM as nine shifted GEMMs over
+// the zero-bordered grid, accumulated in place.
+int conv3x3_head(const Layout& o, int n_out, int* layout, int* ld, hipStream_t st) {
   const int M = int(o.M);
-  DepthBinsArgs a;
-  a.bins = o.bins_tab;
-  a.n_bins = o.nbins;
-  a.norm = c->depth_norm;
-  a.pred = pred;
-  a.R = o.R;
-  a.h = o.h;
-  a.w = o.w;
   if (o.b3) {
     if (!o.fused_layer) {     // the tile-GEMM layers leave their output as SB only
       DDP_TRY(launch_sb_to_row(o.q_sb, o.s, M, 256, st));
@@ -665,29 +723,64 @@ int depth_bins_head(const ddp_cfg* c, const Layout& o, float* pred, hipStream_t 
     pr.stream = o.bins_stream;
     pr.M = M;
     pr.ns = 72;
-    pr.conv_h = o.h;
-    pr.conv_w = o.w;
+    pr.conv_h = o.hh;
+    pr.conv_w = o.wh;
     pr.bias = o.bins_bias;
     prof_begin(TAG_HEAD, st);
     DDP_TRY(launch_b3_sgemm(&pr, 1, 0, 1, st));
     prof_end(TAG_HEAD, st);
-    a.logits = o.bins_logits;
-    a.layout = 0;
-    a.ld = 256;
+    *layout = 0;
+    *ld = 256;
   } else {
-    DDP_TRY(launch_blk_to_pad(o.q, o.bins_in, o.R, o.h, o.w, o.bins_guard, st));
-    const int rows = o.R * (o.h + 2) * (o.w + 2);
+    DDP_TRY(launch_blk_to_pad(o.q, o.bins_in, o.R, o.hh, o.wh, o.bins_guard, st));
+    const int rows = o.R * (o.hh + 2) * (o.wh + 2);
     for (int t = 0; t < 9; ++t) {
-      const int off = (t / 3 - 1) * (o.w + 2) + (t % 3 - 1);
+      const int off = (t / 3 - 1) * (o.wh + 2) + (t % 3 - 1);
       DDP_TRY(launch_linear(o.bins_in + size_t(o.bins_guard + off) * 256, 256, false, o.bins_wpack + t * 256, 2304,
                             t == 0 ? o.bins_bias : nullptr, t == 0 ? nullptr : o.bins_logits, o.bins_ld, 0, 0, o.bins_logits,
-                            o.bins_ld, rows, o.nbins, 256, 0, st));
+                            o.bins_ld, rows, n_out, 256, 0, st));
     }
-    a.logits = o.bins_logits;
-    a.layout = 1;
-    a.ld = o.bins_ld;
+    *layout = 1;
+    *ld = o.bins_ld;
   }
+  return DDP_OK;
+}
+
+// binned depth head (decode_head.py:233-250) on the encoder output: conv_depth to n_bins channels (conv3x3_head), then
+// k_depth_bins -> the metric prediction `pred` (M)
+int depth_bins_head(const ddp_cfg* c, const Layout& o, float* pred, hipStream_t st) {
+  DepthBinsArgs a;
+  a.bins = o.bins_tab;
+  a.n_bins = o.nbins;
+  a.norm = c->depth_norm;
+  a.pred = pred;
+  a.R = o.R;
+  a.h = o.h;
+  a.w = o.w;
+  a.logits = o.bins_logits;
+  DDP_TRY(conv3x3_head(o, o.nbins, &a.layout, &a.ld, st));
   return launch_depth_bins(a, st);
+}
+
+// the 3x3 conv_seg of the bev head on the encoder output (fp32 fragment-major o.q), then k_bev_seg3: the step's probabilities set /
+// accumulated in o.prob; `code` (u chain, K_cls <= 8): the step's x0 code bytes; `logits_out`: rows of 32 for k_bev_update
+int bev_seg3_head(const ddp_cfg* c, const Layout& o, bool first, unsigned char* code, float* logits_out, hipStream_t st) {
+  BevSeg3Args a{};
+  a.logits = o.bins_logits;
+  DDP_TRY(conv3x3_head(o, o.Kc, &a.layout, &a.ld, st));
+  a.num_classes = o.Kc;
+  a.prob = o.prob;
+  a.first = first;
+  a.code = code;
+  a.logits_out = logits_out;
+  a.threshold = c->threshold;
+  a.R = o.R;
+  a.hh = o.hh;
+  a.wh = o.wh;
+  prof_begin(TAG_HEAD, st);          // (the route's witness: a second TAG_HEAD record per step behind the convolution's)
+  const int rc = launch_bev_seg3(a, st);
+  prof_end(TAG_HEAD, st);
+  return rc;
 }
 
 // eps of the regression head's depth_pred: the HEAD's depth range (decode_head.py:258-266; 0 / 0 = the depther's)
@@ -920,6 +1013,10 @@ struct Plan {
   // the DDIM update through the 2^K-row table T = LUT64 . W_m^T - per step: u update, q = rx + resample(u), layer 0's projections;
   // no GEMM at the map size after u_0
   bool bev_chain = false;
+  // bev with the 3x3 conv_seg (cfg->bev_seg_kernel == 3): nine taps x K_cls columns do not fit the two tall stages of the MODE 8 tail, so
+  // the last layer runs as a plain layer and conv_seg follows as the implicit 3x3 GEMM (the fp32 engine: nine shifted GEMMs) +
+  // k_bev_seg3.  With bev_chain the u chain is kept around it (k_bev_seg3 writes the codes); otherwise k_bev_seg3 feeds k_bev_update
+  bool bev_seg3 = false;
 };
 
 Plan plan_of(const ddp_cfg* c, const Layout& o) {
@@ -933,7 +1030,9 @@ Plan plan_of(const ddp_cfg* c, const Layout& o) {
   p.lt_fused = p.u_chain && lt;
   p.depth_lt = c->task == DDP_TASK_DEPTH && lt && !o.nbins;
   p.depth_chain = p.depth_lt && o.rvpad && o.L >= 2;
-  p.bev_chain = c->task == DDP_TASK_BEV && lt && o.lut64;
+  // (the 1x1 head needs the last layer + tail stream; the 3x3 head keeps the chain around a plain last layer and has none)
+  p.bev_chain = c->task == DDP_TASK_BEV && o.lut64 && (o.seg3 ? o.fused_pro && !(c->flags & DDP_FLAG_UNFUSED_TAIL) : lt);
+  p.bev_seg3 = o.seg3;
   return p;
 }
 
@@ -1135,10 +1234,23 @@ int sample_depth(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, 
 int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, const Plan& p, const Layout& o, const float* d_noise,
                float* d_out, hipStream_t st) {
   const int M0 = int(o.M0);
-  const BevGeom geom = bev_geom(c);
+  // geom: the map (h, w) and the head grid - the x0 feedback; rs: the grid resampling, whose source is the prescaled map when
+  // cfg->bev_prescale is set.  The prescale is linear, so the u chain survives: resample(prescale(W_x x + b + u)) = rx' +
+  // resample(prescale(u)), with u kept at the map size (the nearest-resize of the thresholded maps goes to (h, w))
+  const BevGeom geom = bev_geom(c), rs = bev_geom(c, &o);
+  const BevPrescale ps{o.h, o.w, o.hp, o.wp, o.pre_rscale};
+  // the source of the grid resampling for a row-major map `src` of `maps` maps
+  auto prescaled = [&](const float* src, int maps, const float** out) {
+    *out = src;
+    if (!o.prescale) return int(DDP_OK);
+    *out = o.pre;
+    return launch_bev_prescale(src, o.pre, maps, ps, st);
+  };
+  const float* rsrc = nullptr;
   unsigned char* code = reinterpret_cast<unsigned char*>(o.logits);            // (M) the step's x0 code per head-grid token
   if (p.bev_chain) {
-    DDP_TRY(launch_bev_resample(o.xproj, o.s, o.B, geom, st));                  // rx = resample(W_x x + b), B maps
+    DDP_TRY(prescaled(o.xproj, o.B, &rsrc));
+    DDP_TRY(launch_bev_resample(rsrc, o.s, o.B, rs, st));                       // rx = resample(W_x x + b), B maps
     DDP_TRY(launch_nchw_to_sb(d_noise, o.in_sb, o.R, 256, o.N, st));
     DDP_TRY(launch_b3_linear(o.in_sb, o.wp_m, nullptr, nullptr, 0, 0, 0, o.feat0, 256, M0, 256, 256, st, TAG_FEAT));   // u_0 = W_m . noise
   } else {
@@ -1164,7 +1276,8 @@ int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
         const float ua = pp.sigma_next / (pp.sigma > 1e-8f ? pp.sigma : 1e-8f);
         DDP_TRY(launch_bev_u_update(o.feat0, code, o.tlut, o.R, geom, ua, pp.alpha_next - pp.alpha * ua, st));
       }
-      DDP_TRY(launch_bev_q(o.feat0, o.s, o.q, o.R, o.r, geom, st));
+      DDP_TRY(prescaled(o.feat0, o.R, &rsrc));
+      DDP_TRY(launch_bev_q(rsrc, o.s, o.q, o.R, o.r, rs, st));
     } else {
       // feat = transform(cat[x, mask_t]) on the map, then the grid transform to the head grid
       if (o.b3) {
@@ -1173,11 +1286,22 @@ int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
       } else {
         DDP_TRY(launch_linear(o.mask, 256, false, o.wm, 256, nullptr, o.xproj, 256, o.r * o.N, o.N, o.feat0, 256, M0, 256, 256, 0, st));
       }
-      DDP_TRY(launch_bev_resample(o.feat0, o.s, o.R, geom, st));
+      DDP_TRY(prescaled(o.feat0, o.R, &rsrc));
+      DDP_TRY(launch_bev_resample(rsrc, o.s, o.R, rs, st));
       DDP_TRY(publish_q(o, o.s, st));
     }
     tl.prob_mode = s == 0 ? 1 : 2;
-    DDP_TRY(encoder_forward(w, o, aff, st, /*l0_projected=*/false, /*sb_out=*/!p.bev_chain, p.bev_chain ? &tl : nullptr));
+    // (the 3x3 conv_seg reads the fp32 layer output of a plain last layer)
+    DDP_TRY(encoder_forward(w, o, aff, st, /*l0_projected=*/false, /*sb_out=*/!p.bev_chain && !p.bev_seg3,
+                            p.bev_chain && !p.bev_seg3 ? &tl : nullptr));
+    if (p.bev_seg3) {
+      DDP_TRY(bev_seg3_head(c, o, s == 0, p.bev_chain ? code : nullptr, p.bev_chain ? nullptr : o.logits, st));
+      if (p.bev_chain) continue;
+      BevUpdateArgs ua = bev_update_args(c, w, o, o.mask, s == 0, sp);
+      ua.prob = nullptr;             // (k_bev_seg3 accumulated the probabilities)
+      DDP_TRY(launch_bev_update(ua, st));
+      continue;
+    }
     if (p.bev_chain) continue;     // (the next step's head updates u from the codes the tail wrote)
     DDP_TRY(head_gemm(c, w, o, st));
     DDP_TRY(launch_bev_update(bev_update_args(c, w, o, o.mask, s == 0, sp), st));
@@ -1381,7 +1505,12 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
   DDP_TRY(fold_affine_dev(weights, o.L, 1, film, o.aff, st));
   if (cfg->task == DDP_TASK_BEV) {
     DDP_TRY(launch_nchw_to_tok(d_feat, o.feat0, o.R, 256, o.N, st));
-    DDP_TRY(launch_bev_resample(o.feat0, o.s, o.R, bev_geom(cfg), st));
+    const float* rsrc = o.feat0;
+    if (o.prescale) {
+      DDP_TRY(launch_bev_prescale(o.feat0, o.pre, o.R, BevPrescale{o.h, o.w, o.hp, o.wp, o.pre_rscale}, st));
+      rsrc = o.pre;
+    }
+    DDP_TRY(launch_bev_resample(rsrc, o.s, o.R, bev_geom(cfg, &o), st));
   } else {
     DDP_TRY(launch_nchw_to_tok(d_feat, o.s, o.R, 256, o.N, st));      // row-major staging in `s`
   }
@@ -1389,6 +1518,10 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
   DDP_TRY(encoder_forward(weights, o, o.aff, st));
   // outputs (R,K,h,w) or, for depth, (R,1,h,w) == (R*N)
   if (cfg->task == DDP_TASK_DEPTH && o.nbins) return depth_bins_head(cfg, o, d_out, st);
+  if (o.seg3) {
+    DDP_TRY(bev_seg3_head(cfg, o, true, nullptr, nullptr, st));
+    return launch_finalize_nchw(o.prob, 32, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st);
+  }
   DDP_TRY(head_gemm(cfg, weights, o, st));
   if (cfg->task == DDP_TASK_SEG) return launch_finalize_nchw(o.logits, o.ldl, d_out, o.R, 1, o.Nh, o.Kc, 1.0f, st);
   if (cfg->task == DDP_TASK_DEPTH) return launch_depth_update(depth_update_args(cfg, weights, o, o.logits, nullptr, d_out, ddp_step{}), st);

@@ -378,6 +378,26 @@ struct BevUpdateArgs {
   ddp_step st;
 };
 int launch_bev_update(const BevUpdateArgs& a, hipStream_t st);
+// grid_transform.prescale_factor: bilinear F.interpolate(scale_factor = p, align_corners = False) of a row-major (R, h*w, 256) map to
+// (R, hp*wp, 256), hp = floor(h p), wp = floor(w p); rscale = float(1 / p): the source coordinate comes from the given factor
+struct BevPrescale {
+  int h, w, hp, wp;
+  float rscale;
+};
+int launch_bev_prescale(const float* in, float* out, int R, const BevPrescale& ps, hipStream_t st);
+// 3x3 conv_seg: the step's logits -> sigmoid -> probability rows of 32 set / accumulated (+ the x0 code byte, + the logits as rows of 32)
+struct BevSeg3Args {
+  const float* logits;  // layout 0: fp32 fragment-major, 256 channels; 1: rows of ld floats on the zero-bordered grid (R, hh+2, wh+2)
+  int layout, ld;
+  int num_classes;      // <= 32
+  float* prob;          // (R*Nh, 32)
+  int first;            // prob = (first) else +=
+  unsigned char* code;  // optional (K_cls <= 8): bit k = sigmoid_k > threshold
+  float* logits_out;    // optional (R*Nh, 32): the raw logits for k_bev_update
+  float threshold;
+  int R, hh, wh;
+};
+int launch_bev_seg3(const BevSeg3Args& a, hipStream_t st);
 // the bev sampler's u chain (ddp_kernels.hip: k_bev_q): q (fragment-major, R maps of hh x wh) = rx[map / r] + resample(u[map]);
 // the 2^K x0 vectors of a pixel; u <- ua u + uc T[code at the pixel's nearest head-grid source]
 int launch_bev_q(const float* u, const float* rx, float* q_blk, int R, int r, const BevGeom& g, hipStream_t st);

@@ -2191,6 +2191,82 @@ __global__ void __launch_bounds__(256) k_bev_update(BevUpdateArgs a, int nbA) {
   *reinterpret_cast<f32x4*>(mp) = mn;
 }
 
+// grid_transform.prescale_factor (heads/segm/deformable_head_with_time.py:70-77): F.interpolate(scale_factor = p, mode = 'bilinear',
+// align_corners = False) of a row-major map (R, h*w, 256) -> (R, hp*wp, 256) in front of the grid resampling.  PyTorch's index arithmetic
+// (UpSample.h, area_pixel_compute_source_index with the GIVEN scale factor): src = (dst + 0.5) / p - 0.5, clamped at 0; the upper
+// neighbour clamped at in - 1; weights (1 - l, l).  Every index is inside the map, so nothing is selected to zero: four unconditional
+// 1-KiB row loads per wave, one coalesced 1-KiB store.  Byte-streaming: reads the map once (through L2), writes p^2 maps.
+__device__ __forceinline__ void bev_prescale_index(int dst, int in_len, float rscale, int& i0, int& i1, float& l1) {
+  const float src = fmaxf(rscale * (float(dst) + 0.5f) - 0.5f, 0.f);
+  i0 = min(int(src), in_len - 1);
+  i1 = min(i0 + 1, in_len - 1);
+  l1 = src - float(i0);
+}
+__global__ void __launch_bounds__(256) k_bev_prescale(const float* __restrict__ in, float* __restrict__ out, int R, BevPrescale ps) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int Np = ps.hp * ps.wp;
+  if (m >= R * Np) return;
+  const int img = m / Np, n = m - img * Np;
+  const int oi = n / ps.wp, oj = n - oi * ps.wp;
+  int y0, y1, x0, x1;
+  float ly, lx;
+  bev_prescale_index(oi, ps.h, ps.rscale, y0, y1, ly);
+  bev_prescale_index(oj, ps.w, ps.rscale, x0, x1, lx);
+  const float* base = in + size_t(img) * ps.h * ps.w * 256 + lane * 4;
+  const f32x4 v00 = *reinterpret_cast<const f32x4*>(base + size_t(y0 * ps.w + x0) * 256);
+  const f32x4 v01 = *reinterpret_cast<const f32x4*>(base + size_t(y0 * ps.w + x1) * 256);
+  const f32x4 v10 = *reinterpret_cast<const f32x4*>(base + size_t(y1 * ps.w + x0) * 256);
+  const f32x4 v11 = *reinterpret_cast<const f32x4*>(base + size_t(y1 * ps.w + x1) * 256);
+  const f32x4 acc = (v00 * (1.f - lx) + v01 * lx) * (1.f - ly) + (v10 * (1.f - lx) + v11 * lx) * ly;
+  *reinterpret_cast<f32x4*>(out + size_t(m) * 256 + lane * 4) = acc;
+}
+
+// The 3x3 conv_seg's logits of a step (heads/segm/deformable_head_with_time.py:136-139,235): the analogue of k_depth_bins.  One thread per
+// head-grid token streams the token's K_cls <= 32 logits (16 B per load, all of them in flight: clamped quad indices, columns >= K_cls
+// dropped afterwards), applies torch.sigmoid, sets (first) or accumulates the token's probability row of 32, and leaves what the step's x0
+// needs: the code byte (bit k = sigmoid_k > threshold, K_cls <= 8: the u chain) or the logits as rows of 32 for k_bev_update.
+// layout 0: fp32 fragment-major with 256 channels (the stream GEMM's output); 1: rows of `ld` floats on the zero-bordered grid.
+__global__ void __launch_bounds__(256) k_bev_seg3(BevSeg3Args a) {
+  const int Nh = a.hh * a.wh;
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= a.R * Nh) return;
+  const float* p;
+  if (a.layout == 0) {
+    p = a.logits + size_t(m >> 5) * 8192 + (m & 31) * 4;
+  } else {
+    const int img = m / Nh, n = m - img * Nh;
+    const int i = n / a.wh, j = n - i * a.wh;
+    p = a.logits + (size_t(img) * (a.hh + 2) * (a.wh + 2) + size_t(i + 1) * (a.wh + 2) + (j + 1)) * a.ld;
+  }
+  const int K = a.num_classes, nq = (K + 3) >> 2;
+  f32x4 v[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int q = u < nq ? u : nq - 1;
+    const size_t off = a.layout == 0 ? size_t((q >> 1) & 3) * 256 + (q & 1) * 128 : size_t(q) * 4;
+    v[u] = *reinterpret_cast<const f32x4*>(p + off);
+  }
+  float* pr = a.prob + size_t(m) * 32;
+  float* lo = a.logits_out ? a.logits_out + size_t(m) * 32 : nullptr;
+  unsigned code = 0;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    if (u >= nq) break;
+    f32x4 s;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool on = 4 * u + e < K;
+      s[e] = on ? sigmoidf_(v[u][e]) : 0.f;
+      if (u < 2 && on && s[e] > a.threshold) code |= 1u << ((4 * u + e) & 7);
+    }
+    if (!a.first) s += *reinterpret_cast<const f32x4*>(pr + 4 * u);
+    *reinterpret_cast<f32x4*>(pr + 4 * u) = s;
+    if (lo) *reinterpret_cast<f32x4*>(lo + 4 * u) = v[u];
+  }
+  if (a.code) a.code[m] = (unsigned char)code;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -2536,8 +2612,21 @@ int launch_bev_u_update(float* u, const unsigned char* code, const float* tlut, 
   hipLaunchKernelGGL(k_bev_u_update, dim3(cdiv(long(R) * g.h * g.w, 4)), dim3(256), 0, st, u, code, tlut, R, g, ua, uc);
   return check_launch("k_bev_u_update");
 }
+int launch_bev_prescale(const float* in, float* out, int R, const BevPrescale& ps, hipStream_t st) {
+  hipLaunchKernelGGL(k_bev_prescale, dim3(cdiv(long(R) * ps.hp * ps.wp, 4)), dim3(256), 0, st, in, out, R, ps);
+  return check_launch("k_bev_prescale");
+}
+int launch_bev_seg3(const BevSeg3Args& a, hipStream_t st) {
+  if (a.num_classes < 1 || a.num_classes > 32 || (a.code && a.num_classes > 8)) {
+    set_error("bev_seg3: %d classes (1..32; the code byte holds 8)", a.num_classes);
+    return DDP_E_BADCFG;
+  }
+  hipLaunchKernelGGL(k_bev_seg3, dim3(cdiv(long(a.R) * a.hh * a.wh, 256)), dim3(256), 0, st, a);
+  return check_launch("k_bev_seg3");
+}
 int launch_bev_update(const BevUpdateArgs& a, hipStream_t st) {
-  const int nbA = cdiv(long(a.R) * a.g.hh * a.g.wh * a.num_classes, 256);
+  // prob == nullptr: k_bev_seg3 already accumulated the step's probabilities (3x3 conv_seg) - the DDIM update alone
+  const int nbA = a.prob ? cdiv(long(a.R) * a.g.hh * a.g.wh * a.num_classes, 256) : 0;
   const int nbB = cdiv(long(a.R) * a.g.h * a.g.w, 4);
   hipLaunchKernelGGL(k_bev_update, dim3(nbA + nbB), dim3(256), 0, st, a, nbA);
   return check_launch("k_bev_update");

@@ -34,6 +34,30 @@ _LAYER_KEYS = {
 }
 
 
+def check_bev_head(prescale, seg_kernel, h, w):
+    """(bev_prescale, bev_seg_kernel) of ``ddp_cfg`` from the head's grid_transform['prescale_factor'] and seg_conv_kernel.
+    The reference builds a 3x3 conv_seg for ANY seg_conv_kernel other than 1 (heads/segm/deformable_head_with_time.py:136-139);
+    here only 1 and 3 are accepted.
+    The ABI field is a FLOAT and the library sizes the prescaled map as floor(h * double(float p)); F.interpolate uses the Python
+    double.  For a factor float cannot hold (0.9 on a 10-wide map: 8 against 9) the returned value is the float next to
+    float32(p) that gives the double's sizes on both axes; if neither neighbour does, the factor is refused."""
+    import math
+    import numpy as np
+    if seg_kernel not in (1, 3):
+        raise ValueError(f'seg_conv_kernel must be 1 or 3, got {seg_kernel!r}')
+    p = float(prescale)
+    if not (p > 0 and math.isfinite(p)):
+        raise ValueError(f'prescale_factor must be a positive float, got {prescale!r}')
+    want = (math.floor(h * p), math.floor(w * p))
+    if min(want) < 1:
+        raise ValueError(f'prescale_factor {p}: the prescaled {h} x {w} map is empty')
+    p32 = np.float32(p)
+    for cand in (p32, np.nextafter(p32, np.float32(np.inf)), np.nextafter(p32, np.float32(0))):
+        if (math.floor(h * float(cand)), math.floor(w * float(cand))) == want:
+            return float(cand), int(seg_kernel)
+    raise ValueError(f'prescale_factor {p}: no float32 next to it gives the {want[0]} x {want[1]} prescaled map of the reference')
+
+
 def hot_path_keys(task, num_layers, head_prefix='decode_head.'):
     """(struct field, state_dict key) pairs of the hot path (SURVEY.md §8b checkpoint layout)."""
     conv = 'down.conv' if task == 'depth' else 'transform.conv'
@@ -76,7 +100,7 @@ class PackedWeights:
         for l, lk in enumerate(layers):
             for f, k in lk:
                 entries.append((l, f, k))
-        offs, total = {}, 0
+        offs, total, numel = {}, 0, {}
         for l, f, k in entries:
             if k not in state_dict:
                 if f in ('time_w', 'time_b'):     # layer built without use_time_mlp
@@ -84,12 +108,14 @@ class PackedWeights:
                 raise KeyError(f'hot-path parameter {k!r} missing from state_dict')
             n = state_dict[k].numel()
             offs[(l, f)] = (total, k)
+            numel[(l, f)] = n
             total += (n + 63) // 64 * 64
         flat = torch.zeros(total, dtype=torch.float32, device=device)
         for (l, f), (o, k) in offs.items():
             flat[o:o + state_dict[k].numel()].copy_(state_dict[k].detach().reshape(-1))
         self.flat = flat
         self.offsets = offs
+        self.numel = numel
         self.task = task
         self.num_layers = num_layers
         self.n_bins = state_dict['<depth_bins>'].numel() if depth_bins is not None else 0
@@ -119,11 +145,14 @@ class DDPEngine:
                  head_hw=None, bev_input_scope=None, bev_output_scope=None, device=None, head_prefix='decode_head.',
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
-                 depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None):
+                 depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
+                 bev_prescale=1.0, bev_seg_kernel=1):
         """depth: ``min_depth`` / ``max_depth`` are the depther's range (x0 normalisation); ``head_min_depth`` / ``head_max_depth``
         the decode head's (eps of the regression head; default: the depther's).  ``depth_bins`` (n_bins) = the bin centres of a
         binned head (``classify=True``: conv_depth has n_bins outputs, ``depth_norm`` in 'linear' / 'softmax' / 'sigmoid'); with
-        ``weights`` given, the bins are the ones packed there."""
+        ``weights`` given, the bins are the ones packed there.
+        bev: ``bev_prescale`` = grid_transform['prescale_factor'] of the head, ``bev_seg_kernel`` = its seg_conv_kernel (1 or 3; with
+        3 the state dict's conv_seg.weight is (K,256,3,3))."""
         self.lib = _lib.load(lib_path)
         if not torch.cuda.is_available():
             raise _lib.DdpError('no HIP device visible: ddp_amd has no CPU path')
@@ -154,6 +183,15 @@ class DDPEngine:
                 cfg.bev_in_min[a], cfg.bev_in_max[a] = imin, imax
                 cfg.bev_out_first[a], cfg.bev_out_step[a] = omin + ostep / 2, ostep
             cfg.head_h, cfg.head_w = out_sizes
+            # (the defaults stay zeroed fields: an ABI-6 configuration is the same bytes as before)
+            p, k = check_bev_head(bev_prescale, bev_seg_kernel, h, w)
+            cfg.bev_prescale, cfg.bev_seg_kernel = (p if p != 1.0 else 0.0), (k if k != 1 else 0)
+            n_head = self.weights.numel[(None, 'head_w')]      # (a packed 1x1 tensor read as a 3x3 one would be read 9x past its end)
+            if n_head != num_classes * 256 * (9 if cfg.bev_seg_kernel == 3 else 1):
+                raise ValueError(f'conv_seg.weight has {n_head} elements: not a {k}x{k} '
+                                 f'convolution from 256 channels to {num_classes} classes')
+        elif bev_prescale != 1.0 or bev_seg_kernel != 1:
+            raise ValueError('bev_prescale / bev_seg_kernel configure the bev head only')
         else:
             cfg.head_h, cfg.head_w = (h, w) if head_hw is None else head_hw
         self.gemm = gemm if gemm is not None else default_gemm_mode()

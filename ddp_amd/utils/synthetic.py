@@ -100,13 +100,15 @@ def time_mlp_state(gen, sd):
     sd['time_mlp.3.bias'] = _uniform(gen, (TIME_DIM,), 1.0 / math.sqrt(TIME_DIM))
 
 
-def make_state_dict(task='seg', num_classes=150, num_layers=6, feat_channels=256, seed=2, profile='init', n_bins=None):
+def make_state_dict(task='seg', num_classes=150, num_layers=6, feat_channels=256, seed=2, profile='init', n_bins=None,
+                    seg_conv_kernel=1):
     """Hot-path ``state_dict`` (CPU fp32) for ``task`` in {'seg', 'depth', 'bev'}.
 
     seg  : segmentation/mmseg/models/segmentors/ddp.py:78,92-112 + decode head
     depth: depth/depth/models/depther/ddp.py:70-91 (``down`` conv over 256+1 channels, 3x3 ``conv_depth``)
     bev  : bev/mmdet3d/models/fusion_models/ddp.py:91,104-114 (``transform`` over 256+feat_channels,
-           embedding (7,256)); head keys are given the ``decode_head.`` prefix here as well.
+           embedding (7,256)); head keys are given the ``decode_head.`` prefix here as well.  ``seg_conv_kernel=3``: the 3x3
+           conv_seg of heads/segm/deformable_head_with_time.py:136-139, weight (K,256,3,3) (the default draws today's tensors).
     """
     gen = torch.Generator(device='cpu')
     gen.manual_seed(int(seed))
@@ -133,7 +135,10 @@ def make_state_dict(task='seg', num_classes=150, num_layers=6, feat_channels=256
         sd['decode_head.conv_depth.weight'] = _xavier(gen, 1, EMBED, 3, 3) * 4.0
         sd['decode_head.conv_depth.bias'] = _normal(gen, (1,), mean=2.0, std=0.1)
     else:
-        sd['decode_head.conv_seg.weight'] = _xavier(gen, num_classes, EMBED, 1, 1) * PROFILES[profile]['seg_gain']
+        if seg_conv_kernel not in (1, 3) or (seg_conv_kernel == 3 and task != 'bev'):
+            raise ValueError('seg_conv_kernel: 1, or 3 for the bev head')
+        k = seg_conv_kernel
+        sd['decode_head.conv_seg.weight'] = _xavier(gen, num_classes, EMBED, k, k) * PROFILES[profile]['seg_gain']
         sd['decode_head.conv_seg.bias'] = _normal(gen, (num_classes,), std=0.02)
     return sd
 

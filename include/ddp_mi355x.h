@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define DDP_ABI_VERSION 6
+#define DDP_ABI_VERSION 7
 #define DDP_MAX_LAYERS 12
 #define DDP_MAX_STEPS 64
 #define DDP_EMBED 256
@@ -63,6 +63,12 @@ enum { DDP_GEMM_F32_MFMA = 0, DDP_GEMM_BF16X3 = 1 };
  * pixel become the weights of the bin centres.  LINEAR: relu(l) + 0.1, / sum;  SOFTMAX: softmax;  SIGMOID: sigmoid(l), / sum. */
 enum { DDP_DEPTH_NORM_LINEAR = 0, DDP_DEPTH_NORM_SOFTMAX = 1, DDP_DEPTH_NORM_SIGMOID = 2 };
 #define DDP_MAX_DEPTH_BINS 256
+/* bev grid_transform.prescale_factor: the prescaled map (floor(h p), floor(w p)) gets a workspace buffer of its own (B r maps of 256
+ * channels).  Two bounds, both checked by validate(): the library carves it up to DDP_BEV_MAX_PRESCALE_AREA times the pixels of the
+ * map itself (p <= 4 on both axes), and - like the head grid - up to DDP_MAX_CALL_TOKENS prescaled tokens per call
+ * (batch * randsteps * floor(h p) * floor(w p)), which keeps 32-bit row counters and row * 1024 offsets safe */
+#define DDP_BEV_MAX_PRESCALE_AREA 16
+#define DDP_MAX_CALL_TOKENS 1464843 /* 1.5e9 / 1024 */
 /* ddp_cfg.flags (diagnostics, bf16x3 engine): run the decoder layer / the head of a step as the separate tile GEMMs they
  * were fused from (identical arithmetic per contraction; used by same-box A/B runs and by the parity tests that keep
  * the unfused kernels covered).  UNFUSED_LAYER implies the unfused step head and seg tail as well.
@@ -89,7 +95,8 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                      head (k_layer MODE 3), the 9-tap head GEMM on the SB layer output and k_depth_update per step instead
                                      of k_depth_head + k_layer MODE 10 / MODE 9.  bev: the concat-conv GEMM, grid resampling, head GEMM and
                                      k_bev_update on the 256-channel map per step instead of the u chain (k_bev_u_update, k_bev_q, k_layer
-                                     MODE 8).  depth / bev: the same operators regrouped - results agree to rounding, not bit for bit */ };
+                                     MODE 8).  depth / bev: the same operators regrouped - results agree to rounding, not bit for bit.
+                                     bev with the 3x3 conv_seg: the same launches with the 3x3 head (+ k_bev_seg3) in place of the head GEMM */ };
 
 /* Problem description.  Mirrors the constructor kwargs of the reference `DDP` classes
  * (segmentors/ddp.py:57-67; depther/ddp.py:42-54; fusion_models/ddp.py:67-80). */
@@ -121,6 +128,21 @@ typedef struct ddp_cfg {
   int32_t depth_norm;         /* DDP_DEPTH_NORM_* (binned head) */
   float head_min_depth, head_max_depth; /* the decode head's depth range: eps of the regression head (decode_head.py:258-266).
                                            0 / 0: the same as min_depth / max_depth, which keep normalising x0 (depther/ddp.py:240) */
+  /* ---- ABI 7 (bev only; a zeroed field keeps the behaviour of ABI 6) ---- */
+  float bev_prescale;         /* grid_transform.prescale_factor (heads/segm/deformable_head_with_time.py:70-77): 0 or 1 = none; else a
+                                 bilinear F.interpolate(scale_factor = p, align_corners = False) of the feature map to (floor(h p),
+                                 floor(w p)) runs in front of the grid resampling, whose normalisation then uses the prescaled size.
+                                 Both prescaled sides must be >= 1, their product <= DDP_BEV_MAX_PRESCALE_AREA * h * w and
+                                 batch * randsteps * product <= DDP_MAX_CALL_TOKENS.  THE FIELD IS A FLOAT and the library computes
+                                 the sizes as floor(h * (double)bev_prescale): for a factor float cannot hold exactly the rounded
+                                 value can give one row / column fewer than PyTorch's floor(h * p) of the Python double (0.9 on a
+                                 10-wide map: 8 against 9).  The caller must pass a float whose sizes equal those of its double -
+                                 the neighbouring float above does where rounding went below - or refuse the factor
+                                 (ddp_amd.engine.check_bev_head does both).  The source coordinates use 1 / p of the value passed:
+                                 a relative difference of <= 2^-23 from PyTorch's */
+  int32_t bev_seg_kernel;     /* seg_conv_kernel (:136-139): 0 or 1 = the 1x1 conv_seg; 3 = Conv2d(256, K_cls, 3, padding = 1) with
+                                 ddp_weights.head_w (K_cls,256,3,3).  Other values are refused (the reference builds a 3x3 for ANY
+                                 value other than 1) */
 } ddp_cfg;
 
 typedef struct ddp_layer_weights {            /* decode_head.encoder.layers.<l>.* */
@@ -140,8 +162,8 @@ typedef struct ddp_weights {
   const float *time1_w, *time1_b;         /* (1024,17),(1024) time_mlp.1 */
   const float *time3_w, *time3_b;         /* (1024,1024),(1024) time_mlp.3 */
   const float *embedding;                 /* (K_cls+1,256) embedding_table.weight; NULL for depth */
-  const float *head_w, *head_b;           /* seg/bev conv_seg (K_cls,256),(K_cls); depth conv_depth (1,256,3,3),(1), binned depth
-                                             (n_bins,256,3,3),(n_bins) */
+  const float *head_w, *head_b;           /* seg/bev conv_seg (K_cls,256),(K_cls); bev with bev_seg_kernel = 3: (K_cls,256,3,3),(K_cls);
+                                             depth conv_depth (1,256,3,3),(1), binned depth (n_bins,256,3,3),(n_bins) */
   ddp_layer_weights layers[DDP_MAX_LAYERS];
   const float* depth_bins;                /* (n_bins) bin centres of the binned depth head (the caller evaluates the reference's
                                              torch.linspace / torch.logspace); NULL otherwise */
@@ -214,7 +236,8 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
 
 /* DeformableHeadWithTime.forward: feat (R,256,hh,wh) NCHW + time embedding (1024) -> head output
  * seg: logits (R,K_cls,hh,wh); depth: metric depth (R,1,hh,wh); bev: sigmoid maps.  Uses step slot 0
- * of the workspace constants for FiLM, recomputed from d_temb.  R = batch*randsteps. */
+ * of the workspace constants for FiLM, recomputed from d_temb.  R = batch*randsteps.  bev: cfg->bev_prescale and
+ * cfg->bev_seg_kernel are honoured as in ddp_sample. */
 int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float* d_feat,
                      const float* d_temb, float* d_out, void* d_workspace, void* stream);
 

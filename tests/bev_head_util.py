@@ -1,0 +1,162 @@
+"""Shared by the BEV-head tests: the fixtures of ``tests/golden/bev_head/`` (made by ``golden/gen_golden_bev_head.py``) and a CPU
+restatement of the two head variants they cover - ``grid_transform.prescale_factor`` and the 3x3 ``conv_seg``
+(bev/mmdet3d/models/heads/segm/deformable_head_with_time.py:70-77,136-139; fusion_models/ddp.py:268-301) - composed from
+``oracle.ddp_oracle`` pieces."""
+import glob
+import json
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ddp_amd.utils import synthetic
+from golden_util import fingerprint
+from oracle import ddp_oracle as O
+
+BEV_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'bev_head')
+CLASSES = ['a', 'b', 'c', 'd', 'e', 'f']
+
+
+def encoder_cfg(num_layers):
+    return dict(type='DetrTransformerEncoder', num_layers=num_layers,
+                transformerlayers=dict(type='BaseTransformerLayer', use_time_mlp=True,
+                                       attn_cfgs=dict(type='MultiScaleDeformableAttention', embed_dims=256, num_levels=1,
+                                                      num_heads=8, dropout=0.0),
+                                       ffn_cfgs=dict(type='FFN', embed_dims=256, feedforward_channels=1024, ffn_drop=0.,
+                                                     act_cfg=dict(type='GELU')),
+                                       operation_order=('self_attn', 'norm', 'ffn', 'norm')))
+
+
+POSENC = dict(type='SinePositionalEncoding', num_feats=128, normalize=True, offset=-0.5)
+
+
+def sampler_cases():
+    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(BEV_DIR, '*.npz'))
+                  if os.path.basename(p) != 'head_forward.npz')
+
+
+def all_cases():
+    return sampler_cases() + ['head_forward']
+
+
+def state_dict_of(cfg):
+    sd = synthetic.make_state_dict('bev', cfg.get('num_classes', 6), cfg['num_layers'], cfg.get('feat_channels', 256),
+                                   seed=cfg['seed'] + 100, seg_conv_kernel=cfg.get('seg_conv_kernel', 1))
+    # 'seg_gain': conv_seg scaled so that the logits spread over tens of units - with the seeded initialisation they sit within a
+    # unit of 0, i.e. every probability next to the 0.5 threshold, and no seed keeps all of them 1e-3 away from it
+    sd['decode_head.conv_seg.weight'] = sd['decode_head.conv_seg.weight'] * float(cfg.get('seg_gain', 1.0))
+    return sd
+
+
+def load(name):
+    """-> cfg, state_dict, x (1,Cx,h,w), noise (r,256,h,w) (sampler cases) / feat (R,256,h,w), None (head case), arrays."""
+    z = np.load(os.path.join(BEV_DIR, name + '.npz'))
+    cfg = json.loads(str(z['config']))
+    arrays = {k: torch.from_numpy(z[k]) for k in z.files if k != 'config'}
+    sd = state_dict_of(cfg)
+    assert abs(synthetic.checksum(sd) - float(arrays['weights_fp'])) <= 1e-9 * abs(float(arrays['weights_fp']))
+    if cfg['task'] == 'bev_head_forward':
+        feat, _ = synthetic.make_inputs(cfg['R'], cfg['h'], cfg['w'], 1, 256, 256, seed=cfg['seed'])
+        assert np.allclose(fingerprint(feat), arrays['feat_fp'].numpy(), rtol=1e-12)
+        return cfg, sd, feat, None, arrays
+    x, noise = synthetic.make_inputs(1, cfg['h'], cfg['w'], cfg['randsteps'], cfg['feat_channels'], 256, seed=cfg['seed'])
+    assert np.allclose(fingerprint(x), arrays['x_fp'].numpy(), rtol=1e-12)
+    assert np.allclose(fingerprint(noise), arrays['noise_fp'].numpy(), rtol=1e-12)
+    return cfg, sd, x, noise[0], arrays
+
+
+def grid_transform_of(cfg):
+    gt = dict(input_scope=cfg['input_scope'], output_scope=cfg['output_scope'])
+    if cfg.get('prescale_factor', 1) != 1:
+        gt['prescale_factor'] = cfg['prescale_factor']
+    return gt
+
+
+def head_kwargs(cfg):
+    """constructor kwargs of ``BEVDeformableHeadWithTime`` (and of the reference's class) for a case"""
+    return dict(num_feature_levels=1, encoder=encoder_cfg(cfg['num_layers']), positional_encoding=POSENC,
+                classes=CLASSES[:cfg.get('num_classes', 6)] if cfg.get('num_classes', 6) <= 6 else
+                [f'c{i}' for i in range(cfg['num_classes'])],
+                loss='focal', grid_transform=grid_transform_of(cfg), in_channels=256,
+                seg_conv_kernel=cfg.get('seg_conv_kernel', 1))
+
+
+def engine_kwargs(cfg, batch=1):
+    """``DDPEngine`` kwargs of a sampler case"""
+    return dict(h=cfg['h'], w=cfg['w'], batch=batch, randsteps=cfg['randsteps'], timesteps=cfg['timesteps'],
+                num_classes=cfg.get('num_classes', 6), feat_channels=cfg['feat_channels'], bit_scale=cfg['bit_scale'],
+                time_difference=cfg.get('time_difference', 1), threshold=cfg.get('threshold', 0.5),
+                bev_input_scope=cfg['input_scope'], bev_output_scope=cfg['output_scope'],
+                bev_prescale=cfg.get('prescale_factor', 1), bev_seg_kernel=cfg.get('seg_conv_kernel', 1))
+
+
+# ---- the two operators ----------------------------------------------------------------------------------------------------------
+def prescale(feat, p):
+    """BEVGridTransform's prescale (reference :71-77), restated without F.interpolate: the output size is floor(in p), the source
+    coordinate (dst + 0.5) / p - 0.5 comes from the GIVEN factor (not from the size ratio), is clamped at 0, and the upper
+    neighbour is clamped at in - 1 (ATen UpSample.h, area_pixel_compute_source_index / compute_source_index_and_lambda).  The size
+    is floor(in p) of the Python DOUBLE: 0.9 on a 10-wide map gives 9 (float32(0.9) would give 8)."""
+    if p == 1:
+        return feat
+    h, w = feat.shape[-2:]
+
+    def axis(n):
+        out = int(np.floor(n * float(p)))
+        rs = torch.tensor(1.0 / float(p), dtype=torch.float32)
+        src = ((torch.arange(out, dtype=torch.float32) + 0.5) * rs - 0.5).clamp(min=0)
+        i0 = src.floor().long().clamp(max=n - 1)
+        i1 = (i0 + 1).clamp(max=n - 1)
+        l1 = (src - i0.to(src.dtype)).to(feat.dtype)
+        return i0, i1, l1
+
+    y0, y1, ly = axis(h)
+    x0, x1, lx = axis(w)
+    ly = ly.view(-1, 1)
+    top = feat[..., y0, :][..., x0] * (1 - lx) + feat[..., y0, :][..., x1] * lx
+    bot = feat[..., y1, :][..., x0] * (1 - lx) + feat[..., y1, :][..., x1] * lx
+    return top * (1 - ly) + bot * ly
+
+
+def head_forward(feat, temb, sd, cfg):
+    """DeformableHeadWithTime.forward (reference :179-235) with both variants: prescale, grid transform (normalised on the
+    prescaled size: grid_sample sees the prescaled map), encoder, conv_seg 1x1 or 3x3 (padding 1), sigmoid."""
+    ft = O.bev_grid_transform(prescale(feat, cfg.get('prescale_factor', 1)), input_scope=cfg['input_scope'],
+                              output_scope=cfg['output_scope'])
+    bs, c, h, w = ft.shape
+    mem = O.encoder_forward(ft, temb, sd)
+    mem = mem.permute(0, 2, 1).reshape(bs, c, h, w).contiguous()
+    k = cfg.get('seg_conv_kernel', 1)
+    return torch.sigmoid(F.conv2d(mem, sd['decode_head.conv_seg.weight'], sd['decode_head.conv_seg.bias'], padding=k // 2))
+
+
+def sample(x, noise, sd, cfg, trace=None):
+    """fusion_models/ddp.py:268-301 for ONE sample with the case's head.  trace (list): per step, the thresholded maps (r,K,H,W),
+    the smallest |prob - threshold|, the noisy maps entering the step (r,256,h,w) and the head's output."""
+    h, w = x.shape[-2:]
+    r, bit, thr = cfg['randsteps'], cfg['bit_scale'], cfg.get('threshold', 0.5)
+    K = cfg.get('num_classes', 6)
+    xr = x.repeat(r, 1, 1, 1)
+    mask_t = noise.clone()
+    outs = []
+    for t_now, t_next in O.sampling_time_pairs(cfg['timesteps'], cfg.get('time_difference', 1), 0.0):
+        times_now = torch.tensor([t_now], dtype=torch.float32)
+        times_next = torch.tensor([t_next], dtype=torch.float32)
+        feat = F.conv2d(torch.cat([xr, mask_t], dim=1), sd['transform.conv.weight'], sd['transform.conv.bias'])
+        log_snr = O.alpha_cosine_log_snr(times_now)
+        log_snr_next = O.alpha_cosine_log_snr(times_next)
+        alpha, sigma = O.log_snr_to_alpha_sigma(log_snr.view(-1, 1, 1, 1))
+        alpha_next, sigma_next = O.log_snr_to_alpha_sigma(log_snr_next.view(-1, 1, 1, 1))
+        temb = O.time_mlp(log_snr, sd)
+        prob = head_forward(feat, temb, sd, cfg)
+        pred = prob > thr
+        if trace is not None:
+            trace.append(dict(pred=pred.clone(), margin=float((prob - thr).abs().min()), mask_in=mask_t.clone(), prob=prob.clone()))
+        pred = pred * (torch.arange(K) + 1).view(1, K, 1, 1)
+        pred = F.interpolate(pred.float(), size=(h, w), mode='nearest').to(torch.int64)
+        e = F.embedding(pred, sd['embedding_table.weight']).mean(dim=1).permute(0, 3, 1, 2)
+        x0 = (torch.sigmoid(e) * 2 - 1) * bit
+        pred_noise = (mask_t - alpha * x0) / sigma.clamp(min=1e-8)
+        mask_t = x0 * alpha_next + pred_noise * sigma_next
+        outs.append(prob)
+    return torch.cat(outs, dim=0).mean(dim=0, keepdim=True), torch.stack(outs)
