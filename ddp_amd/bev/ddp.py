@@ -76,7 +76,10 @@ class DDP(nn.Module, _SamplerMixin):
                                       nn.Linear(tmp_channels * 4, tmp_channels * 4))
 
     @torch.no_grad()
-    def ddim_sample(self, x, head, noise=None):
+    def ddim_sample(self, x, head, noise=None, return_steps=False):
+        """``return_steps``: -> (out, record (K,b,r,head_h,head_w) int32 bit words - bit c = the step's prob_c > threshold
+        (fusion_models/ddp.py:290) -, disagreement (b,head_h,head_w) - the fraction of recorded bits that differ from
+        out > threshold)."""
         x0 = x[0]
         if not x0.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')
@@ -94,11 +97,13 @@ class DDP(nn.Module, _SamplerMixin):
                              threshold=self.threshold, bev_input_scope=head.grid_transform['input_scope'],
                              bev_output_scope=head.grid_transform['output_scope'],
                              bev_prescale=getattr(head, 'prescale_factor', 1.0),
-                             bev_seg_kernel=getattr(head, 'seg_conv_kernel', 1), device=x0.device)
+                             bev_seg_kernel=getattr(head, 'seg_conv_kernel', 1), device=x0.device,
+                             record_steps=return_steps)
         ver = sum(p._version for p in head.parameters())
         # everything of the head that shapes the engine: its identity, grid transform (scopes, prescale) and conv_seg kernel
         gt = head.grid_transform
         hkey = (id(head), repr(gt['input_scope']), repr(gt['output_scope']), getattr(head, 'prescale_factor', 1.0),
-                getattr(head, 'seg_conv_kernel', 1))
+                getattr(head, 'seg_conv_kernel', 1), bool(return_steps))
         eng = self._get_engine((b, c, h, w, str(x0.device), self.timesteps, self.randsteps, ver) + hkey, factory)
-        return eng.sample(x0.contiguous().float(), noise.contiguous().float())
+        out = eng.sample(x0.contiguous().float(), noise.contiguous().float())
+        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out

@@ -93,6 +93,9 @@ struct Layout {
   // bf16x3 mode: split weights and split fragment-major activations
   int b3;
   unsigned char* x0_trace = nullptr;   // DDP_FLAG_RECORD_X0: (K, M) argmax class of every step
+  // DDP_FLAG_STEP_RECORD: the record (K, M) - seg uint8 (== x0_trace), depth fp32, bev uint32 - and the disagreement map (B, Nh)
+  unsigned char* step_rec = nullptr;
+  float* step_map = nullptr;
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
@@ -184,12 +187,17 @@ int validate(const ddp_cfg* c) {
     return DDP_E_BADCFG;
   }
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
-                   DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS)) {
+                   DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
+                   DDP_FLAG_STEP_RECORD)) {
     set_error("unknown flags 0x%x", c->flags);
     return DDP_E_BADCFG;
   }
   if ((c->flags & (DDP_FLAG_FORCE_X0 | DDP_FLAG_RECORD_X0)) && c->task != DDP_TASK_SEG) {
     set_error("DDP_FLAG_RECORD_X0 / DDP_FLAG_FORCE_X0 exist for the segmentation sampler only (task %d)", c->task);
+    return DDP_E_BADCFG;
+  }
+  if ((c->flags & DDP_FLAG_STEP_RECORD) && (c->flags & DDP_FLAG_FORCE_X0)) {
+    set_error("DDP_FLAG_STEP_RECORD cannot be combined with DDP_FLAG_FORCE_X0 (a test instrument with its own trace layout)");
     return DDP_E_BADCFG;
   }
   if (c->depth_n_bins != 0 && c->task != DDP_TASK_DEPTH) {
@@ -251,6 +259,11 @@ int validate(const ddp_cfg* c) {
     return DDP_E_BADCFG;
   }
   return DDP_OK;
+}
+
+// bytes of the step record (include/ddp_mi355x.h): one element per (step, map, head-grid token)
+inline size_t step_record_bytes(const ddp_cfg* c) {
+  return size_t(c->timesteps) * c->batch * c->randsteps * c->head_h * c->head_w * (c->task == DDP_TASK_SEG ? 1 : 4);
 }
 
 void carve(const ddp_cfg* c, float* base, Layout* o) {
@@ -394,7 +407,7 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->pre = cv.take((size_t(o->R) * o->hp * o->wp + 3) / 4 * 4 * 256);
   }
   o->x0_trace = reinterpret_cast<unsigned char*>(
-      cv.take((c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) && c->task == DDP_TASK_SEG
+      cv.take((c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) && c->task == DDP_TASK_SEG && !(c->flags & DDP_FLAG_STEP_RECORD)
                   ? ((c->flags & DDP_FLAG_FORCE_X0 ? 2 : 1) * size_t(o->K) * o->M + 3) / 4
                   : 0));
   if (o->b3) {
@@ -430,6 +443,13 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
       o->rs0 = o->hbuf + Mp * 256;
       o->rvpad = o->rs0 + align64(o->M * 96);
     }
+  }
+  // step record + disagreement map: the LAST two buffers, so that every offset in front of them is the one of the cfg without
+  // the flag.  (seg with DDP_FLAG_RECORD_X0 as well: one buffer serves both flags - the x0 trace moves here)
+  if (c->flags & DDP_FLAG_STEP_RECORD) {
+    o->step_rec = reinterpret_cast<unsigned char*>(cv.take((step_record_bytes(c) + 3) / 4));
+    o->step_map = cv.take(size_t(o->B) * o->Nh);
+    if (c->task == DDP_TASK_SEG) o->x0_trace = o->step_rec;
   }
   o->total = cv.off * sizeof(float);
 }
@@ -863,7 +883,7 @@ SegUpdateArgs seg_update_args(const float* logits, int ldl, int num_classes, con
 }
 
 // the x0 trace of seg step s.  FORCE_X0: [0] = the caller's decisions (read), [1] = the step's own argmax (written); RECORD_X0
-// alone: [0] written
+// alone: [0] written; STEP_RECORD: the same (K, M) record, in the step-record buffer
 struct X0Trace {
   unsigned char* idx = nullptr;
   const unsigned char* force = nullptr;
@@ -873,7 +893,7 @@ X0Trace x0_trace_of(const ddp_cfg* c, const Layout& o, int s) {
   if (c->flags & DDP_FLAG_FORCE_X0) {
     t.force = o.x0_trace + size_t(s) * o.M;
     t.idx = o.x0_trace + size_t(o.K + s) * o.M;
-  } else if (c->flags & DDP_FLAG_RECORD_X0) {
+  } else if (c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_STEP_RECORD)) {
     t.idx = o.x0_trace + size_t(s) * o.M;
   }
   return t;
@@ -1036,6 +1056,32 @@ Plan plan_of(const ddp_cfg* c, const Layout& o) {
   return p;
 }
 
+// The launches DDP_FLAG_STEP_RECORD adds carry the profiler tag no launch of ddp_sample otherwise uses (TAG_GENERIC), so the launch
+// records count them: tests/test_step_record_gpu.py asserts the figures the header states.  Usage: prof_begin(TAG_GENERIC, st) in
+// front of the launch, `return recorded(launch_...(...), st)` behind it
+inline int recorded(int rc, hipStream_t st) {
+  prof_end(TAG_GENERIC, st);
+  return rc;
+}
+
+// DDP_FLAG_STEP_RECORD: the disagreement map from the finished record and the output the sampler just wrote (one launch, last)
+int step_disagreement(const ddp_cfg* c, const Layout& o, const float* d_out, hipStream_t st) {
+  if (!o.step_rec) return DDP_OK;
+  prof_begin(TAG_GENERIC, st);
+  StepDisagreementArgs a{};
+  a.rec = o.step_rec;
+  a.out = d_out;
+  a.map = o.step_map;
+  a.task = c->task;
+  a.B = o.B;
+  a.r = o.r;
+  a.K = o.K;
+  a.N = o.Nh;
+  a.num_classes = o.Kc;
+  a.threshold = c->threshold;
+  return recorded(launch_step_disagreement(a, st), st);
+}
+
 // the segmentation sampler after the xproj hoist: noise staging, K steps, reduction
 int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, const Plan& p, const Layout& o, const float* d_x,
                const float* d_noise, const float* d_step_noise, float* d_out, hipStream_t st) {
@@ -1144,8 +1190,9 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
   }
   // reduction over (steps x r) and token-major -> NCHW (ddp.py:243-245); the layer kernel's tails leave the scores fragment-major
   const int frag_nch = p.seg_tail ? (o.Kc + 63) / 64 : 0;
-  if (c->accumulation) return launch_finalize_nchw(o.prob, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st, frag_nch);
-  return launch_finalize_nchw(o.logits, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r), st, frag_nch);
+  if (c->accumulation) DDP_TRY(launch_finalize_nchw(o.prob, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st, frag_nch));
+  else DDP_TRY(launch_finalize_nchw(o.logits, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r), st, frag_nch));
+  return step_disagreement(c, o, d_out, st);
 }
 
 // the depth sampler after the xproj hoist: noise staging, loop invariants of the chain, K steps, mean over r
@@ -1187,8 +1234,13 @@ int sample_depth(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, 
   tl.threshold = c->threshold;
   tl.ldl = 32;
   auto update_args = [&](const ddp_step& stp) { return depth_update_args(c, w, o, o.nbins ? nullptr : o.logits, o.mask, o.pred, stp); };
+  // DDP_FLAG_STEP_RECORD: the step's metric prediction goes to its slice of the record instead of o.pred (the same kernels write
+  // it, the mean over r reads the last slice)
+  float* const rec = reinterpret_cast<float*>(o.step_rec);
+  float* pred = o.pred;
   for (int s = 0; s < o.K; ++s) {
     const float* aff = o.aff + size_t(s) * o.L * 512;
+    if (rec) pred = rec + size_t(s) * o.M;
     // fused step boundary: the PREVIOUS step's DDIM update (from the taps its last layer's tail left) runs in front of this head
     DepthUpdateArgs prev;
     const DepthUpdateArgs* upd = nullptr;
@@ -1219,15 +1271,28 @@ int sample_depth(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, 
     if (p.depth_lt) {
       // (the nine taps were written by the last layer's tail: k_layer MODE 9)
     } else if (o.nbins) {
-      DDP_TRY(depth_bins_head(c, o, o.pred, st));
+      DDP_TRY(depth_bins_head(c, o, pred, st));
     } else {
       DDP_TRY(head_gemm(c, w, o, st));
     }
     // the update of every step but the last runs inside the next step's head (k_layer MODE 3) on the fused path; the last step's
     // (and every step's on the other paths) here: it also leaves the metric depth prediction the output is made of
-    if (!(p.depth_lt && s + 1 < o.K)) DDP_TRY(launch_depth_update(update_args(steps[s]), st));
+    if (!(p.depth_lt && s + 1 < o.K)) {
+      DepthUpdateArgs ua = update_args(steps[s]);
+      ua.pred = pred;
+      DDP_TRY(launch_depth_update(ua, st));
+    } else if (rec) {
+      // (fused boundary: the next step's head forms this prediction in registers and keeps only the updated depth - the record
+      // takes it from the same taps by k_depth_update's head-only form, which leaves the noisy depth alone)
+      DepthUpdateArgs ua = update_args(steps[s]);
+      ua.pred = pred;
+      ua.depth_t = nullptr;
+      prof_begin(TAG_GENERIC, st);
+      DDP_TRY(recorded(launch_depth_update(ua, st), st));
+    }
   }
-  return launch_mean_r(o.pred, d_out, o.B, o.r, o.N, st);
+  DDP_TRY(launch_mean_r(pred, d_out, o.B, o.r, o.N, st));
+  return step_disagreement(c, o, d_out, st);
 }
 
 // the BEV sampler after the xproj hoist: noise staging (u_0 on the chain), K steps, reduction
@@ -1266,6 +1331,14 @@ int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
   tl.threshold = c->threshold;
   tl.x0_idx = code;
   tl.ldl = 32;
+  // DDP_FLAG_STEP_RECORD: after the step's head, its decisions as bit words - from the code byte on the u chain, else from the
+  // raw logits k_bev_update thresholds (both on the head grid, in front of the nearest resize to the map)
+  auto record = [&](int s) {
+    if (!o.step_rec) return int(DDP_OK);
+    prof_begin(TAG_GENERIC, st);
+    return recorded(launch_bev_record(p.bev_chain ? code : nullptr, o.logits, reinterpret_cast<unsigned*>(o.step_rec) + size_t(s) * o.M,
+                                      o.Kc, c->threshold, int(o.M), st), st);
+  };
   for (int s = 0; s < o.K; ++s) {
     const ddp_step& sp = steps[s];
     const float* aff = o.aff + size_t(s) * o.L * 512;
@@ -1296,17 +1369,23 @@ int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
                             p.bev_chain && !p.bev_seg3 ? &tl : nullptr));
     if (p.bev_seg3) {
       DDP_TRY(bev_seg3_head(c, o, s == 0, p.bev_chain ? code : nullptr, p.bev_chain ? nullptr : o.logits, st));
+      DDP_TRY(record(s));
       if (p.bev_chain) continue;
       BevUpdateArgs ua = bev_update_args(c, w, o, o.mask, s == 0, sp);
       ua.prob = nullptr;             // (k_bev_seg3 accumulated the probabilities)
       DDP_TRY(launch_bev_update(ua, st));
       continue;
     }
-    if (p.bev_chain) continue;     // (the next step's head updates u from the codes the tail wrote)
+    if (p.bev_chain) {             // (the next step's head updates u from the codes the tail wrote)
+      DDP_TRY(record(s));
+      continue;
+    }
     DDP_TRY(head_gemm(c, w, o, st));
+    DDP_TRY(record(s));
     DDP_TRY(launch_bev_update(bev_update_args(c, w, o, o.mask, s == 0, sp), st));
   }
-  return launch_finalize_nchw(o.prob, 32, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st);
+  DDP_TRY(launch_finalize_nchw(o.prob, 32, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st));
+  return step_disagreement(c, o, d_out, st);
 }
 
 }  // namespace
@@ -1471,13 +1550,14 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
 int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_idx) {
   DDP_TRY(validate(cfg));
   DDP_TRY(check_ptr(d_workspace, "workspace"));
-  if (!d_idx || !(cfg->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) || cfg->task != DDP_TASK_SEG) {
+  const bool step_rec = d_idx && (cfg->flags & DDP_FLAG_STEP_RECORD);
+  if (!step_rec && (!d_idx || !(cfg->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) || cfg->task != DDP_TASK_SEG)) {
     set_error("x0_trace: needs a segmentation cfg with DDP_FLAG_RECORD_X0 or DDP_FLAG_FORCE_X0");
     return DDP_E_BADCFG;
   }
   Layout o;
   carve(cfg, static_cast<float*>(d_workspace), &o);
-  *d_idx = o.x0_trace;
+  *d_idx = step_rec ? o.step_rec : o.x0_trace;
   return DDP_OK;
 }
 
@@ -2329,6 +2409,9 @@ struct FcnLoopLayout {
   // images of the FiLM-scaled 3x3 weights and the shift vector; conv_seg's images and padded bias
   unsigned char *conv_streams, *cls_stream;
   float *conv_shifts, *cls_bias;
+  // DDP_FLAG_STEP_RECORD: (K, M) uint8 record and the (B, N) disagreement map - the last two buffers of the workspace
+  unsigned char* step_rec;
+  float* step_map;
   size_t bytes;
 };
 int fcn_loop_layout(const ddp_cfg* c, int num_convs, char* base, FcnLoopLayout* o) {
@@ -2363,6 +2446,9 @@ int fcn_loop_layout(const ddp_cfg* c, int num_convs, char* base, FcnLoopLayout* 
   o->conv_shifts = takef(size_t(c->timesteps) * (num_convs > 0 ? num_convs : 1) * 256);
   o->cls_stream = reinterpret_cast<unsigned char*>(take(size_t(8) * b3_stage_bytes()));
   o->cls_bias = takef(256);
+  const bool rec = (c->flags & DDP_FLAG_STEP_RECORD) != 0;
+  o->step_rec = rec ? reinterpret_cast<unsigned char*>(take(step_record_bytes(c))) : nullptr;
+  o->step_map = rec ? takef(size_t(c->batch) * N) : nullptr;
   o->bytes = off;
   return DDP_OK;
 }
@@ -2517,10 +2603,24 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
       DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M * 256, o.snoise, R, 256, N, st));
       a.step_noise = o.snoise;
     }
+    a.x0_idx = o.step_rec ? o.step_rec + size_t(s) * M : nullptr;
     DDP_TRY(launch_seg_update(a, st));
   }
-  if (cfg->accumulation) return launch_finalize_nchw(o.prob, o.head.ldl, d_out, B, r, N, Kc, float(r * K), st);
-  return launch_finalize_nchw(o.head.logits, o.head.ldl, d_out, B, r, N, Kc, float(r), st);
+  if (cfg->accumulation) DDP_TRY(launch_finalize_nchw(o.prob, o.head.ldl, d_out, B, r, N, Kc, float(r * K), st));
+  else DDP_TRY(launch_finalize_nchw(o.head.logits, o.head.ldl, d_out, B, r, N, Kc, float(r), st));
+  if (!o.step_rec) return DDP_OK;
+  StepDisagreementArgs da{};
+  da.rec = o.step_rec;
+  da.out = d_out;
+  da.map = o.step_map;
+  da.task = DDP_TASK_SEG;
+  da.B = B;
+  da.r = r;
+  da.K = K;
+  da.N = N;
+  da.num_classes = Kc;
+  prof_begin(TAG_GENERIC, st);
+  return recorded(launch_step_disagreement(da, st), st);
 }
 
 }  // extern "C"

@@ -18,6 +18,10 @@
 
 namespace ddp {
 
+// torch.sigmoid as every kernel of the library evaluates it - ONE definition: the bev step record (ddp_step_record.hip) must threshold
+// the same value k_bev_update / k_bev_seg3 (ddp_kernels.hip) feed back
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 
@@ -404,5 +408,20 @@ int launch_bev_q(const float* u, const float* rx, float* q_blk, int R, int r, co
 int launch_build_bev_lut(const float* emb, float* lut, int K, float bit_scale, hipStream_t st);
 int launch_bev_u_update(float* u, const unsigned char* code, const float* tlut, int R, const BevGeom& g, float ua, float uc,
                         hipStream_t st);
+
+// ---- ddp_step_record.hip (DDP_FLAG_STEP_RECORD) ---------------------------------------------------
+// bev step record: rec[m] bit c = prob_c > threshold at head-grid token m, from the u chain's code byte (code, K_cls <= 8) or,
+// code == nullptr, from the raw conv_seg logits (M, 32) of the separate kernels
+int launch_bev_record(const unsigned char* code, const float* logits, unsigned* rec, int num_classes, float threshold, int M,
+                      hipStream_t st);
+// the step-disagreement map (B, N) from the record (K, B, r, N) and the sampler's output (B, K_cls, N) - include/ddp_mi355x.h
+struct StepDisagreementArgs {
+  const void* rec;      // seg uint8 classes, depth fp32 predictions, bev uint32 bit words
+  const float* out;     // what ddp_sample returned (seg / bev; unused for depth)
+  float* map;
+  int task, B, r, K, N, num_classes;
+  float threshold;
+};
+int launch_step_disagreement(const StepDisagreementArgs& a, hipStream_t st);
 
 }  // namespace ddp

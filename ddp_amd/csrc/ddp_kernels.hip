@@ -18,7 +18,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------
 // NCHW (R, C, N) -> token-major (R, N, C): 64x64 tiles through LDS (stride 65: conflict-free both ways)

@@ -95,7 +95,9 @@ class DDP(nn.Module, _SamplerMixin):
                 for a, b in schedule.get_sampling_timesteps(self.timesteps, self.time_difference, 0.0)]
 
     @torch.no_grad()
-    def sample(self, x, img_metas=None, noise=None):
+    def sample(self, x, img_metas=None, noise=None, return_steps=False):
+        """``return_steps``: -> (out, record (K,b,r,h,w) float32 - every step's ``depth_pred`` (depther/ddp.py:239) -, disagreement
+        (b,h,w) - their standard deviation per pixel)."""
         if not x.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')
         b, c, h, w = x.shape
@@ -120,12 +122,14 @@ class DDP(nn.Module, _SamplerMixin):
             return DDPEngine(self.hot_path_state_dict(), 'depth', h=h, w=w, batch=b, randsteps=self.randsteps,
                              timesteps=self.timesteps, bit_scale=self.bit_scale, time_difference=self.time_difference,
                              min_depth=self.min_depth, max_depth=self.max_depth, depth_scale_up=su, depth_use_eps=ue,
-                             head_min_depth=hmin, head_max_depth=hmax, depth_bins=bins, depth_norm=norm, device=x.device)
+                             head_min_depth=hmin, head_max_depth=hmax, depth_bins=bins, depth_norm=norm, device=x.device,
+                             record_steps=return_steps)
         # keyed without the geometry: a new (b, h, w) re-uses the engine through set_geometry (no weight repacking)
         bins_key = None if bins is None else (getattr(head, 'bins_strategy', None), head.n_bins, norm)
         eng = self._get_engine(('depth', str(x.device), self.timesteps, self.randsteps, self.bit_scale, self.time_difference,
-                                self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key), factory, geometry=(b, h, w))
-        return eng.sample(x.contiguous().float(), noise.contiguous().float())
+                                self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key, bool(return_steps)), factory, geometry=(b, h, w))
+        out = eng.sample(x.contiguous().float(), noise.contiguous().float())
+        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)

@@ -146,8 +146,10 @@ class DDPEngine:
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
-                 bev_prescale=1.0, bev_seg_kernel=1):
-        """depth: ``min_depth`` / ``max_depth`` are the depther's range (x0 normalisation); ``head_min_depth`` / ``head_max_depth``
+                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False):
+        """``record_steps`` (DDP_FLAG_STEP_RECORD): keep every step's prediction and compute the step-disagreement map on the
+        device - ``step_record()`` / ``step_disagreement()`` after ``sample()``.
+        depth: ``min_depth`` / ``max_depth`` are the depther's range (x0 normalisation); ``head_min_depth`` / ``head_max_depth``
         the decode head's (eps of the regression head; default: the depther's).  ``depth_bins`` (n_bins) = the bin centres of a
         binned head (``classify=True``: conv_depth has n_bins outputs, ``depth_norm`` in 'linear' / 'softmax' / 'sigmoid'); with
         ``weights`` given, the bins are the ones packed there.
@@ -224,6 +226,8 @@ class DDPEngine:
             cfg.flags |= _lib.FLAG_FORCE_X0
         if gather_guess_zero:      # diagnostic: forces the LDS gather's refill branch (identical results)
             cfg.flags |= _lib.FLAG_GATHER_GUESS_ZERO
+        if record_steps:
+            cfg.flags |= _lib.FLAG_STEP_RECORD
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
         cfg.bit_scale, cfg.min_depth, cfg.max_depth, cfg.threshold = bit_scale, min_depth, max_depth, threshold
@@ -241,6 +245,7 @@ class DDPEngine:
         _lib.check(self.lib.ddp_query_const_workspace(C.byref(cfg), C.byref(cbytes)), self.lib)
         self._const_floats = cbytes.value // 4       # model region: a prefix of the workspace, independent of the geometry
         self._prepared = False
+        self._sampled = False
         self.geometry_changes = 0
 
     # ------------------------------------------------------------------------------------------
@@ -283,6 +288,7 @@ class DDPEngine:
         self.cfg, self.workspace = n, ws
         self.geometry_changes += 1
         self._x0_set = False       # force_x0: the decisions buffer belongs to the geometry region
+        self._sampled = False      # (so do the step record and the disagreement map)
         return self
 
     def out_shape(self):
@@ -319,7 +325,27 @@ class DDPEngine:
             _lib.check(self.lib.ddp_sample(C.byref(c), C.byref(self.weights.struct), self.steps, x.data_ptr(),
                                            noise.data_ptr(), step_noise.data_ptr() if step_noise is not None else None,
                                            out.data_ptr(), self.workspace.data_ptr(), self._stream()), self.lib)
+        self._sampled = True
         return out
+
+    def _step_base(self):
+        if not self.cfg.flags & _lib.FLAG_STEP_RECORD:
+            raise _lib.DdpError('step_record() / step_disagreement() need an engine built with record_steps=True')
+        if not getattr(self, '_sampled', False):
+            raise _lib.DdpError('no step record yet: call sample() first')
+        p = C.c_void_p()
+        _lib.check(self.lib.ddp_x0_trace(C.byref(self.cfg), self.workspace.data_ptr(), C.byref(p)), self.lib)
+        return p.value - self.workspace.data_ptr()
+
+    def step_record(self):
+        """(K, B, r, H, W): what every step of the LAST sample() call predicted, per noise replica - seg uint8 argmax class, depth
+        float32 metric depth, bev int32 bit words (bit c = prob_c > threshold; the C side's uint32).  A fresh tensor."""
+        return step_record_view(self.workspace, self._step_base(), self.cfg).clone()
+
+    def step_disagreement(self):
+        """(B, H, W) float32: where the K * r recorded predictions of the LAST sample() call disagree with its output - seg / bev
+        the fraction of differing decisions, depth the standard deviation (include/ddp_mi355x.h).  A fresh tensor."""
+        return step_disagreement_view(self.workspace, self._step_base(), self.cfg).clone()
 
     def capture(self, x, noise, step_noise=None):
         """One ``sample()`` call as a hipGraph (``torch.cuda.CUDAGraph`` is hipGraph on ROCm): ``ddp_sample`` neither
@@ -388,6 +414,28 @@ class DDPEngine:
         return out
 
 
+def step_record_sizes(cfg):
+    """(record_bytes, map_bytes) of include/ddp_mi355x.h (DDP_FLAG_STEP_RECORD), as formulas of the cfg"""
+    n = cfg.batch * cfg.head_h * cfg.head_w
+    return cfg.timesteps * cfg.randsteps * n * (1 if cfg.task == _lib.TASK_SEG else 4), n * 4
+
+
+def _round256(n):
+    return (n + 255) // 256 * 256
+
+
+def step_record_view(workspace, base, cfg):
+    dtype = {_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32}[cfg.task]
+    nbytes = step_record_sizes(cfg)[0]
+    return workspace.view(torch.uint8)[base:base + nbytes].view(dtype).view(cfg.timesteps, cfg.batch, cfg.randsteps, cfg.head_h, cfg.head_w)
+
+
+def step_disagreement_view(workspace, base, cfg):
+    rec, nbytes = step_record_sizes(cfg)
+    off = base + _round256(rec)
+    return workspace.view(torch.uint8)[off:off + nbytes].view(torch.float32).view(cfg.batch, cfg.head_h, cfg.head_w)
+
+
 class SampleGraph:
     """A captured ``DDPEngine.sample`` call (``DDPEngine.capture``).  ``replay(x, noise)`` copies the inputs into the graph's
     static buffers (stream-ordered, on the current stream) and launches the graph; the returned tensor is the graph's static
@@ -427,7 +475,7 @@ class FcnSamplerEngine:
 
     def __init__(self, state_dict, head, *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150, bit_scale=0.01,
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
-                 device=None, head_prefix='decode_head.', lib_path=None):
+                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False):
         self.lib = _lib.load(lib_path)
         if not torch.cuda.is_available():
             raise _lib.DdpError('no HIP device visible: ddp_amd has no CPU path')
@@ -445,7 +493,7 @@ class FcnSamplerEngine:
         cfg.num_classes, cfg.feat_channels = num_classes, 256
         cfg.h = cfg.head_h = h
         cfg.w = cfg.head_w = w
-        cfg.gemm_mode, cfg.flags = _lib.GEMM_BF16X3, 0
+        cfg.gemm_mode, cfg.flags = _lib.GEMM_BF16X3, (_lib.FLAG_STEP_RECORD if record_steps else 0)
         cfg.accumulation, cfg.bit_scale = int(bool(accumulation)), bit_scale
         self.cfg, self.sampler = cfg, sampler
         recs = schedule.step_records('seg', timesteps, time_difference, sample_range0, noise_schedule, sampler)
@@ -455,8 +503,10 @@ class FcnSamplerEngine:
                 setattr(self.steps[i], k, v)
         nbytes = C.c_size_t(0)
         _lib.check(self.lib.ddp_sample_fcn_workspace(C.byref(cfg), head.num_convs, head.dilation, C.byref(nbytes)), self.lib)
+        self._ws_bytes = nbytes.value
         self.workspace = torch.empty(nbytes.value // 4 + 64, dtype=torch.float32, device=self.device)
         self._prepared = False
+        self._sampled = False
 
     def prepare(self):
         """``ddp_prepare_fcn``: everything that depends on weights and schedule only (time embeddings, x0 table, concat-conv
@@ -489,7 +539,24 @@ class FcnSamplerEngine:
                                                step_noise.data_ptr() if step_noise is not None else None, out.data_ptr(),
                                                self.workspace.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
                        self.lib)
+        self._sampled = True
         return out
+
+    def _step_base(self):
+        if not self.cfg.flags & _lib.FLAG_STEP_RECORD:
+            raise _lib.DdpError('step_record() / step_disagreement() need an engine built with record_steps=True')
+        if not self._sampled:
+            raise _lib.DdpError('no step record yet: call sample() first')
+        rec, smap = step_record_sizes(self.cfg)      # the last two buffers of ddp_sample_fcn's workspace (include/ddp_mi355x.h)
+        return self._ws_bytes - _round256(smap) - _round256(rec)
+
+    def step_record(self):
+        """(K, B, r, h, w) uint8: the argmax class every step of the LAST sample() call fed back.  A fresh tensor."""
+        return step_record_view(self.workspace, self._step_base(), self.cfg).clone()
+
+    def step_disagreement(self):
+        """(B, h, w) float32: the fraction of the K * r recorded decisions that differ from the output's argmax.  A fresh tensor."""
+        return step_disagreement_view(self.workspace, self._step_base(), self.cfg).clone()
 
 
 def seg_postprocess(scores, img_size, crop_size=None, out_size=None, align_corners=False, flip=None, out=None):

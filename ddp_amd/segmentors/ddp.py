@@ -134,16 +134,18 @@ class DDP(nn.Module, _SamplerMixin):
             times.append(t[:, None].repeat(1, batch))
         return times
 
-    def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample'):
+    def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample',
+                    record_steps=False):
         from ..decode_heads.fcn_head_with_time import FCNHeadWithTime
         K = self.timesteps if timesteps is None else timesteps
         r = self.randsteps if randsteps is None else randsteps
         acc = self.accumulation if accumulation is None else accumulation
         common = dict(batch=b, randsteps=r, timesteps=K, num_classes=self.num_classes, bit_scale=self.bit_scale,
                       time_difference=self.time_difference, sample_range0=self.sample_range[0],
-                      noise_schedule=self.noise_schedule, sampler=sampler, accumulation=acc, device=device)
+                      noise_schedule=self.noise_schedule, sampler=sampler, accumulation=acc, device=device,
+                      record_steps=record_steps)
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule)
+               self.noise_schedule, bool(record_steps))
         if isinstance(self.decode_head, FCNHeadWithTime):
             # any registered head goes through _decode_head_forward_test in the reference (ddp.py:192-196); here the loop
             # around FCNHeadWithTime is its own C entry (ddp_sample_fcn), one engine per geometry
@@ -169,26 +171,30 @@ class DDP(nn.Module, _SamplerMixin):
             raise RuntimeError(f'expected {self.decode_head.in_channels[0]} feature channels, got {x.shape[1]}')
 
     @torch.no_grad()
-    def ddim_sample(self, x, img_metas=None, noise=None):
+    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False):
         """x (b,256,h,w) -> (b,K,h,w).  ``noise`` (b,r,256,h,w) may be injected (parity tests);
-        by default it is drawn with torch.randn like the reference (ddp.py:220)."""
+        by default it is drawn with torch.randn like the reference (ddp.py:220).
+        ``return_steps``: -> (out, record (K,b,r,h,w) uint8 - every step's argmax class, the reference's ``outs`` as decisions -,
+        disagreement (b,h,w) - the fraction of them that differ from the output's argmax)."""
         self._check_feature(x)
         b, c, h, w = x.shape
         if noise is None:
             noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
-        eng = self._engine_for(b, h, w, x.device, 'ddim')
-        return eng.sample(x.contiguous().float(), noise.contiguous().float())
+        eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps)
+        out = eng.sample(x.contiguous().float(), noise.contiguous().float())
+        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     @torch.no_grad()
-    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None):
+    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False):
         self._check_feature(x)
         b, c, h, w = x.shape
         if noise is None:
             noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
         if step_noise is None:
             step_noise = torch.randn((self.timesteps, b, self.randsteps, c, h, w), device=x.device)
-        eng = self._engine_for(b, h, w, x.device, 'ddpm')
-        return eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
+        eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps)
+        out = eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
+        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)

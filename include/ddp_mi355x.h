@@ -86,6 +86,10 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
        /* depth head variants (depth/depth/models/decode_heads/decode_head.py:252-262; model configuration, not diagnostics): */
        DDP_FLAG_DEPTH_SCALE_UP = 256 /* depth = sigmoid(conv_depth) * eps, eps = max_depth (or 1 with NO_EPS) instead of relu(conv_depth) + eps */,
        DDP_FLAG_DEPTH_NO_EPS = 512 /* use_eps=False: eps = 0 (relu branch) / 1 (scale_up branch) instead of min_depth / max_depth */,
+       DDP_FLAG_STEP_RECORD = 1024 /* model surface, all three tasks, both samplers, both engines, ddp_sample and ddp_sample_fcn: keep every
+                                      step's prediction (the reference's `outs`, segmentors/ddp.py:241-245) and compute the step-
+                                      disagreement map on the device - see ddp_x0_trace.  Refused together with DDP_FLAG_FORCE_X0; any
+                                      other flag may be combined.  Clear: launches, workspace sizes and outputs are unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
@@ -230,6 +234,30 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
  * set_x0_decisions() ran.  Both flags are rejected (DDP_E_BADCFG) for tasks other than DDP_TASK_SEG.
  * The workspace LAYOUT (which bytes hold what, incl. this buffer's place) is an implementation detail of one build: it is
  * queried, never assumed, and may change between library builds of the same DDP_ABI_VERSION. */
+/* DDP_FLAG_STEP_RECORD (any task): *d_idx is the base of the STEP RECORD instead, and no other flag is needed.  After ddp_sample
+ * the record holds one slice per step s, (K, B, r, H, W) with (H, W) = (head_h, head_w) (== (h, w) for seg and depth); the element
+ * type behind the `unsigned char*` depends on the task:
+ *   seg   uint8   the argmax class of the step's scores per replica - the value ddp.py:235 feeds back, i.e. the DDP_FLAG_RECORD_X0
+ *                 trace (with both flags set ONE buffer is carved and both describe it)
+ *   depth float   the head's metric prediction of the step (`depth_pred`, depther/ddp.py:239), before normalisation and before the
+ *                 clamp of encode_decode
+ *   bev   uint32  bit c = (prob_c > threshold) at the head-grid pixel (fusion_models/ddp.py:290), before the nearest resize
+ * Sizes, as formulas of the cfg:
+ *   record_bytes = timesteps * batch * randsteps * head_h * head_w * (seg: 1, depth / bev: 4)
+ *   map_bytes    = batch * head_h * head_w * 4
+ * Both are carved at the END of the workspace, each rounded up to 256 bytes: ddp_query_workspace grows by
+ * round256(record_bytes) + round256(map_bytes), every other offset and ddp_query_const_workspace are those of the cfg without
+ * the flag.  The STEP-DISAGREEMENT MAP, (B, H, W) float, starts at *d_idx + round256(record_bytes) and is written once per
+ * ddp_sample by k_step_disagreement, after the output (same stream, hipGraph-capturable like the rest):
+ *   seg   the fraction of the K * r recorded decisions of the pixel that differ from its final decision = argmax over the classes
+ *         of the output ddp_sample returned (first maximum wins, as ddp_seg_postprocess)
+ *   bev   the mean over the K * r records and the K_cls classes of [bit_c != (out_c > threshold)], out = the returned mean probability
+ *   depth the standard deviation of the K * r recorded predictions (two passes in fp32, population form)
+ * K * r = 1 gives zeros.  ddp_sample_fcn honours the flag the same way (seg record and map); ddp_x0_trace does not know that
+ * loop's layout: there the two buffers are the last of ITS workspace, the record at
+ * ddp_sample_fcn_workspace(cfg) - round256(map_bytes) - round256(record_bytes), the map behind it as above.
+ * Extra launches with the flag set: one k_step_disagreement per call; bev + one k_bev_record per step; depth + one head-only
+ * k_depth_update per step whose update runs fused inside the next step's head (the fused step boundary); seg none. */
 int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_idx);
 
 /* ---- finer-grained entry points (unit tests, and the decode_head plugin surface) ------------- */

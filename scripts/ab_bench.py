@@ -63,7 +63,9 @@ def main():
             os.environ.update(env)
             try:
                 if name not in engines:
-                    engines[name] = DDPEngine(sd, task, lib_path=path, **kw)
+                    # DDP_STEP_RECORD=1 in a variant's environment: DDP_FLAG_STEP_RECORD set (needs a library that knows the flag)
+                    rec_kw = dict(record_steps=True) if os.environ.get('DDP_STEP_RECORD') == '1' else {}
+                    engines[name] = DDPEngine(sd, task, lib_path=path, **rec_kw, **kw)
                     engines[name].prepare()
                 eng = engines[name]
                 out = eng.sample(dx, dn)
@@ -73,6 +75,7 @@ def main():
                     if ref is None:
                         ref = o
                     err = float((o - ref).abs().max() / ref.abs().max())
+                    same_bits = bool(torch.equal(o, ref))
                 t0 = time.perf_counter()
                 for _ in range(args.reps):
                     eng.sample(dx, dn, out=out)
@@ -92,6 +95,7 @@ def main():
                 rec = dict(ms_per_batch=round(ms, 3), images_per_s=round(wl['batch'] / ms * 1e3, 2), kernels_ms=per)
                 if rnd == 0:
                     rec['max_rel_vs_first'] = err
+                    rec['bit_identical_to_first'] = same_bits
                 results[name].append(rec)
                 print(name, json.dumps(rec), flush=True)
             finally:
