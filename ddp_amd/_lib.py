@@ -18,6 +18,7 @@ GEMM_F32_MFMA, GEMM_BF16X3 = 0, 1
 FLAG_UNFUSED_LAYER, FLAG_UNFUSED_PROLOGUE, FLAG_RECORD_X0, FLAG_GATHER_GUESS_ZERO, FLAG_FCN_PREPARED, FLAG_FORCE_X0, FLAG_UNFUSED_TAIL, FLAG_SB_HEAD = 1, 2, 4, 8, 16, 32, 64, 128
 FLAG_DEPTH_SCALE_UP, FLAG_DEPTH_NO_EPS = 256, 512
 FLAG_STEP_RECORD = 1024
+FLAG_SEEDED_NOISE = 2048
 DEPTH_NORM_LINEAR, DEPTH_NORM_SOFTMAX, DEPTH_NORM_SIGMOID = 0, 1, 2
 MAX_DEPTH_BINS = 256
 BEV_MAX_PRESCALE_AREA = 16

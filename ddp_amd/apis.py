@@ -41,9 +41,15 @@ def _to_device(data, device):
     return data
 
 
-def _run_batch(model, data, device, **kwargs):
+def _run_batch(model, data, device, batch_indices=None, **kwargs):
     data = dict(data)
     data['img'] = _to_device(data['img'], device)
+    # seeded noise (model.noise_seed set): image i of the batch draws the noise of dataset index batch_indices[0] + i, whatever
+    # samples_per_gpu is and whichever rank the batch landed on (a batch_sampler of a sequential or strided sampler hands out
+    # increasing indices; the first one names the batch)
+    inner = getattr(model, 'module', model)
+    if getattr(inner, 'noise_seed', None) is not None and batch_indices:
+        kwargs = dict(kwargs, image_base=int(batch_indices[0]))
     with torch.no_grad():
         return model(return_loss=False, **kwargs, **data)
 
@@ -68,7 +74,7 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     dataset = data_loader.dataset
     results = []
     for batch_indices, data in zip(data_loader.batch_sampler, data_loader):
-        result = _run_batch(model, data, device)
+        result = _run_batch(model, data, device, batch_indices)
         results.extend(_post(dataset, result, batch_indices, pre_eval, format_only, format_args))
     return results
 
@@ -82,7 +88,7 @@ def multi_gpu_test(model, data_loader, tmpdir=None, gpu_collect=False, pre_eval=
     dataset = data_loader.dataset
     results = []
     for batch_indices, data in zip(data_loader.batch_sampler, data_loader):
-        result = _run_batch(model, data, device, rescale=True)
+        result = _run_batch(model, data, device, batch_indices, rescale=True)
         results.extend(_post(dataset, result, batch_indices, pre_eval, format_only, format_args))
     return collect_results(results, len(dataset), tmpdir=tmpdir, gpu_collect=gpu_collect)
 

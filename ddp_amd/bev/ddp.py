@@ -55,8 +55,11 @@ class DDP(nn.Module, _SamplerMixin):
 
     def __init__(self, bit_scale=1, timesteps=1, randsteps=1, time_difference=1, learned_sinusoidal_dim=16,
                  sample_range=(0, 0.999), noise_schedule='cosine', diffusion='ddim', threshold=0.5,
-                 feat_channels=512, tmp_channels=256, **kwargs):
+                 feat_channels=512, tmp_channels=256, noise_seed=None, **kwargs):
+        """``noise_seed`` (not a reference kwarg): None - torch.randn per call; an integer - the start noise is generated on the
+        device (DDP_FLAG_SEEDED_NOISE) from (noise_seed, image index, call)."""
         super().__init__()
+        self.noise_seed = noise_seed
         if noise_schedule not in schedule.NOISE_SCHEDULES:
             raise ValueError(f'invalid noise schedule {noise_schedule}')
         if tmp_channels != 256:
@@ -76,15 +79,17 @@ class DDP(nn.Module, _SamplerMixin):
                                       nn.Linear(tmp_channels * 4, tmp_channels * 4))
 
     @torch.no_grad()
-    def ddim_sample(self, x, head, noise=None, return_steps=False):
-        """``return_steps``: -> (out, record (K,b,r,head_h,head_w) int32 bit words - bit c = the step's prob_c > threshold
+    def ddim_sample(self, x, head, noise=None, return_steps=False, image_base=0, call=0):
+        """With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
+        ``return_steps``: -> (out, record (K,b,r,head_h,head_w) int32 bit words - bit c = the step's prob_c > threshold
         (fusion_models/ddp.py:290) -, disagreement (b,head_h,head_w) - the fraction of recorded bits that differ from
         out > threshold)."""
         x0 = x[0]
         if not x0.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')
         b, c, h, w = x0.shape
-        if noise is None:
+        seeded = noise is None and self.noise_seed is not None
+        if noise is None and not seeded:
             noise = torch.randn((b, self.randsteps, 256, h, w), device=x0.device)
         sd = dict(self.state_dict())
         sd.update({'decode_head.' + k: v for k, v in head.state_dict().items()})
@@ -98,12 +103,15 @@ class DDP(nn.Module, _SamplerMixin):
                              bev_output_scope=head.grid_transform['output_scope'],
                              bev_prescale=getattr(head, 'prescale_factor', 1.0),
                              bev_seg_kernel=getattr(head, 'seg_conv_kernel', 1), device=x0.device,
-                             record_steps=return_steps)
+                             record_steps=return_steps, seeded_noise=seeded)
         ver = sum(p._version for p in head.parameters())
         # everything of the head that shapes the engine: its identity, grid transform (scopes, prescale) and conv_seg kernel
         gt = head.grid_transform
         hkey = (id(head), repr(gt['input_scope']), repr(gt['output_scope']), getattr(head, 'prescale_factor', 1.0),
-                getattr(head, 'seg_conv_kernel', 1), bool(return_steps))
+                getattr(head, 'seg_conv_kernel', 1), bool(return_steps), seeded)
         eng = self._get_engine((b, c, h, w, str(x0.device), self.timesteps, self.randsteps, ver) + hkey, factory)
-        out = eng.sample(x0.contiguous().float(), noise.contiguous().float())
+        if seeded:
+            out = eng.sample(x0.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
+        else:
+            out = eng.sample(x0.contiguous().float(), noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out

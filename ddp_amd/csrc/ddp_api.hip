@@ -96,6 +96,7 @@ struct Layout {
   // DDP_FLAG_STEP_RECORD: the record (K, M) - seg uint8 (== x0_trace), depth fp32, bev uint32 - and the disagreement map (B, Nh)
   unsigned char* step_rec = nullptr;
   float* step_map = nullptr;
+  float* seed_noise = nullptr;   // DDP_FLAG_SEEDED_NOISE: (B, r, Cm, h, w) start noise of the call, written by k_noise_fill_nchw
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
@@ -188,7 +189,7 @@ int validate(const ddp_cfg* c) {
   }
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
                    DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
-                   DDP_FLAG_STEP_RECORD)) {
+                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE)) {
     set_error("unknown flags 0x%x", c->flags);
     return DDP_E_BADCFG;
   }
@@ -444,6 +445,9 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
       o->rvpad = o->rs0 + align64(o->M * 96);
     }
   }
+  // seeded start noise: immediately in front of the step-record buffers (the end of the workspace without them), so that the record
+  // and the map stay the last of the workspace and every other offset is the one of the cfg without the flag
+  if (c->flags & DDP_FLAG_SEEDED_NOISE) o->seed_noise = cv.take(o->M0 * o->Cm);
   // step record + disagreement map: the LAST two buffers, so that every offset in front of them is the one of the cfg without
   // the flag.  (seg with DDP_FLAG_RECORD_X0 as well: one buffer serves both flags - the x0 trace moves here)
   if (c->flags & DDP_FLAG_STEP_RECORD) {
@@ -1065,6 +1069,13 @@ inline int recorded(int rc, hipStream_t st) {
 }
 
 // DDP_FLAG_STEP_RECORD: the disagreement map from the finished record and the output the sampler just wrote (one launch, last)
+// DDP_FLAG_SEEDED_NOISE: d_noise is the device key; the start noise of the call goes to `buf` (B images of `per_image` floats, NCHW),
+// which every consumer then reads in place of the caller's tensor (one launch, first)
+int seeded_start_noise(const uint32_t* key, float* buf, int B, size_t per_image, hipStream_t st) {
+  prof_begin(TAG_GENERIC, st);
+  return recorded(launch_noise_fill_nchw(key, buf, B, per_image, st), st);
+}
+
 int step_disagreement(const ddp_cfg* c, const Layout& o, const float* d_out, hipStream_t st) {
   if (!o.step_rec) return DDP_OK;
   prof_begin(TAG_GENERIC, st);
@@ -1084,7 +1095,7 @@ int step_disagreement(const ddp_cfg* c, const Layout& o, const float* d_out, hip
 
 // the segmentation sampler after the xproj hoist: noise staging, K steps, reduction
 int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, const Plan& p, const Layout& o, const float* d_x,
-               const float* d_noise, const float* d_step_noise, float* d_out, hipStream_t st) {
+               const float* d_noise, const float* d_step_noise, const uint32_t* key, float* d_out, hipStream_t st) {
   const int M = int(o.M), M0 = int(o.M0);
   if (p.head7) {
     // (the first step's head reads d_noise itself)
@@ -1183,7 +1194,12 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
     a.x0_force = x0.force;
     a.x0_idx = x0.idx;
     if (c->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
-      DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
+      if (key) {   // DDP_FLAG_SEEDED_NOISE: the step's noise is generated token-major - no NCHW tensor, no transpose
+        prof_begin(TAG_GENERIC, st);
+        DDP_TRY(recorded(launch_noise_fill_tok(key, o.snoise, o.B, o.r, o.N, s, st), st));
+      } else {
+        DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
+      }
       a.step_noise = o.snoise;
     }
     DDP_TRY(launch_seg_update(a, st));
@@ -1525,11 +1541,18 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     set_error("steps is NULL");
     return DDP_E_NULL;
   }
-  if (cfg->sampler == DDP_SAMPLER_DDPM) DDP_TRY(check_ptr(d_step_noise, "step_noise"));
+  const bool seeded = (cfg->flags & DDP_FLAG_SEEDED_NOISE) != 0;
+  if (cfg->sampler == DDP_SAMPLER_DDPM && !seeded) DDP_TRY(check_ptr(d_step_noise, "step_noise"));
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout o;
   carve(cfg, static_cast<float*>(d_workspace), &o);
   const Plan p = plan_of(cfg, o);
+  const uint32_t* key = nullptr;
+  if (seeded) {
+    key = reinterpret_cast<const uint32_t*>(d_noise);
+    DDP_TRY(seeded_start_noise(key, o.seed_noise, o.B, size_t(o.r) * o.Cm * o.N, st));
+    d_noise = o.seed_noise;
+  }
   // loop-invariant half of the concat-conv: xproj = W_x x + b  (ddp.py:223-224 with the x columns hoisted)
   if (p.head7) {
     // (inside the first step's head)
@@ -1542,7 +1565,7 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     DDP_TRY(launch_linear(o.xtok, o.Cx, false, o.wx, o.Cx, weights->transform_b, nullptr, 0, 0, 0, o.xproj, 256, o.B * o.N,
                           256, o.Cx, 0, st, TAG_XPROJ));
   }
-  if (cfg->task == DDP_TASK_SEG) return sample_seg(cfg, weights, steps, p, o, d_x, d_noise, d_step_noise, d_out, st);
+  if (cfg->task == DDP_TASK_SEG) return sample_seg(cfg, weights, steps, p, o, d_x, d_noise, d_step_noise, key, d_out, st);
   if (cfg->task == DDP_TASK_DEPTH) return sample_depth(cfg, weights, steps, p, o, d_noise, d_out, st);
   return sample_bev(cfg, weights, steps, p, o, d_noise, d_out, st);
 }
@@ -2412,6 +2435,7 @@ struct FcnLoopLayout {
   // DDP_FLAG_STEP_RECORD: (K, M) uint8 record and the (B, N) disagreement map - the last two buffers of the workspace
   unsigned char* step_rec;
   float* step_map;
+  float* seed_noise;   // DDP_FLAG_SEEDED_NOISE: (B, r, 256, h, w) start noise, in front of the step-record buffers
   size_t bytes;
 };
 int fcn_loop_layout(const ddp_cfg* c, int num_convs, char* base, FcnLoopLayout* o) {
@@ -2446,6 +2470,7 @@ int fcn_loop_layout(const ddp_cfg* c, int num_convs, char* base, FcnLoopLayout* 
   o->conv_shifts = takef(size_t(c->timesteps) * (num_convs > 0 ? num_convs : 1) * 256);
   o->cls_stream = reinterpret_cast<unsigned char*>(take(size_t(8) * b3_stage_bytes()));
   o->cls_bias = takef(256);
+  o->seed_noise = takef((c->flags & DDP_FLAG_SEEDED_NOISE) ? M * 256 : 0);
   const bool rec = (c->flags & DDP_FLAG_STEP_RECORD) != 0;
   o->step_rec = rec ? reinterpret_cast<unsigned char*>(take(step_record_bytes(c))) : nullptr;
   o->step_map = rec ? takef(size_t(c->batch) * N) : nullptr;
@@ -2572,7 +2597,8 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
   DDP_TRY(check_ptr(d_x, "x"));
   DDP_TRY(check_ptr(d_noise, "noise"));
   DDP_TRY(check_ptr(d_out, "out"));
-  if (cfg->sampler == DDP_SAMPLER_DDPM) DDP_TRY(check_ptr(d_step_noise, "step_noise"));
+  const bool seeded = (cfg->flags & DDP_FLAG_SEEDED_NOISE) != 0;
+  if (cfg->sampler == DDP_SAMPLER_DDPM && !seeded) DDP_TRY(check_ptr(d_step_noise, "step_noise"));
   hipStream_t st = static_cast<hipStream_t>(stream);
   FcnLoopLayout o;
   DDP_TRY(fcn_loop_layout(cfg, num_convs, static_cast<char*>(d_workspace), &o));
@@ -2588,6 +2614,12 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
   DDP_TRY(launch_nchw_to_tok(d_x, o.xtok, B, Cx, N, st));
   DDP_TRY(launch_row_to_sb(o.xtok, Cx, o.in_sb, B * N, Cx, st));
   DDP_TRY(launch_b3_linear(o.in_sb, wpx, weights->transform_b, nullptr, 0, 0, 0, o.xproj, 256, B * N, 256, Cx, st, TAG_XPROJ));
+  const uint32_t* key = nullptr;
+  if (seeded) {
+    key = reinterpret_cast<const uint32_t*>(d_noise);
+    DDP_TRY(seeded_start_noise(key, o.seed_noise, B, size_t(r) * 256 * N, st));
+    d_noise = o.seed_noise;
+  }
   DDP_TRY(launch_nchw_to_tok(d_noise, o.mask, R, 256, N, st));
   for (int s = 0; s < K; ++s) {
     const ddp_step& sp = steps[s];
@@ -2600,7 +2632,12 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
     SegUpdateArgs a = seg_update_args(o.head.logits, o.head.ldl, Kc, o.lut, o.mask, o.prob, cfg->accumulation ? (s == 0 ? 1 : 2) : 0,
                                       cfg->sampler, sp, M);
     if (cfg->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
-      DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M * 256, o.snoise, R, 256, N, st));
+      if (key) {
+        prof_begin(TAG_GENERIC, st);
+        DDP_TRY(recorded(launch_noise_fill_tok(key, o.snoise, B, r, N, s, st), st));
+      } else {
+        DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M * 256, o.snoise, R, 256, N, st));
+      }
       a.step_noise = o.snoise;
     }
     a.x0_idx = o.step_rec ? o.step_rec + size_t(s) * M : nullptr;

@@ -424,4 +424,11 @@ struct StepDisagreementArgs {
 };
 int launch_step_disagreement(const StepDisagreementArgs& a, hipStream_t st);
 
+// ---- ddp_noise.hip (DDP_FLAG_SEEDED_NOISE) ---------------------------------------------------------
+// key: the 8 DEVICE words {seed_lo, seed_hi, image_base, stream_base, call, 0, 0, 0} (include/ddp_mi355x.h)
+// start noise of a call, NCHW: out (B, per_image), per_image = r * Cm * h * w
+int launch_noise_fill_nchw(const uint32_t* key, float* out, int B, size_t per_image, hipStream_t st);
+// noise added after step `step`, token-major rows of 256 channels: out (B * r * N, 256)
+int launch_noise_fill_tok(const uint32_t* key, float* out, int B, int r, int N, int step, hipStream_t st);
+
 }  // namespace ddp

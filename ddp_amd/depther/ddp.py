@@ -60,8 +60,11 @@ class DDP(nn.Module, _SamplerMixin):
 
     def __init__(self, bit_scale=1, bits=8, timesteps=1, randsteps=1, time_difference=1, learned_sinusoidal_dim=16,
                  sample_range=(0, 0.999), ddim=True, rule=None, min_depth=1e-3, max_depth=80, backbone=None,
-                 neck=None, decode_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+                 neck=None, decode_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, noise_seed=None):
+        """``noise_seed`` (not a reference kwarg): None - torch.randn per call; an integer - the start noise is generated on the
+        device (DDP_FLAG_SEEDED_NOISE) from (noise_seed, image index, call)."""
         super().__init__()
+        self.noise_seed = noise_seed
         if not ddim:
             raise NotImplementedError('the reference references ddpm_step but never defines it (depther/ddp.py:244)')
         if learned_sinusoidal_dim != 16:
@@ -95,13 +98,15 @@ class DDP(nn.Module, _SamplerMixin):
                 for a, b in schedule.get_sampling_timesteps(self.timesteps, self.time_difference, 0.0)]
 
     @torch.no_grad()
-    def sample(self, x, img_metas=None, noise=None, return_steps=False):
-        """``return_steps``: -> (out, record (K,b,r,h,w) float32 - every step's ``depth_pred`` (depther/ddp.py:239) -, disagreement
+    def sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0):
+        """With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
+        ``return_steps``: -> (out, record (K,b,r,h,w) float32 - every step's ``depth_pred`` (depther/ddp.py:239) -, disagreement
         (b,h,w) - their standard deviation per pixel)."""
         if not x.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')
         b, c, h, w = x.shape
-        if noise is None:
+        seeded = noise is None and self.noise_seed is not None
+        if noise is None and not seeded:
             noise = torch.randn((b, self.randsteps, 1, h, w), device=x.device)
 
         head = self.decode_head
@@ -123,12 +128,16 @@ class DDP(nn.Module, _SamplerMixin):
                              timesteps=self.timesteps, bit_scale=self.bit_scale, time_difference=self.time_difference,
                              min_depth=self.min_depth, max_depth=self.max_depth, depth_scale_up=su, depth_use_eps=ue,
                              head_min_depth=hmin, head_max_depth=hmax, depth_bins=bins, depth_norm=norm, device=x.device,
-                             record_steps=return_steps)
+                             record_steps=return_steps, seeded_noise=seeded)
         # keyed without the geometry: a new (b, h, w) re-uses the engine through set_geometry (no weight repacking)
         bins_key = None if bins is None else (getattr(head, 'bins_strategy', None), head.n_bins, norm)
         eng = self._get_engine(('depth', str(x.device), self.timesteps, self.randsteps, self.bit_scale, self.time_difference,
-                                self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key, bool(return_steps)), factory, geometry=(b, h, w))
-        out = eng.sample(x.contiguous().float(), noise.contiguous().float())
+                                self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key, bool(return_steps), seeded), factory,
+                               geometry=(b, h, w))
+        if seeded:
+            out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
+        else:
+            out = eng.sample(x.contiguous().float(), noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
@@ -156,9 +165,9 @@ class DDP(nn.Module, _SamplerMixin):
         if mode == 'slide':
             raise NotImplementedError("test_cfg.mode='slide' (the reference raises here as well: encoder_decoder.py:186-187)")
 
-    def _low_res(self, img, img_metas):
+    def _low_res(self, img, img_metas, image_base=0, call=0):
         """backbone + neck + the K-step loop: the (b,1,h/4,w/4) map every epilogue below starts from."""
-        return self.sample(self.extract_feat(img)[0], img_metas)
+        return self.sample(self.extract_feat(img)[0], img_metas, **self._seed_kw(image_base, call))
 
     def _post(self, maps, flips, size):
         from ..engine import depth_postprocess
@@ -168,15 +177,15 @@ class DDP(nn.Module, _SamplerMixin):
         hi = self.decode_head.max_depth if self.decode_head.max_depth is not None else float('inf')
         return depth_postprocess(maps, flips, size, lo, hi, self.align_corners)
 
-    def encode_decode(self, img, img_metas=None, rescale=False):
+    def encode_decode(self, img, img_metas=None, rescale=False, image_base=0, call=0):
         """depther/ddp.py:95-109: clamp to the head's depth range, resize to the network input when ``rescale`` - one fused
         kernel (``ddp_depth_postprocess``), no intermediate (b,1,h,w) clamp result."""
-        d = self._low_res(img, img_metas)
+        d = self._low_res(img, img_metas, **self._seed_kw(image_base, call))
         return self._post([d], [None], img.shape[2:] if rescale else d.shape[2:])
 
-    def whole_inference(self, img, img_meta, rescale):
+    def whole_inference(self, img, img_meta, rescale, image_base=0, call=0):
         """encoder_decoder.py:160-166."""
-        return self.encode_decode(img, img_meta, rescale)
+        return self.encode_decode(img, img_meta, rescale, **self._seed_kw(image_base, call))
 
     @staticmethod
     def _flip_of(img_meta):
@@ -186,22 +195,22 @@ class DDP(nn.Module, _SamplerMixin):
             return direction
         return None
 
-    def inference(self, img, img_meta, rescale):
+    def inference(self, img, img_meta, rescale, image_base=0, call=0):
         """encoder_decoder.py:168-196 (mode 'whole'): ``whole_inference`` with the test-time flip undone, the flip folded into
         the same kernel (it reads the mirrored source pixel)."""
         self._check_mode()
         if img_meta:
             ori_shape = img_meta[0]['ori_shape']
             assert all(m['ori_shape'] == ori_shape for m in img_meta)
-        d = self._low_res(img, img_meta)
+        d = self._low_res(img, img_meta, **self._seed_kw(image_base, call))
         return self._post([d], [self._flip_of(img_meta)], img.shape[2:] if rescale else d.shape[2:])
 
-    def simple_test(self, img, img_meta, rescale=True):
+    def simple_test(self, img, img_meta, rescale=True, image_base=0):
         """encoder_decoder.py:198-209: list (batch) of (1,H,W) float32 arrays.  ``img`` may hold b >= 1 images (independent
         noise per image; the reference's sampler is b = 1 only, depther/ddp.py:232)."""
-        return list(self.inference(img, img_meta, rescale).cpu().numpy())
+        return list(self.inference(img, img_meta, rescale, **self._seed_kw(image_base)).cpu().numpy())
 
-    def aug_test(self, imgs, img_metas, rescale=True):
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0):
         """encoder_decoder.py:210-229: mean over the augmentations (KITTI / NYU test pipelines: plain + horizontal flip,
         depth/configs/_base_/datasets/kitti.py:30-33).  Every augmentation runs the full sampling loop with its own noise; only the
         LOW-RESOLUTION maps are kept and ONE kernel does clamp -> resize -> flip-undo -> running sum -> / n per output pixel."""
@@ -212,11 +221,11 @@ class DDP(nn.Module, _SamplerMixin):
             # the reference adds the per-augmentation maps in place (:222-224): they must have one size
             raise RuntimeError(f'aug_test: augmentations of different input sizes {sorted(sizes)} cannot be averaged')
         maps, flips = [], []
-        for img, meta in zip(imgs, img_metas):
+        for a, (img, meta) in enumerate(zip(imgs, img_metas)):
             if meta:
                 ori_shape = meta[0]['ori_shape']
                 assert all(m['ori_shape'] == ori_shape for m in meta)
-            maps.append(self._low_res(img, meta))
+            maps.append(self._low_res(img, meta, **self._seed_kw(image_base, a)))      # (seeded noise: the augmentation index is the `call`)
             flips.append(self._flip_of(meta))
         return list(self._post(maps, flips, imgs[0].shape[2:]).cpu().numpy())
 

@@ -136,7 +136,70 @@ class PackedWeights:
         broadcast_weights(self.flat, src=src, force=force)
 
 
-class DDPEngine:
+def noise_key_words(seed, image_base=0, stream_base=0, call=0):
+    """The 8 uint32 words of the device key of DDP_FLAG_SEEDED_NOISE (include/ddp_mi355x.h):
+    {seed_lo, seed_hi, image_base, stream_base, call, 0, 0, 0}; ``seed`` is taken modulo 2^64, the others modulo 2^32."""
+    seed = int(seed)
+    m = 0xFFFFFFFF
+    return [seed & m, (seed >> 32) & m, int(image_base) & m, int(stream_base) & m, int(call) & m, 0, 0, 0]
+
+
+class _SeededNoise:
+    """What DDPEngine and FcnSamplerEngine share for ``seeded_noise=True``: the 8-word device key tensor, the argument checks of
+    ``sample()`` and the view of the start-noise buffer (``_workspace_bytes()`` is the engine's own workspace query)."""
+
+    def _init_key(self):
+        self.seeded = bool(self.cfg.flags & _lib.FLAG_SEEDED_NOISE)
+        self._key_words = None
+        self._key = torch.zeros(8, dtype=torch.int32, device=self.device) if self.seeded else None
+
+    def _write_key(self, seed=None, image_base=None, stream_base=None, call=None):
+        """update the given words of the key (the others keep their value) and copy it to the device on the current stream"""
+        import numpy as np
+        old = self._key_words
+        if old is None:
+            if seed is None:
+                raise _lib.DdpError('seeded_noise engine: sample() / capture() need seed=')
+            old = noise_key_words(0)
+        new = noise_key_words(seed if seed is not None else old[0] | (old[1] << 32),
+                              old[2] if image_base is None else image_base, old[3] if stream_base is None else stream_base,
+                              old[4] if call is None else call)
+        self._key_words = new
+        host = torch.from_numpy(np.array(new, dtype=np.uint32).view(np.int32))
+        with torch.cuda.device(self.device):
+            self._key.copy_(host)
+
+    def _noise_args(self, noise, step_noise, seed):
+        """-> True when the call is a seeded one; refuses the combinations that make no sense"""
+        if self.seeded:
+            if noise is not None or step_noise is not None:
+                raise _lib.DdpError('seeded_noise engine: the noise is generated on the device - pass seed=, not noise= / step_noise=')
+            return True
+        if seed is not None:
+            raise _lib.DdpError('seed= needs an engine built with seeded_noise=True')
+        if noise is None:
+            raise _lib.DdpError('sample() needs noise= (or an engine built with seeded_noise=True and seed=)')
+        return False
+
+    def last_noise(self):
+        """(B, r, Cm, h, w) float32 VIEW of the workspace buffer that holds the start noise the LAST seeded sample() call (or
+        graph replay) generated; valid until the next call."""
+        if not self.seeded:
+            raise _lib.DdpError('last_noise() needs an engine built with seeded_noise=True')
+        if not getattr(self, '_sampled', False):
+            raise _lib.DdpError('no noise yet: call sample() first')
+        c = self.cfg
+        cm = 1 if c.task == _lib.TASK_DEPTH else 256
+        n = c.batch * c.randsteps * cm * c.h * c.w
+        end = self._workspace_bytes()
+        if c.flags & _lib.FLAG_STEP_RECORD:
+            rec, smap = step_record_sizes(c)
+            end -= _round256(rec) + _round256(smap)
+        off = end - _round256(n * 4)
+        return self.workspace.view(torch.uint8)[off:off + n * 4].view(torch.float32).view(c.batch, c.randsteps, cm, c.h, c.w)
+
+
+class DDPEngine(_SeededNoise):
     """One configured problem: (task, sizes, schedule) + weights + workspace."""
 
     def __init__(self, state_dict, task='seg', *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150,
@@ -146,8 +209,10 @@ class DDPEngine:
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
-                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False):
-        """``record_steps`` (DDP_FLAG_STEP_RECORD): keep every step's prediction and compute the step-disagreement map on the
+                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False):
+        """``seeded_noise`` (DDP_FLAG_SEEDED_NOISE): start noise and ddpm step noise are generated on the device from a key -
+        ``sample(x, seed=...)``, ``last_noise()``; ``noise=`` / ``step_noise=`` are refused.
+        ``record_steps`` (DDP_FLAG_STEP_RECORD): keep every step's prediction and compute the step-disagreement map on the
         device - ``step_record()`` / ``step_disagreement()`` after ``sample()``.
         depth: ``min_depth`` / ``max_depth`` are the depther's range (x0 normalisation); ``head_min_depth`` / ``head_max_depth``
         the decode head's (eps of the regression head; default: the depther's).  ``depth_bins`` (n_bins) = the bin centres of a
@@ -228,6 +293,8 @@ class DDPEngine:
             cfg.flags |= _lib.FLAG_GATHER_GUESS_ZERO
         if record_steps:
             cfg.flags |= _lib.FLAG_STEP_RECORD
+        if seeded_noise:
+            cfg.flags |= _lib.FLAG_SEEDED_NOISE
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
         cfg.bit_scale, cfg.min_depth, cfg.max_depth, cfg.threshold = bit_scale, min_depth, max_depth, threshold
@@ -247,6 +314,12 @@ class DDPEngine:
         self._prepared = False
         self._sampled = False
         self.geometry_changes = 0
+        self._init_key()
+
+    def _workspace_bytes(self):
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.ddp_query_workspace(C.byref(self.cfg), C.byref(nbytes)), self.lib)
+        return nbytes.value
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -303,16 +376,24 @@ class DDPEngine:
                                             self.workspace.data_ptr(), self._stream()), self.lib)
         self._prepared = True
 
-    def sample(self, x, noise, step_noise=None, out=None):
-        """x (B,Cx,h,w); noise (B,r,Cm,h,w); step_noise (K,B,r,Cm,h,w) for ddpm -> output tensor."""
+    def sample(self, x, noise=None, step_noise=None, out=None, *, seed=None, image_base=0, call=0, stream_base=0, _key_ready=False):
+        """x (B,Cx,h,w); noise (B,r,Cm,h,w); step_noise (K,B,r,Cm,h,w) for ddpm -> output tensor.
+        ``seeded_noise=True`` engines: ``seed`` (64 bit), ``image_base`` (image b of the batch draws the noise of image
+        ``image_base + b``), ``call`` (separates the sampler calls that belong to one image) and ``stream_base`` make the key, which
+        is written to the engine's device key tensor on the current stream in front of the call."""
         c = self.cfg
         cm = 1 if self.task == 'depth' else 256
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         assert tuple(x.shape) == (c.batch, c.feat_channels, c.h, c.w), (tuple(x.shape), (c.batch, c.feat_channels, c.h, c.w))
-        assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
-        assert noise.numel() == c.batch * c.randsteps * cm * c.h * c.w
-        if self.sampler == 'ddpm':
-            assert step_noise is not None and step_noise.is_contiguous() and step_noise.numel() == c.timesteps * noise.numel()
+        if self._noise_args(noise, step_noise, seed):
+            if not _key_ready:
+                self._write_key(seed, image_base, stream_base, call)
+            noise = self._key
+        else:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+            assert noise.numel() == c.batch * c.randsteps * cm * c.h * c.w
+            if self.sampler == 'ddpm':
+                assert step_noise is not None and step_noise.is_contiguous() and step_noise.numel() == c.timesteps * noise.numel()
         if not self._prepared:
             self.prepare()
         if (c.flags & _lib.FLAG_FORCE_X0) and not getattr(self, '_x0_set', False):
@@ -347,8 +428,10 @@ class DDPEngine:
         the fraction of differing decisions, depth the standard deviation (include/ddp_mi355x.h).  A fresh tensor."""
         return step_disagreement_view(self.workspace, self._step_base(), self.cfg).clone()
 
-    def capture(self, x, noise, step_noise=None):
-        """One ``sample()`` call as a hipGraph (``torch.cuda.CUDAGraph`` is hipGraph on ROCm): ``ddp_sample`` neither
+    def capture(self, x, noise=None, step_noise=None, *, seed=None, image_base=0, call=0, stream_base=0):
+        """``seeded_noise=True`` engines: ``capture(x, seed=...)`` - the graph holds no noise tensor; the kernels read the key
+        from the engine's device key tensor, which ``SampleGraph.replay(seed=...)`` rewrites in front of the launch.
+        One ``sample()`` call as a hipGraph (``torch.cuda.CUDAGraph`` is hipGraph on ROCm): ``ddp_sample`` neither
         synchronises nor touches host memory after enqueue - its ~45 launches (kernels, device-to-device copies, memsets) go to
         the stream it is given, the schedule scalars travel as kernel arguments - so the whole K-step loop records under stream
         capture and replays with ONE host call.  What that buys is host time: one image per call (the reference's protocol, and
@@ -356,19 +439,27 @@ class DDPEngine:
         their data loaders.  Inputs are copied into the graph's own static buffers at replay; -> ``SampleGraph``."""
         if not self._prepared:
             self.prepare()
-        sx, sn = x.detach().clone(), noise.detach().clone()
-        ssn = step_noise.detach().clone() if step_noise is not None else None
+        kw = {}
+        if self._noise_args(noise, step_noise, seed):
+            self._write_key(seed, image_base, stream_base, call)      # (host -> device: in front of the capture, never inside it)
+            torch.cuda.synchronize(self.device)
+            sn = ssn = None
+            kw = dict(seed=seed, _key_ready=True)
+        else:
+            sn = noise.detach().clone()
+            ssn = step_noise.detach().clone() if step_noise is not None else None
+        sx = x.detach().clone()
         out = torch.empty(self.out_shape(), dtype=torch.float32, device=self.device)
         cur = torch.cuda.current_stream(self.device)
         side = torch.cuda.Stream(self.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):              # warm-up on the capture stream: one-time attribute calls happen here
-            self.sample(sx, sn, ssn, out=out)
+            self.sample(sx, sn, ssn, out=out, **kw)
         cur.wait_stream(side)
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=side):
-            self.sample(sx, sn, ssn, out=out)
+            self.sample(sx, sn, ssn, out=out, **kw)
         return SampleGraph(self, g, sx, sn, ssn, out)
 
     def _x0_view(self, which):
@@ -450,8 +541,15 @@ class SampleGraph:
         self.workspace = engine.workspace
         self.workspace_ptr = engine.workspace.data_ptr()
 
-    def replay(self, x=None, noise=None, step_noise=None):
+    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None):
+        """seeded engines: ``seed`` / ``image_base`` / ``call`` given here replace those words of the engine's device key (stream-
+        ordered, in front of the launch); none given: the graph repeats the last key."""
         eng = self.engine
+        if eng.seeded:
+            if noise is not None or step_noise is not None:
+                raise _lib.DdpError('seeded_noise engine: replay(seed=...), not noise= / step_noise=')
+        elif seed is not None or image_base is not None or call is not None:
+            raise _lib.DdpError('seed= / image_base= / call= need an engine built with seeded_noise=True')
         if eng.geometry() != self.geometry:
             raise _lib.DdpError(f'graph captured for geometry {self.geometry}, engine is now at {eng.geometry()}')
         if eng.workspace.data_ptr() != self.workspace_ptr:
@@ -465,17 +563,19 @@ class SampleGraph:
             self.noise.copy_(noise.reshape(self.noise.shape), non_blocking=True)
         if step_noise is not None:
             self.step_noise.copy_(step_noise.reshape(self.step_noise.shape), non_blocking=True)
+        if seed is not None or image_base is not None or call is not None:
+            eng._write_key(seed, image_base, None, call)
         self.graph.replay()
         return self.out
 
 
-class FcnSamplerEngine:
+class FcnSamplerEngine(_SeededNoise):
     """The K-step sampler with ``FCNHeadWithTime`` as decode head (``ddp_sample_fcn``): same inputs,
     schedule and outputs as ``DDPEngine`` for task 'seg'.  ``head`` is a ``ddp_amd.FCNHeadWithTime`` (parameter holder)."""
 
     def __init__(self, state_dict, head, *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150, bit_scale=0.01,
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
-                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False):
+                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False):
         self.lib = _lib.load(lib_path)
         if not torch.cuda.is_available():
             raise _lib.DdpError('no HIP device visible: ddp_amd has no CPU path')
@@ -493,7 +593,8 @@ class FcnSamplerEngine:
         cfg.num_classes, cfg.feat_channels = num_classes, 256
         cfg.h = cfg.head_h = h
         cfg.w = cfg.head_w = w
-        cfg.gemm_mode, cfg.flags = _lib.GEMM_BF16X3, (_lib.FLAG_STEP_RECORD if record_steps else 0)
+        cfg.gemm_mode = _lib.GEMM_BF16X3
+        cfg.flags = (_lib.FLAG_STEP_RECORD if record_steps else 0) | (_lib.FLAG_SEEDED_NOISE if seeded_noise else 0)
         cfg.accumulation, cfg.bit_scale = int(bool(accumulation)), bit_scale
         self.cfg, self.sampler = cfg, sampler
         recs = schedule.step_records('seg', timesteps, time_difference, sample_range0, noise_schedule, sampler)
@@ -507,6 +608,10 @@ class FcnSamplerEngine:
         self.workspace = torch.empty(nbytes.value // 4 + 64, dtype=torch.float32, device=self.device)
         self._prepared = False
         self._sampled = False
+        self._init_key()
+
+    def _workspace_bytes(self):
+        return self._ws_bytes
 
     def prepare(self):
         """``ddp_prepare_fcn``: everything that depends on weights and schedule only (time embeddings, x0 table, concat-conv
@@ -521,14 +626,19 @@ class FcnSamplerEngine:
         c.flags |= _lib.FLAG_FCN_PREPARED
         self._prepared = True
 
-    def sample(self, x, noise, step_noise=None, out=None):
+    def sample(self, x, noise=None, step_noise=None, out=None, *, seed=None, image_base=0, call=0, stream_base=0):
+        """as ``DDPEngine.sample`` (seeded engines: ``seed=`` ... in place of ``noise=`` / ``step_noise=``)"""
         c = self.cfg
         if not self._prepared:
             self.prepare()
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (c.batch, 256, c.h, c.w)
-        assert noise.is_cuda and noise.is_contiguous() and noise.numel() == c.batch * c.randsteps * 256 * c.h * c.w
-        if self.sampler == 'ddpm':
-            assert step_noise is not None and step_noise.is_contiguous() and step_noise.numel() == c.timesteps * noise.numel()
+        if self._noise_args(noise, step_noise, seed):
+            self._write_key(seed, image_base, stream_base, call)
+            noise = self._key
+        else:
+            assert noise.is_cuda and noise.is_contiguous() and noise.numel() == c.batch * c.randsteps * 256 * c.h * c.w
+            if self.sampler == 'ddpm':
+                assert step_noise is not None and step_noise.is_contiguous() and step_noise.numel() == c.timesteps * noise.numel()
         if out is None:
             out = torch.empty((c.batch, c.num_classes, c.h, c.w), dtype=torch.float32, device=self.device)
         if x.device != self.device or noise.device != self.device or out.device != self.device:

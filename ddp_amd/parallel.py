@@ -51,9 +51,11 @@ def gather_outputs(local_out, total, force=False):
     return torch.cat([b[:n] for b, n in zip(bufs, sizes)], dim=0)
 
 
-def sample_sharded(make_engine, x, noise, total=None):
+def sample_sharded(make_engine, x, noise=None, total=None, seed=None, call=0):
     """Run the loop on this rank's shard of a global batch.  ``x`` / ``noise`` hold the GLOBAL batch
     (e.g. produced identically on every rank); ``make_engine(b_local)`` builds the rank-local engine.
+    A ``seeded_noise=True`` engine takes ``seed=`` in place of ``noise``: the shard [a, b) runs with ``image_base = a``, so
+    every image draws the noise it would draw in the whole-batch call and N ranks compute what one rank computes.
     Returns (local_out, (start, stop))."""
     rank = dist.get_rank() if is_distributed() else 0
     world = dist.get_world_size() if is_distributed() else 1
@@ -62,4 +64,8 @@ def sample_sharded(make_engine, x, noise, total=None):
     if b == a:
         return None, (a, b)
     eng = make_engine(b - a)
+    if getattr(eng, 'seeded', False):
+        if noise is not None or seed is None:
+            raise ValueError('sample_sharded: a seeded_noise engine takes seed=, not noise')
+        return eng.sample(x[a:b].contiguous(), seed=seed, image_base=a, call=call), (a, b)
     return eng.sample(x[a:b].contiguous(), noise[a:b].contiguous()), (a, b)

@@ -65,6 +65,13 @@ class _SamplerMixin:
             cache[key] = hit
         return hit[1]
 
+    def _seed_kw(self, image_base=0, call=0):
+        """the keyword arguments that carry the noise key down the call chain - none without ``noise_seed``, so that an unseeded
+        model calls its (possibly replaced) members exactly as before"""
+        if getattr(self, 'noise_seed', None) is None:
+            return {}
+        return dict(image_base=image_base, call=call)
+
     def _get_engine(self, key, factory, geometry=None):
         cache = self.__dict__.setdefault('_engine_cache', {})
         ver = self._weights_version()
@@ -89,8 +96,12 @@ class DDP(nn.Module, _SamplerMixin):
     def __init__(self, bit_scale=0.1, timesteps=1, randsteps=1, time_difference=1, learned_sinusoidal_dim=16,
                  sample_range=(0, 0.999), noise_schedule='cosine', diffusion='ddim', accumulation=False,
                  backbone=None, neck=None, decode_head=None, auxiliary_head=None, train_cfg=None, test_cfg=None,
-                 pretrained=None, init_cfg=None):
+                 pretrained=None, init_cfg=None, noise_seed=None):
+        """``noise_seed`` (not a reference kwarg): None - the noise is drawn with torch.randn per call, as the reference does; an
+        integer - start and step noise are generated on the device (DDP_FLAG_SEEDED_NOISE) from (noise_seed, image index, call),
+        so an image's result does not depend on the batch it was in, on the rank it ran on or on the calls before it."""
         super().__init__()
+        self.noise_seed = noise_seed
         if noise_schedule not in schedule.NOISE_SCHEDULES:
             raise ValueError(f'invalid noise schedule {noise_schedule}')            # ddp.py:90
         if learned_sinusoidal_dim != 16:
@@ -135,7 +146,7 @@ class DDP(nn.Module, _SamplerMixin):
         return times
 
     def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample',
-                    record_steps=False):
+                    record_steps=False, seeded=False):
         from ..decode_heads.fcn_head_with_time import FCNHeadWithTime
         K = self.timesteps if timesteps is None else timesteps
         r = self.randsteps if randsteps is None else randsteps
@@ -143,9 +154,9 @@ class DDP(nn.Module, _SamplerMixin):
         common = dict(batch=b, randsteps=r, timesteps=K, num_classes=self.num_classes, bit_scale=self.bit_scale,
                       time_difference=self.time_difference, sample_range0=self.sample_range[0],
                       noise_schedule=self.noise_schedule, sampler=sampler, accumulation=acc, device=device,
-                      record_steps=record_steps)
+                      record_steps=record_steps, seeded_noise=seeded)
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule, bool(record_steps))
+               self.noise_schedule, bool(record_steps), bool(seeded))
         if isinstance(self.decode_head, FCNHeadWithTime):
             # any registered head goes through _decode_head_forward_test in the reference (ddp.py:192-196); here the loop
             # around FCNHeadWithTime is its own C entry (ddp_sample_fcn), one engine per geometry
@@ -171,13 +182,18 @@ class DDP(nn.Module, _SamplerMixin):
             raise RuntimeError(f'expected {self.decode_head.in_channels[0]} feature channels, got {x.shape[1]}')
 
     @torch.no_grad()
-    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False):
+    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0):
         """x (b,256,h,w) -> (b,K,h,w).  ``noise`` (b,r,256,h,w) may be injected (parity tests);
         by default it is drawn with torch.randn like the reference (ddp.py:220).
+        With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
         ``return_steps``: -> (out, record (K,b,r,h,w) uint8 - every step's argmax class, the reference's ``outs`` as decisions -,
         disagreement (b,h,w) - the fraction of them that differ from the output's argmax)."""
         self._check_feature(x)
         b, c, h, w = x.shape
+        if noise is None and self.noise_seed is not None:
+            eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True)
+            out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
+            return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
             noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
         eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps)
@@ -185,9 +201,13 @@ class DDP(nn.Module, _SamplerMixin):
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     @torch.no_grad()
-    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False):
+    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0):
         self._check_feature(x)
         b, c, h, w = x.shape
+        if noise is None and step_noise is None and self.noise_seed is not None:
+            eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True)
+            out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
+            return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
             noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
         if step_noise is None:
@@ -199,20 +219,20 @@ class DDP(nn.Module, _SamplerMixin):
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)
 
-    def encode_decode(self, img, img_metas=None):
+    def encode_decode(self, img, img_metas=None, image_base=0, call=0):
         """ddp.py:114-129."""
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_metas)
+            out = self.ddim_sample(x, img_metas, **self._seed_kw(image_base, call))
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_metas)
+            out = self.ddpm_sample(x, img_metas, **self._seed_kw(image_base, call))
         else:
             raise NotImplementedError
         return F.interpolate(out, size=img.shape[2:], mode='bilinear', align_corners=self.align_corners)
 
-    def whole_inference(self, img, img_meta=None, rescale=False):
+    def whole_inference(self, img, img_meta=None, rescale=False, image_base=0, call=0):
         """encoder_decoder.py:229-248: crop to img_shape and resize to ori_shape when rescale."""
-        seg_logit = self.encode_decode(img, img_meta)
+        seg_logit = self.encode_decode(img, img_meta, **self._seed_kw(image_base, call))
         if rescale and img_meta:
             rs = img_meta[0]['img_shape'][:2]
             seg_logit = seg_logit[:, :, :rs[0], :rs[1]]
@@ -229,22 +249,25 @@ class DDP(nn.Module, _SamplerMixin):
             raise AssertionError(f"test_cfg.mode must be 'slide' or 'whole', got {mode!r}")
         return mode or 'whole'
 
-    def _sample(self, x, img_meta=None):
+    def _sample(self, x, img_meta=None, image_base=0, call=0):
         if self.diffusion == 'ddim':
-            return self.ddim_sample(x, img_meta)
+            return self.ddim_sample(x, img_meta, **self._seed_kw(image_base, call))
         if self.diffusion == 'ddpm':
-            return self.ddpm_sample(x, img_meta)
+            return self.ddpm_sample(x, img_meta, **self._seed_kw(image_base, call))
         raise NotImplementedError
 
     SLIDE_WINDOWS_PER_CALL = 16          # windows x images sampled in one call of the loop (memory bound of the workspace)
 
-    def _slide(self, img, img_meta, rescale, want, flip=None):
+    def _slide(self, img, img_meta, rescale, want, flip=None, image_base=0, call=0):
         """Sliding-window inference (encoder_decoder.py:180-227).  The reference runs ``encode_decode`` - backbone, neck and a
         K-step loop - window by window; the windows all have one size, so here they go through backbone + loop as ONE batch
         (chunks of SLIDE_WINDOWS_PER_CALL maps, independent noise per window as in the reference) and only their LOW-RESOLUTION
         scores are kept.  ``ddp_seg_slide_postprocess`` then does, per output pixel, what the reference does with image-size
         tensors: resize per window, ``preds += pad(...)`` in window order, ``/ count_mat``, crop to img_shape, resize to
-        ori_shape, [softmax, flip-undo, argmax]."""
+        ori_shape, [softmax, flip-undo, argmax].
+        With ``self.noise_seed`` set, every window-chunk is a sampler call of its own ``call`` value (``call`` + the chunk's index)
+        and its maps - windows x images, window-major - draw the noise of images ``image_base``, ``image_base`` + 1, ...: no two
+        windows of a call share noise, and no two chunks do."""
         from ..engine import seg_slide_postprocess, slide_windows
         cfg = self.test_cfg
         get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
@@ -256,7 +279,7 @@ class DDP(nn.Module, _SamplerMixin):
         for i in range(0, len(crops), per):
             chunk = crops[i:i + per]
             x = self.extract_feat(torch.cat(chunk, dim=0))[0]
-            lows.append(self._sample(x, img_meta).reshape(len(chunk), b, self.num_classes, x.shape[2], x.shape[3]))
+            lows.append(self._sample(x, img_meta, **self._seed_kw(image_base, call + i // per)).reshape(len(chunk), b, self.num_classes, x.shape[2], x.shape[3]))
         scores = torch.cat(lows, dim=0)
         keep = out = None
         if rescale and img_meta:
@@ -264,11 +287,11 @@ class DDP(nn.Module, _SamplerMixin):
             out = tuple(img_meta[0]['ori_shape'][:2])
         return seg_slide_postprocess(scores, ys, xs, (ch, cw), img.shape[2:], keep, out, self.align_corners, flip, want)
 
-    def slide_inference(self, img, img_meta, rescale):
+    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0):
         """encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
-        return self._slide(img, img_meta, rescale, 'scores')
+        return self._slide(img, img_meta, rescale, 'scores', **self._seed_kw(image_base, call))
 
-    def inference(self, img, img_meta, rescale):
+    def inference(self, img, img_meta, rescale, image_base=0, call=0):
         """encoder_decoder.py:251-287, mode 'whole' (what every DDP config sets): class probabilities at ``ori_shape`` with
         the test-time flip undone - the building block of ``aug_test``.  ``simple_test`` does not go through here: its
         fused epilogue never materialises these (B,K,H,W) tensors."""
@@ -281,16 +304,20 @@ class DDP(nn.Module, _SamplerMixin):
             if img_meta and img_meta[0].get('flip', False):
                 fl = img_meta[0].get('flip_direction', 'horizontal')
                 assert fl in ('horizontal', 'vertical')
-            return self._slide(img, img_meta, rescale, 'prob', fl)
-        output = F.softmax(self.whole_inference(img, img_meta, rescale), dim=1)
+            return self._slide(img, img_meta, rescale, 'prob', fl, **self._seed_kw(image_base, call))
+        output = F.softmax(self.whole_inference(img, img_meta, rescale, **self._seed_kw(image_base, call)), dim=1)
         if img_meta and img_meta[0].get('flip', False):
             direction = img_meta[0].get('flip_direction', 'horizontal')
             assert direction in ('horizontal', 'vertical')
             output = output.flip(dims=(3,) if direction == 'horizontal' else (2,))
         return output
 
-    def aug_test(self, imgs, img_metas, rescale=True):
-        """encoder_decoder.py:306-331: mean of the per-augmentation probabilities (multi-scale / flip), then argmax.
+    AUG_CALL_STRIDE = 1 << 16            # seeded noise: augmentation a owns the call values [a * stride, (a + 1) * stride)
+
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0):
+        """With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
+        index), so no two augmentations of an image share noise.
+        encoder_decoder.py:306-331: mean of the per-augmentation probabilities (multi-scale / flip), then argmax.
         Every augmentation runs the full sampling loop with its own noise, as in the reference; only the LOW-RESOLUTION
         scores of each are kept, and one fused epilogue (``ddp_seg_aug_postprocess``) does resize -> crop -> resize ->
         softmax -> flip-undo for all of them, the mean and the argmax per output pixel: the (1,K,H,W) tensors ``inference``
@@ -302,20 +329,20 @@ class DDP(nn.Module, _SamplerMixin):
         if self._mode() == 'slide':
             # no shipped config combines sliding windows with test-time augmentation: the reference's own composition
             # (running mean of ``inference``, encoder_decoder.py:306-331) over the fused per-augmentation slide epilogue
-            prob = self.inference(imgs[0], img_metas[0], rescale)
-            for img, meta in zip(imgs[1:], img_metas[1:]):
-                prob += self.inference(img, meta, rescale)
+            prob = self.inference(imgs[0], img_metas[0], rescale, **self._seed_kw(image_base, 0))
+            for a, (img, meta) in enumerate(zip(imgs[1:], img_metas[1:]), 1):
+                prob += self.inference(img, meta, rescale, **self._seed_kw(image_base, a * self.AUG_CALL_STRIDE))
             prob /= len(imgs)
             return list(prob.argmax(dim=1).cpu().numpy().astype('int64'))
         ori_shape = tuple(img_metas[0][0]['ori_shape'][:2])
         scores, metas = [], []
-        for img, meta in zip(imgs, img_metas):
+        for a, (img, meta) in enumerate(zip(imgs, img_metas)):
             assert all(tuple(m['ori_shape'][:2]) == ori_shape for m in meta)
             x = self.extract_feat(img)[0]
             if self.diffusion == 'ddim':
-                scores.append(self.ddim_sample(x, meta))
+                scores.append(self.ddim_sample(x, meta, **self._seed_kw(image_base, a)))
             elif self.diffusion == 'ddpm':
-                scores.append(self.ddpm_sample(x, meta))
+                scores.append(self.ddpm_sample(x, meta, **self._seed_kw(image_base, a)))
             else:
                 raise NotImplementedError
             metas.append(dict(img_size=tuple(img.shape[2:]), crop_size=tuple(meta[0]['img_shape'][:2]),
@@ -334,7 +361,7 @@ class DDP(nn.Module, _SamplerMixin):
                 flip = meta.get('flip_direction', 'horizontal')
         return crop, out_size, flip
 
-    def simple_test(self, img, img_meta=None, rescale=True):
+    def simple_test(self, img, img_meta=None, rescale=True, image_base=0):
         """encoder_decoder.py:250-304 (mode='whole'), post-loop epilogue fused into one kernel:
         the (1,K,H,W) resized scores / probabilities of the reference are never materialised.  ``img`` may hold
         b >= 1 images (§8 f4): the loop runs once on the whole batch with independent noise per image, and every
@@ -348,12 +375,12 @@ class DDP(nn.Module, _SamplerMixin):
             # softmax is monotone, so the two agree except where fp32 rounding of exp / the division makes two probabilities EQUAL
             # that came from different scores - the reference then returns the lower class index, this path the class with the
             # larger score.  test_slide_epilogue_golden bounds it: identical wherever the reference's top-2 margin exceeds 1e-5.)
-            return list(self._slide(img, img_meta, rescale, 'seg', fl).cpu().numpy().astype('int64'))
+            return list(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base)).cpu().numpy().astype('int64'))
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_meta)
+            out = self.ddim_sample(x, img_meta, **self._seed_kw(image_base))
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_meta)
+            out = self.ddpm_sample(x, img_meta, **self._seed_kw(image_base))
         else:
             raise NotImplementedError
         b = out.shape[0]
@@ -370,7 +397,7 @@ class DDP(nn.Module, _SamplerMixin):
             res.append(seg[0].cpu().numpy().astype('int64'))
         return res
 
-    def forward(self, img, img_metas=None, return_loss=False, rescale=True, **kwargs):
+    def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, **kwargs):
         """base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
         augmentation lists the test pipeline produces."""
         if return_loss:
@@ -379,11 +406,11 @@ class DDP(nn.Module, _SamplerMixin):
             if len(img) != 1:
                 if img_metas is None or len(img_metas) != len(img):
                     raise ValueError(f'num of augmentations ({len(img)}) != num of image meta ({0 if img_metas is None else len(img_metas)})')
-                return self.aug_test(list(img), list(img_metas), rescale)
+                return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}))
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
-        return self.simple_test(img, img_metas, rescale)
+        return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}))
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
@@ -398,7 +425,7 @@ class SelfAlignedDDP(DDP):
     (:150-164) - is exposed as ``self_aligned_predict``."""
 
     @torch.no_grad()
-    def self_aligned_predict(self, x, noise=None, return_logits=False):
+    def self_aligned_predict(self, x, noise=None, return_logits=False, image_base=0, call=0):
         """self_aligned_ddp.py:150-164: ONE decoder pass at t = 1 on pure noise, then the x0 projection:
             feat = transform(cat[x, noise]); logits = decode_head(feat, time_mlp(log_snr(1)))
             preds = (sigmoid(embedding_table(argmax(logits))) * 2 - 1) * bit_scale
@@ -410,12 +437,16 @@ class SelfAlignedDDP(DDP):
         from .. import _lib
         self._check_feature(x)
         b, c, h, w = x.shape
-        if noise is None:
-            noise = torch.randn_like(x)
-
         # the head dispatch of _engine_for (the reference's pre-pass goes through the generic _decode_head_forward_test)
-        eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned')
-        logits = eng.sample(x.contiguous().float(), noise.reshape(b, 1, c, h, w).contiguous().float())
+        if noise is None and self.noise_seed is not None:
+            eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned',
+                                   seeded=True)
+            logits = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
+        else:
+            if noise is None:
+                noise = torch.randn_like(x)
+            eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned')
+            logits = eng.sample(x.contiguous().float(), noise.reshape(b, 1, c, h, w).contiguous().float())
         preds = torch.empty((b, 256, h, w), dtype=torch.float32, device=x.device)
         emb = self.embedding_table.weight.detach().float().contiguous()
         with torch.cuda.device(x.device):

@@ -90,6 +90,10 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                       step's prediction (the reference's `outs`, segmentors/ddp.py:241-245) and compute the step-
                                       disagreement map on the device - see ddp_x0_trace.  Refused together with DDP_FLAG_FORCE_X0; any
                                       other flag may be combined.  Clear: launches, workspace sizes and outputs are unchanged */,
+       DDP_FLAG_SEEDED_NOISE = 2048 /* model surface, all three tasks, both samplers, both engines, ddp_sample and ddp_sample_fcn: the start
+                                       noise and the ddpm step noise are generated on the device from a key instead of being read from
+                                       the caller's tensors - see "Seeded noise" below.  Any other flag may be combined.  Clear: launches,
+                                       workspace sizes and outputs are unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
@@ -217,6 +221,7 @@ int ddp_prepare_geometry(const ddp_cfg* cfg, void* d_workspace, void* stream);
  *   d_x          (B, Cx, h, w)           frozen neck feature, NCHW
  *   d_noise      (B, r, Cm, h, w)        start noise (the reference draws torch.randn in-method)
  *   d_step_noise (K, B, r, Cm, h, w)     per-step noise, ddpm only, else NULL
+ *   (DDP_FLAG_SEEDED_NOISE: d_noise is the 8-word device key and d_step_noise is ignored - "Seeded noise" below)
  *   d_out        seg: (B, K_cls, h, w); depth: (B, 1, h, w); bev: (B, K_cls, head_h, head_w) */
 int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* steps,
                const float* d_x, const float* d_noise, const float* d_step_noise, float* d_out,
@@ -259,6 +264,34 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
  * Extra launches with the flag set: one k_step_disagreement per call; bev + one k_bev_record per step; depth + one head-only
  * k_depth_update per step whose update runs fused inside the next step's head (the fused step boundary); seg none. */
 int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_idx);
+
+/* Seeded noise (DDP_FLAG_SEEDED_NOISE, any task; csrc/ddp_noise.hip).  With the flag set, ddp_sample / ddp_sample_fcn read
+ *   d_noise       a DEVICE array of 8 uint32 words {seed_lo, seed_hi, image_base, stream_base, call, 0, 0, 0}, 16-byte aligned.  The
+ *                 kernels read the words from device memory when they run, so a captured graph picks up a new key without being
+ *                 captured again.  Words 5..7 are reserved: the kernels ignore them, the caller writes zeros
+ *   d_step_noise  ignored, may be NULL
+ * and generate every value with Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments
+ * 0x9E3779B9 / 0xBB67AE85):
+ *   key     = (seed_lo, seed_hi)
+ *   counter = (e >> 2, image_base + b, stream, call), e = the flat index of the element inside image b's (r, Cm, h, w) block;
+ *             the element's value is output lane e & 3 of that counter
+ *   stream  = stream_base for the start noise, stream_base + 1 + s for the noise added after step s (ddpm, ddpm_add_noise != 0;
+ *             other steps generate nothing)
+ *   normals = Box-Muller on u = ((x >> 9) + 0.5) * 2^-23 (exact in fp32, inside (0, 1)): rad = sqrtf(-2 logf(u0)),
+ *             lanes (0, 1) = rad * (cospi(2 u1), sinpi(2 u1)) from words (0, 1), lanes (2, 3) the same from words (2, 3)
+ * A value is thus a function of (seed, image, stream, call, e) only - not of batch, of the position in the batch, of the layout
+ * it is written in or of the grid that wrote it: image i of a batch whose image_base is a equals a one-image call with
+ * image_base = a + i.  The start noise is written NCHW by k_noise_fill_nchw into a workspace buffer that every consumer reads in
+ * place of the caller's tensor; a ddpm step's noise is written token-major by k_noise_fill_tok straight into the buffer the update
+ * kernel reads (no (K, B, r, Cm, h, w) tensor, no per-step transpose).  Size and place, as formulas of the cfg:
+ *   noise_bytes = batch * randsteps * Cm * h * w * 4      (Cm = 1 for depth, else 256)
+ * carved IMMEDIATELY IN FRONT of the step-record buffers - at the END of the workspace when DDP_FLAG_STEP_RECORD is clear -, rounded
+ * up to 256 bytes: ddp_query_workspace grows by round256(noise_bytes), the buffer starts at
+ *   ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)] - round256(noise_bytes),
+ * every other offset and ddp_query_const_workspace are those of the cfg without the flag; ddp_sample_fcn_workspace follows the same
+ * rule.  The buffer holds the (B, r, Cm, h, w) start noise of the LAST call until the next one.
+ * Extra launches with the flag set: one k_noise_fill_nchw per call; per noise-adding ddpm step one k_noise_fill_tok in place of the
+ * NCHW -> token-major transpose. */
 
 /* ---- finer-grained entry points (unit tests, and the decode_head plugin surface) ------------- */
 
