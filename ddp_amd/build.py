@@ -48,7 +48,82 @@ def needs_build():
     return not os.path.exists(LIB_PATH) or built_hash() != source_hash()
 
 
+# test-only probe of the elementwise __device__ functions (tests/probe/, tests/test_device_math_gpu.py): its own library and its
+# own stamp, outside source_hash(); ddp_amd never loads it and libddp_mi355x.so does not contain it
+PROBE_SRC = os.path.join(HERE, '..', 'tests', 'probe', 'device_math_probe.hip')
+PROBE_LIB_PATH = os.path.join(LIB_DIR, 'libddp_probe.so')
+PROBE_STAMP_PATH = os.path.join(LIB_DIR, '.probe_sha')
+
+
+def probe_hash():
+    """sha256 (16 hex digits) over the probe source + the csrc headers it includes"""
+    import hashlib
+    h = hashlib.sha256()
+    for name, path in [('device_math_probe.hip', PROBE_SRC)] + [(s, os.path.join(CSRC, s)) for s in sorted(HEADERS)]:
+        with open(path, 'rb') as f:
+            h.update(name.encode() + b'\0' + f.read())
+    return h.hexdigest()[:16]
+
+
+def probe_built_hash():
+    try:
+        with open(PROBE_STAMP_PATH) as f:
+            return f.read().strip()
+    except OSError:
+        return ''
+
+
+def probe_needs_build():
+    return not os.path.exists(PROBE_LIB_PATH) or probe_built_hash() != probe_hash()
+
+
+def probe_cmd(out_path):
+    """the one hipcc line of the probe (no object file in between): the product FLAGS + the csrc include path"""
+    return [_hipcc()] + FLAGS + ['-I', CSRC, '-x', 'hip', '-shared', os.path.normpath(PROBE_SRC), '-o', out_path]
+
+
+def _start_probe(force, verbose):
+    """start the probe's hipcc (or nothing, when it is current); -> finish(), which waits for it and writes the stamp"""
+    if not force and not probe_needs_build():
+        return lambda: PROBE_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    sha = probe_hash()                   # hashed BEFORE compiling, as in build()
+    if os.path.exists(PROBE_STAMP_PATH):
+        os.remove(PROBE_STAMP_PATH)
+    cmd = probe_cmd(PROBE_LIB_PATH)
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    proc = subprocess.Popen(cmd)
+
+    def finish():
+        if proc.wait() != 0:
+            raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+        with open(PROBE_STAMP_PATH, 'w') as f:
+            f.write(sha + '\n')
+        return PROBE_LIB_PATH
+    return finish
+
+
+def build_probe(force=False, verbose=True):
+    return _start_probe(force, verbose)()
+
+
 def build(force=False, verbose=True):
+    # the probe compiles beside the product's objects; its compile-time checks of the schedule tables make build() fail
+    finish_probe = _start_probe(force, verbose)
+    try:
+        path = _build_product(force, verbose)
+    except BaseException:
+        try:
+            finish_probe()
+        except RuntimeError:
+            pass
+        raise
+    finish_probe()
+    return path
+
+
+def _build_product(force, verbose):
     if not force and not needs_build():
         return LIB_PATH
     os.makedirs(LIB_DIR, exist_ok=True)

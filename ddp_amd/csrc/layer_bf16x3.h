@@ -183,7 +183,14 @@ __device__ __forceinline__ float bf_elem(const u32x4& v, int u) {
 // wave per SIMD ~5 instructions hide behind an MFMA, the 6th costs ~4 cycles, the 8th ~25
 // (scripts/ubench/mfma_fill.hip).  Constants are folded so that exp2 and the final sign need no extra instruction:
 // z' = |x| sqrt(log2 e / 2);  t = 1 / (1 + p z), p z = (p / sqrt(log2 e)) z';  exp(-z^2) = exp2(-z'^2);
-// gelu = hf + |hf| erf(|x|/sqrt 2), hf = x/2.
+// gelu = hf + |hf| erf(|x|/sqrt 2), hf = x/2.  Same accuracy as gelu_fast (gemm_f32.h; both restatements below and the GELU_SCHED /
+// SPLIT_HAND_LO tables are probed one by one by tests/probe/device_math_probe.hip).
+// The two folded constants, named once (double, so that the check below is exact to 1e-15): z' = GELU_ZP |x|, p z = GELU_PZ z'.
+constexpr double GELU_ZP = 0.84932180028801904272;   // sqrt(log2 e / 2)
+constexpr double GELU_PZ = 0.27273748087922250;      // 0.3275911 / sqrt(log2 e)
+constexpr double gelu_cabs(double v) { return v < 0 ? -v : v; }
+static_assert(gelu_cabs(GELU_PZ * 1.2011224087864498 - 0.3275911) < 1e-9, "GELU_PZ is not 0.3275911 / sqrt(log2 e)");
+static_assert(gelu_cabs(2 * GELU_ZP * GELU_ZP - 1.4426950408889634) < 1e-15, "GELU_ZP is not sqrt(log2 e / 2)");
 struct GeluState {
   float x, a, b, c;      // after op 17 the three bf16 pieces live in (b, c, a): gelu_ph / gelu_pm / gelu_pl
 };
@@ -191,8 +198,8 @@ constexpr int GELU_OPS = 18;
 template <int OP>
 __device__ __forceinline__ void gelu_op(GeluState& g, float v) {
   if (OP == 0) g.x = v;
-  else if (OP == 1) g.a = fabsf(g.x) * 0.84932180028801904272f;                  // z' = |x| sqrt(log2(e)/2)
-  else if (OP == 2) g.b = fmaf(0.27274550239055780f, g.a, 1.0f);                 // 1 + 0.3275911 z, z = z' / sqrt(log2 e)
+  else if (OP == 1) g.a = fabsf(g.x) * float(GELU_ZP);                           // z' = |x| sqrt(log2(e)/2)
+  else if (OP == 2) g.b = fmaf(float(GELU_PZ), g.a, 1.0f);                       // 1 + 0.3275911 z, z = z' / sqrt(log2 e)
   else if (OP == 3) g.c = g.a * g.a;
   else if (OP == 4) g.b = __builtin_amdgcn_rcpf(g.b);                            // t
   else if (OP == 5) g.a = fmaf(1.061405429f, g.b, -1.453152027f);                // p
@@ -257,8 +264,8 @@ __device__ __forceinline__ void gelu_split8_packed(const float (&x)[8], u32x4& p
   for (int i = 0; i < 4; ++i) {
     const f32x2 xx = {x[2 * i], x[2 * i + 1]};
     const f32x2 ax = {fabsf(xx[0]), fabsf(xx[1])};
-    const f32x2 a = ax * 0.84932180028801904272f;
-    f32x2 b = __builtin_elementwise_fma(a, f32x2{0.27274550239055780f, 0.27274550239055780f}, f32x2{1.0f, 1.0f});
+    const f32x2 a = ax * float(GELU_ZP);
+    f32x2 b = __builtin_elementwise_fma(a, f32x2{float(GELU_PZ), float(GELU_PZ)}, f32x2{1.0f, 1.0f});
     f32x2 c = a * a;
     b = f32x2{__builtin_amdgcn_rcpf(b[0]), __builtin_amdgcn_rcpf(b[1])};
     f32x2 p = __builtin_elementwise_fma(b, f32x2{1.061405429f, 1.061405429f}, f32x2{-1.453152027f, -1.453152027f});
