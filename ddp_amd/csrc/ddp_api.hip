@@ -189,8 +189,14 @@ int validate(const ddp_cfg* c) {
   }
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
                    DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
-                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE)) {
+                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN)) {
     set_error("unknown flags 0x%x", c->flags);
+    return DDP_E_BADCFG;
+  }
+  if ((c->flags & DDP_FLAG_DDPM_CHAIN) && (c->task != DDP_TASK_SEG || c->sampler != DDP_SAMPLER_DDPM)) {
+    // (for any other task or sampler the bit is as unknown as an undefined one, and is reported that way)
+    set_error("unknown flags 0x%x for task %d, sampler %d: DDP_FLAG_DDPM_CHAIN exists for the segmentation ddpm sampler only", c->flags,
+              c->task, c->sampler);
     return DDP_E_BADCFG;
   }
   if ((c->flags & (DDP_FLAG_FORCE_X0 | DDP_FLAG_RECORD_X0)) && c->task != DDP_TASK_SEG) {
@@ -1021,6 +1027,11 @@ struct Plan {
   bool u_chain = false;
   // u chain: the step's tail runs inside the LAST layer's kernel (k_layer MODE 6) - the layer output never leaves the registers
   bool lt_fused = false;
+  // seg + DDPM with DDP_FLAG_DDPM_CHAIN on the fused prologue path: head7 / seg_tail / u_chain / lt_fused under the ddim sampler's
+  // conditions.  The ddpm update is u' = ua' u + uc' T[argmax] + std (W_m eps) with ua' = ((1 - c) / alpha) alpha', uc' = c alpha'
+  // (ddp.py:274-283 under W_m): a noise-adding step runs the pre-pass U <- ua' U + std (E W_m^T) (k_u_noise) in front of its tail,
+  // which then runs with (ua, uc) = (1, uc'); a step without noise runs the tail with (ua', uc'); the last step updates nothing
+  bool ddpm_chain = false;
   // depth (regression head) on the fused path: the step's last layer runs with the nine taps of conv_depth as its tail (k_layer
   // MODE 9) - no head GEMM, no SB copy of the layer output - and the step's update runs in front of the next step's head.  (The
   // binned head takes the route of DDP_FLAG_UNFUSED_TAIL: MODE 3 step head, a plain last layer, conv_depth + k_depth_bins,
@@ -1048,8 +1059,10 @@ Plan plan_of(const ddp_cfg* c, const Layout& o) {
   // the step's last layer with the head convolution as its tail (k_layer MODE 6 / 8 / 9)
   const bool lt = o.fused_pro && o.lt_stream && !(c->flags & DDP_FLAG_UNFUSED_TAIL);
   Plan p;
-  p.head7 = seg_ddim && o.fused_pro && o.r == 1 && o.head7_stream && !(c->flags & DDP_FLAG_SB_HEAD) && !((size_t(o.M) * 256) >> 32);
-  p.seg_tail = seg_ddim && o.fused_layer;
+  p.ddpm_chain = c->task == DDP_TASK_SEG && c->sampler == DDP_SAMPLER_DDPM && (c->flags & DDP_FLAG_DDPM_CHAIN) && o.fused_pro;
+  const bool seg_chain = seg_ddim || p.ddpm_chain;
+  p.head7 = seg_chain && o.fused_pro && o.r == 1 && o.head7_stream && !(c->flags & DDP_FLAG_SB_HEAD) && !((size_t(o.M) * 256) >> 32);
+  p.seg_tail = seg_chain && o.fused_layer;
   p.u_chain = p.seg_tail && o.fused_pro;
   p.lt_fused = p.u_chain && lt;
   p.depth_lt = c->task == DDP_TASK_DEPTH && lt && !o.nbins;
@@ -1181,6 +1194,28 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
       tl.sigma = sp.sigma;
       tl.alpha_next = sp.alpha_next;
       tl.sigma_next = sp.sigma_next;
+      if (p.ddpm_chain && tl.fuse_next) {
+        // fp32, in the reference's grouping (ddp.py:277: mask_t * (1 - c) / alpha, then * alpha_next)
+        const float ua = (1.0f - sp.ddpm_c) / sp.alpha * sp.alpha_next, uc = sp.ddpm_c * sp.alpha_next;
+        const bool noisy = sp.ddpm_add_noise != 0;
+        if (noisy) {
+          // the step's noise token-major (seeded: generated that way), then U <- ua' U + std (E W_m^T): u_s is complete (step 0's head
+          // / the previous tail wrote it) and this step's tail, inside the last layer's kernel or behind it, has not run yet
+          if (key) {
+            prof_begin(TAG_GENERIC, st);
+            DDP_TRY(recorded(launch_noise_fill_tok(key, o.snoise, o.B, o.r, o.N, s, st), st));
+          } else {
+            DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
+          }
+          prof_begin(TAG_GENERIC, st);
+          DDP_TRY(recorded(launch_u_noise(o.ubuf, o.snoise, o.wm, M0, ua, sp.ddpm_std, st), st));
+        }
+        // the tail derives ua = sigma_next / max(sigma, 1e-8), uc = alpha_next - alpha ua: these four give (ua, uc) back exactly
+        tl.alpha = 0.0f;
+        tl.sigma = 1.0f;
+        tl.sigma_next = noisy ? 1.0f : ua;
+        tl.alpha_next = uc;
+      }
     }
     // layer 0's projections come from the step head on the prologue path; the tail reads the fp32 layer output, a head GEMM its SB copy
     DDP_TRY(encoder_forward(w, o, aff, st, /*l0_projected=*/o.fused_pro, /*sb_out=*/!p.seg_tail, p.lt_fused ? &tl : nullptr));
@@ -2500,6 +2535,10 @@ int validate_fcn_loop(const ddp_cfg* cfg, int num_convs, int dilation) {
   DDP_TRY(validate(&c));
   if (cfg->task != DDP_TASK_SEG || cfg->head_h != cfg->h || cfg->head_w != cfg->w) {
     set_error("sample_fcn: segmentation only (FCNHeadWithTime is a segmentation head)");
+    return DDP_E_BADCFG;
+  }
+  if (cfg->flags & DDP_FLAG_DDPM_CHAIN) {
+    set_error("sample_fcn: DDP_FLAG_DDPM_CHAIN is a route of ddp_sample (the FCN loop has no u chain)");
     return DDP_E_BADCFG;
   }
   if (num_convs < 0 || num_convs > 8 || dilation < 1) {

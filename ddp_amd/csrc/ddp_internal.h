@@ -431,4 +431,9 @@ int launch_noise_fill_nchw(const uint32_t* key, float* out, int B, size_t per_im
 // noise added after step `step`, token-major rows of 256 channels: out (B * r * N, 256)
 int launch_noise_fill_tok(const uint32_t* key, float* out, int B, int r, int N, int step, hipStream_t st);
 
+// ---- ddp_ddpm_chain.hip (DDP_FLAG_DDPM_CHAIN) ------------------------------------------------------
+// the noise term of a ddpm step on the seg u chain, in place: ubuf (fp32 fragment-major, whole 32-token groups) <- ua * ubuf +
+// std * (noise . wm^T); noise = exactly M token-major rows of 256 fp32, wm (256, 256) fp32 row-major.  Exact-product fp32 MFMA
+int launch_u_noise(float* ubuf, const float* noise, const float* wm, int M, float ua, float std, hipStream_t st);
+
 }  // namespace ddp

@@ -209,8 +209,11 @@ class DDPEngine(_SeededNoise):
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
-                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False):
-        """``seeded_noise`` (DDP_FLAG_SEEDED_NOISE): start noise and ddpm step noise are generated on the device from a key -
+                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None):
+        """``ddpm_chain`` (DDP_FLAG_DDPM_CHAIN; seg + sampler='ddpm' only): ddpm_sample on the fused step boundary of the ddim
+        sampler, the step noise folded into u by one pre-pass per noise-adding step.  ``None`` reads the environment variable
+        ``DDP_DDPM_CHAIN`` (default off; ignored for any other task or sampler); ``True`` elsewhere raises ValueError.
+        ``seeded_noise`` (DDP_FLAG_SEEDED_NOISE): start noise and ddpm step noise are generated on the device from a key -
         ``sample(x, seed=...)``, ``last_noise()``; ``noise=`` / ``step_noise=`` are refused.
         ``record_steps`` (DDP_FLAG_STEP_RECORD): keep every step's prediction and compute the step-disagreement map on the
         device - ``step_record()`` / ``step_disagreement()`` after ``sample()``.
@@ -295,6 +298,12 @@ class DDPEngine(_SeededNoise):
             cfg.flags |= _lib.FLAG_STEP_RECORD
         if seeded_noise:
             cfg.flags |= _lib.FLAG_SEEDED_NOISE
+        if ddpm_chain is None:     # DDP_DDPM_CHAIN=1: A/B runs of scripts that build their engines without the kwarg
+            ddpm_chain = task == 'seg' and sampler == 'ddpm' and os.environ.get('DDP_DDPM_CHAIN', '0') != '0'
+        if ddpm_chain:
+            if task != 'seg' or sampler != 'ddpm':
+                raise ValueError(f"ddpm_chain is a route of the segmentation ddpm sampler (task {task!r}, sampler {sampler!r})")
+            cfg.flags |= _lib.FLAG_DDPM_CHAIN
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
         cfg.bit_scale, cfg.min_depth, cfg.max_depth, cfg.threshold = bit_scale, min_depth, max_depth, threshold

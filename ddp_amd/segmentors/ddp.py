@@ -92,6 +92,10 @@ class _SamplerMixin:
 @SEGMENTORS.register_module()
 class DDP(nn.Module, _SamplerMixin):
     task = 'seg'
+    # not a reference kwarg (the constructor's stay the reference's): set ``model.ddpm_chain = True`` to run ``diffusion='ddpm'`` /
+    # ``ddpm_sample`` on the fused step boundary of the ddim sampler (DDP_FLAG_DDPM_CHAIN); results agree with the default route to
+    # rounding.  Part of the engine key: flipping it builds (or re-uses) the other engine
+    ddpm_chain = False
 
     def __init__(self, bit_scale=0.1, timesteps=1, randsteps=1, time_difference=1, learned_sinusoidal_dim=16,
                  sample_range=(0, 0.999), noise_schedule='cosine', diffusion='ddim', accumulation=False,
@@ -155,9 +159,12 @@ class DDP(nn.Module, _SamplerMixin):
                       time_difference=self.time_difference, sample_range0=self.sample_range[0],
                       noise_schedule=self.noise_schedule, sampler=sampler, accumulation=acc, device=device,
                       record_steps=record_steps, seeded_noise=seeded)
+        chain = bool(self.ddpm_chain) and sampler == 'ddpm'
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule, bool(record_steps), bool(seeded))
+               self.noise_schedule, bool(record_steps), bool(seeded), chain)
         if isinstance(self.decode_head, FCNHeadWithTime):
+            if chain:
+                raise ValueError('ddpm_chain is a route of the deformable head\'s sampler: the FCNHeadWithTime loop has no u chain')
             # any registered head goes through _decode_head_forward_test in the reference (ddp.py:192-196); here the loop
             # around FCNHeadWithTime is its own C entry (ddp_sample_fcn), one engine per geometry
             def factory():
@@ -168,7 +175,8 @@ class DDP(nn.Module, _SamplerMixin):
         def factory():
             from ..engine import DDPEngine, count_layers
             nl = count_layers(self.hot_path_state_dict())
-            return DDPEngine(None, 'seg', h=h, w=w, feat_channels=256, weights=self._packed_weights(device, 'seg', nl), **common)
+            return DDPEngine(None, 'seg', h=h, w=w, feat_channels=256, weights=self._packed_weights(device, 'seg', nl),
+                             ddpm_chain=chain, **common)
         return self._get_engine(key, factory, geometry=(b, h, w))
 
     def hot_path_state_dict(self):

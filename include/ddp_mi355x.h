@@ -94,6 +94,19 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                        noise and the ddpm step noise are generated on the device from a key instead of being read from
                                        the caller's tensors - see "Seeded noise" below.  Any other flag may be combined.  Clear: launches,
                                        workspace sizes and outputs are unchanged */,
+       DDP_FLAG_DDPM_CHAIN = 4096 /* model surface, seg + DDP_SAMPLER_DDPM through ddp_sample only (any other task or sampler, and
+                                     ddp_sample_fcn, refuse it): ddpm_sample on the fused step boundary of the ddim sampler - the first
+                                     step's head from NCHW, the u chain and the last layer + tail kernel (k_layer MODE 7 / 4 / 6) - with
+                                     the step noise folded into u by ONE pre-pass per noise-adding step (csrc/ddp_ddpm_chain.hip:
+                                     U <- ua' U + std (E W_m^T), ua' = ((1 - c) / alpha) alpha_next; the tail then runs u' = U + c alpha_next
+                                     T[argmax]; a step without noise runs the tail with (ua', c alpha_next); the last step has no update,
+                                     no noise fill or transpose and no pre-pass).  The same operators regrouped: results agree with the
+                                     flag-clear sampler to rounding, not bit for bit.  Without effect on the fp32 engine and with
+                                     DDP_FLAG_UNFUSED_LAYER / _UNFUSED_PROLOGUE (the flag-clear launches run).  Combines with
+                                     DDP_FLAG_UNFUSED_TAIL, _SB_HEAD, _RECORD_X0, _FORCE_X0, _STEP_RECORD, _SEEDED_NOISE and
+                                     _GATHER_GUESS_ZERO as the ddim chain does.  Nothing new is carved: ddp_query_workspace and
+                                     ddp_query_const_workspace return the bytes of the cfg without the flag.  Clear: launches, workspace
+                                     sizes and outputs are unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
