@@ -79,11 +79,14 @@ class DDP(nn.Module, _SamplerMixin):
                                       nn.Linear(tmp_channels * 4, tmp_channels * 4))
 
     @torch.no_grad()
-    def ddim_sample(self, x, head, noise=None, return_steps=False, image_base=0, call=0):
-        """With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
+    def ddim_sample(self, x, head, noise=None, return_steps=False, image_base=0, call=0, hints=None):
+        """``hints``: not built for the bev sampler (ValueError; DDP_FLAG_X0_HINTS is a seg / depth flag).
+        With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
         ``return_steps``: -> (out, record (K,b,r,head_h,head_w) int32 bit words - bit c = the step's prob_c > threshold
         (fusion_models/ddp.py:290) -, disagreement (b,head_h,head_w) - the fraction of recorded bits that differ from
         out > threshold)."""
+        if hints is not None:
+            raise ValueError('hints are not built for the bev sampler (DDP_FLAG_X0_HINTS exists for seg and depth)')
         x0 = x[0]
         if not x0.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')

@@ -97,6 +97,9 @@ struct Layout {
   unsigned char* step_rec = nullptr;
   float* step_map = nullptr;
   float* seed_noise = nullptr;   // DDP_FLAG_SEEDED_NOISE: (B, r, Cm, h, w) start noise of the call, written by k_noise_fill_nchw
+  // DDP_FLAG_X0_HINTS: the caller-written hint map (B, N) - seg uint8, depth fp32 - and its per-row form (M0), written by k_hint_rows_*
+  void* hint_map = nullptr;
+  void* hint_rows = nullptr;
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
@@ -189,9 +192,23 @@ int validate(const ddp_cfg* c) {
   }
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
                    DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
-                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN)) {
+                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN | DDP_FLAG_X0_HINTS)) {
     set_error("unknown flags 0x%x", c->flags);
     return DDP_E_BADCFG;
+  }
+  if (c->flags & DDP_FLAG_X0_HINTS) {
+    if (c->task == DDP_TASK_BEV) {
+      set_error("DDP_FLAG_X0_HINTS exists for the segmentation and depth samplers (task %d: the bev sampler takes no hints)", c->task);
+      return DDP_E_BADCFG;
+    }
+    if (c->flags & DDP_FLAG_FORCE_X0) {
+      set_error("DDP_FLAG_X0_HINTS cannot be combined with DDP_FLAG_FORCE_X0 (both supply the class the step feeds back)");
+      return DDP_E_BADCFG;
+    }
+    if (c->task == DDP_TASK_SEG && c->num_classes > 255) {
+      set_error("DDP_FLAG_X0_HINTS: num_classes %d leaves no uint8 value for a free pixel (<= 255 classes)", c->num_classes);
+      return DDP_E_BADCFG;
+    }
   }
   if ((c->flags & DDP_FLAG_DDPM_CHAIN) && (c->task != DDP_TASK_SEG || c->sampler != DDP_SAMPLER_DDPM)) {
     // (for any other task or sampler the bit is as unknown as an undefined one, and is reported that way)
@@ -453,6 +470,12 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   }
   // seeded start noise: immediately in front of the step-record buffers (the end of the workspace without them), so that the record
   // and the map stay the last of the workspace and every other offset is the one of the cfg without the flag
+  // x0 hints: the private row buffer, then the caller's map immediately in front of the seeded-noise buffer (include/ddp_mi355x.h)
+  if (c->flags & DDP_FLAG_X0_HINTS) {
+    const bool bytes1 = c->task == DDP_TASK_SEG;
+    o->hint_rows = cv.take(bytes1 ? (o->M0 + 3) / 4 : o->M0);
+    o->hint_map = cv.take(bytes1 ? (size_t(o->B) * o->N + 3) / 4 : size_t(o->B) * o->N);
+  }
   if (c->flags & DDP_FLAG_SEEDED_NOISE) o->seed_noise = cv.take(o->M0 * o->Cm);
   // step record + disagreement map: the LAST two buffers, so that every offset in front of them is the one of the cfg without
   // the flag.  (seg with DDP_FLAG_RECORD_X0 as well: one buffer serves both flags - the x0 trace moves here)
@@ -855,6 +878,7 @@ DepthUpdateArgs depth_update_args(const ddp_cfg* c, const ddp_weights* w, const 
   a.scale_up = (c->flags & DDP_FLAG_DEPTH_SCALE_UP) ? 1 : 0;
   a.eps_depth = depth_head_eps(c);
   a.st = stp;
+  a.hint = static_cast<const float*>(o.hint_rows);   // (nullptr without DDP_FLAG_X0_HINTS)
   return a;
 }
 
@@ -894,12 +918,21 @@ SegUpdateArgs seg_update_args(const float* logits, int ldl, int num_classes, con
 
 // the x0 trace of seg step s.  FORCE_X0: [0] = the caller's decisions (read), [1] = the step's own argmax (written); RECORD_X0
 // alone: [0] written; STEP_RECORD: the same (K, M) record, in the step-record buffer
+// DDP_FLAG_X0_HINTS: the hint rows take the place of the forced decisions - the same buffer at every step, with the keep-the-argmax
+// reading of a value >= num_classes - and the record is the one of the cfg without the flag (the model's own argmax)
 struct X0Trace {
   unsigned char* idx = nullptr;
   const unsigned char* force = nullptr;
+  int keep = 0;
 };
 X0Trace x0_trace_of(const ddp_cfg* c, const Layout& o, int s) {
   X0Trace t;
+  if (c->flags & DDP_FLAG_X0_HINTS) {
+    t.force = static_cast<const unsigned char*>(o.hint_rows);
+    t.keep = 1;
+    if (c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_STEP_RECORD)) t.idx = o.x0_trace + size_t(s) * o.M;
+    return t;
+  }
   if (c->flags & DDP_FLAG_FORCE_X0) {
     t.force = o.x0_trace + size_t(s) * o.M;
     t.idx = o.x0_trace + size_t(o.K + s) * o.M;
@@ -1186,6 +1219,7 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
         tl.w = o.wh;
       }
       tl.x0_force = x0.force;
+      tl.x0_keep = x0.keep;
       tl.x0_idx = x0.idx;
       tl.M = M;
       tl.num_classes = o.Kc;
@@ -1227,6 +1261,7 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
     SegUpdateArgs a = seg_update_args(o.logits, o.ldl, o.Kc, o.lut, o.mask, o.prob, c->accumulation ? (s == 0 ? 1 : 2) : 0, c->sampler,
                                       sp, M);
     a.x0_force = x0.force;
+    a.x0_keep = x0.keep;
     a.x0_idx = x0.idx;
     if (c->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
       if (key) {   // DDP_FLAG_SEEDED_NOISE: the step's noise is generated token-major - no NCHW tensor, no transpose
@@ -1582,6 +1617,11 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
   Layout o;
   carve(cfg, static_cast<float*>(d_workspace), &o);
   const Plan p = plan_of(cfg, o);
+  // DDP_FLAG_X0_HINTS: the caller's map as read NOW (a captured graph replays this launch on the buffer's current content) -> rows
+  if (o.hint_rows) {
+    prof_begin(TAG_GENERIC, st);
+    DDP_TRY(recorded(launch_hint_rows(o.hint_map, o.hint_rows, cfg->task, o.B, o.r, o.N, o.Kc, st), st));
+  }
   const uint32_t* key = nullptr;
   if (seeded) {
     key = reinterpret_cast<const uint32_t*>(d_noise);
@@ -1621,6 +1661,13 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
 
 int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float* d_feat, const float* d_temb,
                      float* d_out, void* d_workspace, void* stream) {
+  // one decoder pass has no x0 feedback: DDP_FLAG_X0_HINTS is ignored (the buffers it carves lie behind everything used here)
+  ddp_cfg no_hints;
+  if (cfg && (cfg->flags & DDP_FLAG_X0_HINTS)) {
+    no_hints = *cfg;
+    no_hints.flags &= ~DDP_FLAG_X0_HINTS;
+    cfg = &no_hints;
+  }
   DDP_TRY(validate(cfg));
   DDP_TRY(check_weights(cfg, weights));
   DDP_TRY(check_ptr(d_workspace, "workspace"));
@@ -2539,6 +2586,10 @@ int validate_fcn_loop(const ddp_cfg* cfg, int num_convs, int dilation) {
   }
   if (cfg->flags & DDP_FLAG_DDPM_CHAIN) {
     set_error("sample_fcn: DDP_FLAG_DDPM_CHAIN is a route of ddp_sample (the FCN loop has no u chain)");
+    return DDP_E_BADCFG;
+  }
+  if (cfg->flags & DDP_FLAG_X0_HINTS) {
+    set_error("sample_fcn: DDP_FLAG_X0_HINTS is built for ddp_sample only (the FCN loop takes no hints)");
     return DDP_E_BADCFG;
   }
   if (num_convs < 0 || num_convs > 8 || dilation < 1) {

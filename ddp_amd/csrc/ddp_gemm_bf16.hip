@@ -225,6 +225,7 @@ int launch_b3_tail(const TailLaunch& a, hipStream_t st) {
   la.mask_sb = a.mask_sb;
   la.x0_idx = a.x0_idx;
   la.x0_force = a.x0_force;
+  la.x0_keep = a.x0_keep;
   la.num_classes = a.num_classes;
   la.ldl = a.ldl;
   la.prob_mode = a.prob_mode;
@@ -337,6 +338,7 @@ int launch_b3_l0proj(const L0ProjLaunch& a, hipStream_t st) {
     la.d_alpha = u.st.alpha;
     la.d_alpha_next = u.st.alpha_next;
     la.d_sigma_next = u.st.sigma_next;
+    la.dhint = u.hint;
   }
   static LdsAttrOnce attr;
   attr.ensure(reinterpret_cast<const void*>(&b3::k_layer<TAG_VALUE, 3>), int(b3::LYR_LDS_B));

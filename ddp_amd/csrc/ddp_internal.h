@@ -132,6 +132,7 @@ struct TailLaunch {
   unsigned short* mask_sb;
   unsigned char* x0_idx;        // optional: argmax class per token (diagnostic trace)
   const unsigned char* x0_force;  // optional (DDP_FLAG_FORCE_X0): the class to feed back instead of the argmax
+  int x0_keep;                    // DDP_FLAG_X0_HINTS: x0_force is the hint row buffer - a value >= num_classes keeps the argmax
   int M, num_classes, ldl, prob_mode;
   float alpha, sigma, alpha_next, sigma_next;
   // fuse_next: this launch is also the head of the NEXT step (k_layer MODE 4): mask_sb = nullptr, the update runs on
@@ -271,6 +272,7 @@ struct SegUpdateArgs {
   const float* step_noise;  // ddpm (M,256) token-major or nullptr
   unsigned char* x0_idx;    // optional: argmax class per token (diagnostic trace)
   const unsigned char* x0_force;  // optional (DDP_FLAG_FORCE_X0): the class to feed back instead of the argmax
+  int x0_keep;                    // DDP_FLAG_X0_HINTS: x0_force is the hint row buffer - a value >= num_classes keeps the argmax
   int sampler;
   ddp_step st;
   int rows;
@@ -330,6 +332,8 @@ struct DepthUpdateArgs {
   float min_depth, max_depth, bit_scale, eps_depth;
   int scale_up;             // depth = sigmoid(s) * eps_depth instead of relu(s) + eps_depth
   ddp_step st;
+  const float* hint;        // DDP_FLAG_X0_HINTS: (M) hint rows; a value > 0 replaces the prediction in the x0 normalisation only (pred keeps
+                            // the model's own); nullptr: no hints
 };
 int launch_depth_update(const DepthUpdateArgs& a, hipStream_t st);
 // binned depth head (decode_head.py:233-250): per pixel, the n_bins logits of conv_depth -> normalised weights -> expectation over the
@@ -435,5 +439,10 @@ int launch_noise_fill_tok(const uint32_t* key, float* out, int B, int r, int N, 
 // the noise term of a ddpm step on the seg u chain, in place: ubuf (fp32 fragment-major, whole 32-token groups) <- ua * ubuf +
 // std * (noise . wm^T); noise = exactly M token-major rows of 256 fp32, wm (256, 256) fp32 row-major.  Exact-product fp32 MFMA
 int launch_u_noise(float* ubuf, const float* noise, const float* wm, int M, float ua, float std, hipStream_t st);
+
+// ---- ddp_hints.hip (DDP_FLAG_X0_HINTS) --------------------------------------------------------------
+// the caller's hint map (B, N) - seg uint8, depth fp32 - expanded to the rows m = (b * r + rr) * N + n the decision kernels read, the
+// "free" encodings normalised (seg: >= num_classes -> 255; depth: 0, negative, NaN, +-inf -> 0).  `rows` holds whole 256-byte granules
+int launch_hint_rows(const void* map, void* rows, int task, int B, int r, int N, int num_classes, hipStream_t st);
 
 }  // namespace ddp

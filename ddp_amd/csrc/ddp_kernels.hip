@@ -1661,8 +1661,13 @@ __global__ void __launch_bounds__(256) k_seg_update(SegUpdateArgs a) {
   if (bi >= K) bi = 0;
   if (a.x0_idx && lane == 0) a.x0_idx[m] = (unsigned char)bi;
   if (a.x0_force) {               // teacher forcing (DDP_FLAG_FORCE_X0): the caller's class goes into the update, not the argmax
-    bi = a.x0_force[m];
-    if (bi >= K) bi = 0;
+    const int f = a.x0_force[m];
+    if (a.x0_keep) {              // DDP_FLAG_X0_HINTS: the hint rows - a value >= K leaves the pixel to the argmax
+      if (f < K) bi = f;
+    } else {
+      bi = f;
+      if (bi >= K) bi = 0;
+    }
   }
   if (a.prob && a.prob_mode) {
     float* pr = a.prob + size_t(m) * a.ldl;
@@ -1853,6 +1858,10 @@ __global__ void __launch_bounds__(256) k_depth_update(DepthUpdateArgs a) {
   a.pred[m] = pred;
   }
   if (!a.depth_t) return;   // head-only call: no sampler update
+  if (a.hint) {             // DDP_FLAG_X0_HINTS: a hinted pixel projects its hint (a.pred keeps the model's own prediction)
+    const float hv = a.hint[m];
+    pred = hv > 0.f ? hv : pred;
+  }
   float x0 = (pred - a.min_depth) / (a.max_depth - a.min_depth);
   x0 = (x0 * 2.0f - 1.0f) * a.bit_scale;
   x0 = fminf(fmaxf(x0, -a.bit_scale), a.bit_scale);
@@ -1945,6 +1954,7 @@ __global__ void __launch_bounds__(256) k_blk_to_pad(const float* __restrict__ in
 // formed: layer 0 builds its residual from xproj and d (k_layer MODE 10).
 struct DepthHeadDev {
   const float *rvpad, *rs, *wv, *ws, *py, *px, *taps, *dbias;
+  const float* hint;        // DDP_FLAG_X0_HINTS: (M) hint rows or nullptr (DepthUpdateArgs::hint)
   float *dvec, *v_out, *samp_out;
   int R, h, w, has_upd, scale_up;
   float d_min, d_max, d_bit, d_eps, d_sig, d_alpha, d_alpha_next, d_sigma_next;
@@ -1973,7 +1983,11 @@ __global__ void __launch_bounds__(256) k_depth_head(DepthHeadDev a) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) sacc += tv[t];
     sacc += a.dbias[0];
-    const float pred = a.scale_up ? a.d_eps / (1.0f + expf(-sacc)) : fmaxf(sacc, 0.f) + a.d_eps;
+    float pred = a.scale_up ? a.d_eps / (1.0f + expf(-sacc)) : fmaxf(sacc, 0.f) + a.d_eps;
+    if (a.hint) {
+      const float hv = a.hint[m];
+      pred = hv > 0.f ? hv : pred;
+    }
     float x0 = (pred - a.d_min) / (a.d_max - a.d_min);
     x0 = (x0 * 2.0f - 1.0f) * a.d_bit;
     x0 = fminf(fmaxf(x0, -a.d_bit), a.d_bit);
@@ -2574,7 +2588,7 @@ int launch_depth_head(const DepthHeadArgs& a, hipStream_t st) {
   d.dvec = a.dvec; d.v_out = a.v_out; d.samp_out = a.samp_out;
   d.R = a.R; d.h = a.h; d.w = a.w;
   d.has_upd = a.upd ? 1 : 0;
-  d.taps = nullptr; d.dbias = nullptr; d.scale_up = 0;
+  d.taps = nullptr; d.dbias = nullptr; d.scale_up = 0; d.hint = nullptr;
   d.d_min = d.d_max = d.d_bit = d.d_eps = d.d_sig = d.d_alpha = d.d_alpha_next = d.d_sigma_next = 0.f;
   if (a.upd) {
     const DepthUpdateArgs& u = *a.upd;
@@ -2582,7 +2596,7 @@ int launch_depth_head(const DepthHeadArgs& a, hipStream_t st) {
       set_error("depth head: the fused update must work on the head's own map");
       return DDP_E_BADCFG;
     }
-    d.taps = u.taps; d.dbias = u.bias_ptr; d.scale_up = u.scale_up;
+    d.taps = u.taps; d.dbias = u.bias_ptr; d.scale_up = u.scale_up; d.hint = u.hint;
     d.d_min = u.min_depth; d.d_max = u.max_depth; d.d_bit = u.bit_scale; d.d_eps = u.eps_depth;
     d.d_sig = u.st.sigma; d.d_alpha = u.st.alpha; d.d_alpha_next = u.st.alpha_next; d.d_sigma_next = u.st.sigma_next;
   }

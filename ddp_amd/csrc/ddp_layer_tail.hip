@@ -80,6 +80,7 @@ int launch_b3_layer_tail(const LayerLaunch& l, const TailLaunch& t, const unsign
   la.prob = t.prob;
   la.x0_idx = t.x0_idx;
   la.x0_force = t.x0_force;
+  la.x0_keep = t.x0_keep;
   la.num_classes = t.num_classes;
   la.ldl = t.ldl;
   la.prob_mode = t.prob_mode;

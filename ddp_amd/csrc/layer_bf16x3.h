@@ -167,6 +167,11 @@ struct LayerArgs {
   } gp[4];
   int g_tiles, g_act, conv_dil;
   unsigned long long* stamps;    // -DDDP_LYR_STAMP builds only (scripts/stamp_layer.py): per (block, wave) cycle sums of the phases
+  // DDP_FLAG_X0_HINTS (the last fields: every other argument keeps its place).  x0_keep: the FORCE instantiations read x0_force as the
+  // hint rows - a value < num_classes is fed back, any other keeps the argmax.  dhint (MODE 3 with dtaps): (M) depth hint rows, a value
+  // > 0 replaces the prediction in the x0 normalisation; nullptr: none
+  const float* dhint;
+  int x0_keep;
 };
 
 // vmcnt(12): everything but the 12 newest vector-memory ops (= the DMA pieces of the stage just issued) is done
@@ -959,7 +964,11 @@ k_layer(LayerArgs la) {
 #pragma unroll
           for (int t = 0; t < 9; ++t) sacc += tv[t];
           sacc += la.dbias[0];
-          const float pred = la.d_scale_up ? la.d_eps / (1.0f + expf(-sacc)) : fmaxf(sacc, 0.f) + la.d_eps;
+          float pred = la.d_scale_up ? la.d_eps / (1.0f + expf(-sacc)) : fmaxf(sacc, 0.f) + la.d_eps;
+          if (la.dhint) {                                     // (uniform) DDP_FLAG_X0_HINTS: a hinted pixel projects its hint
+            const float hv = la.dhint[mr];
+            pred = hv > 0.f ? hv : pred;
+          }
           float x0 = (pred - la.d_min) / (la.d_max - la.d_min);
           x0 = (x0 * 2.0f - 1.0f) * la.d_bit;
           x0 = fminf(fmaxf(x0, -la.d_bit), la.d_bit);
@@ -1579,8 +1588,13 @@ k_layer(LayerArgs la) {
       if (la.x0_idx && valid && h == 0) la.x0_idx[m] = (unsigned char)bi;
       if constexpr (FORCE) {      // teacher forcing: a test instrument in its own instantiations, the product's tails do not have it
         if (valid) {
-          bi = la.x0_force[m];
-          if (bi >= K) bi = 0;
+          const int f = la.x0_force[m];
+          if (la.x0_keep) {       // DDP_FLAG_X0_HINTS: the hint rows - a value >= K leaves the pixel to the argmax
+            if (f < K) bi = f;
+          } else {
+            bi = f;
+            if (bi >= K) bi = 0;
+          }
         }
       }
       // Every global load of the epilogue is issued in a batch ahead of its consumers.  The straightforward loops (load 5,

@@ -209,8 +209,14 @@ class DDPEngine(_SeededNoise):
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
-                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None):
-        """``ddpm_chain`` (DDP_FLAG_DDPM_CHAIN; seg + sampler='ddpm' only): ddpm_sample on the fused step boundary of the ddim
+                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None, x0_hints=False):
+        """``x0_hints`` (DDP_FLAG_X0_HINTS; seg and depth): where the caller knows the answer it is fed back as x0 at every step in
+        place of the model's own prediction - ``set_hints()`` / ``hints_view()`` / ``clear_hints()``, ``SampleGraph.replay(hints=)``.
+        seg: (B, h, w) uint8 classes, a value >= num_classes (255) leaves the pixel free; depth: (B, h, w) float32 metric depth, 0 /
+        negative / NaN / inf leaves it free.  Unset hints are no hints: the engine sets everything free whenever it allocates or
+        regrows the workspace and on every ``set_geometry``.  Hints act through the update, i.e. from the second step on:
+        ``timesteps=1`` is accepted and they have no effect.  The output and the step record stay the model's own prediction.
+        ``ddpm_chain`` (DDP_FLAG_DDPM_CHAIN; seg + sampler='ddpm' only): ddpm_sample on the fused step boundary of the ddim
         sampler, the step noise folded into u by one pre-pass per noise-adding step.  ``None`` reads the environment variable
         ``DDP_DDPM_CHAIN`` (default off; ignored for any other task or sampler); ``True`` elsewhere raises ValueError.
         ``seeded_noise`` (DDP_FLAG_SEEDED_NOISE): start noise and ddpm step noise are generated on the device from a key -
@@ -304,6 +310,12 @@ class DDPEngine(_SeededNoise):
             if task != 'seg' or sampler != 'ddpm':
                 raise ValueError(f"ddpm_chain is a route of the segmentation ddpm sampler (task {task!r}, sampler {sampler!r})")
             cfg.flags |= _lib.FLAG_DDPM_CHAIN
+        if x0_hints:
+            if task == 'bev':
+                raise ValueError('x0_hints is built for the seg and depth samplers (DDP_FLAG_X0_HINTS): the bev sampler takes no hints')
+            if force_x0:
+                raise ValueError('x0_hints cannot be combined with force_x0 (DDP_FLAG_X0_HINTS / DDP_FLAG_FORCE_X0)')
+            cfg.flags |= _lib.FLAG_X0_HINTS
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
         cfg.bit_scale, cfg.min_depth, cfg.max_depth, cfg.threshold = bit_scale, min_depth, max_depth, threshold
@@ -324,11 +336,51 @@ class DDPEngine(_SeededNoise):
         self._sampled = False
         self.geometry_changes = 0
         self._init_key()
+        self.clear_hints(_if_any=True)
 
     def _workspace_bytes(self):
         nbytes = C.c_size_t(0)
         _lib.check(self.lib.ddp_query_workspace(C.byref(self.cfg), C.byref(nbytes)), self.lib)
         return nbytes.value
+
+    # ---- DDP_FLAG_X0_HINTS ---------------------------------------------------------------------
+    def hints_view(self):
+        """(B, h, w) VIEW of the caller-written hint map inside the workspace - uint8 (seg) or float32 (depth); the kernels read it
+        when they run (a captured graph picks up what it holds at replay).  Place: include/ddp_mi355x.h, "x0 hints"."""
+        c = self.cfg
+        if not c.flags & _lib.FLAG_X0_HINTS:
+            raise _lib.DdpError('hints need an engine built with x0_hints=True')
+        seg = c.task == _lib.TASK_SEG
+        nbytes = c.batch * c.h * c.w * (1 if seg else 4)
+        end = self._workspace_bytes()
+        if c.flags & _lib.FLAG_STEP_RECORD:
+            rec, smap = step_record_sizes(c)
+            end -= _round256(rec) + _round256(smap)
+        if c.flags & _lib.FLAG_SEEDED_NOISE:
+            end -= _round256(c.batch * c.randsteps * (256 if seg else 1) * c.h * c.w * 4)
+        off = end - _round256(nbytes)
+        v = self.workspace.view(torch.uint8)[off:off + nbytes]
+        return (v if seg else v.view(torch.float32)).view(c.batch, c.h, c.w)
+
+    def set_hints(self, hints):
+        """copy ``hints`` (B, h, w) - uint8 for seg, float32 for depth, on the engine's device - into the hint map (stream-ordered)"""
+        v = self.hints_view()
+        if not isinstance(hints, torch.Tensor) or hints.dtype != v.dtype:
+            raise _lib.DdpError(f'hints must be a {v.dtype} tensor, got {getattr(hints, "dtype", type(hints))}')
+        if tuple(hints.shape) != tuple(v.shape):
+            raise _lib.DdpError(f'hints must have shape {tuple(v.shape)} (batch, h, w), got {tuple(hints.shape)}')
+        if hints.device != self.device:
+            raise _lib.DdpError(f'engine lives on {self.device}: hints are on {hints.device}')
+        with torch.cuda.device(self.device):
+            v.copy_(hints, non_blocking=True)
+
+    def clear_hints(self, _if_any=False):
+        """every pixel free (seg: 255, depth: 0)"""
+        if _if_any and not self.cfg.flags & _lib.FLAG_X0_HINTS:
+            return
+        v = self.hints_view()
+        with torch.cuda.device(self.device):
+            v.fill_(255 if v.dtype == torch.uint8 else 0)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -371,6 +423,7 @@ class DDPEngine(_SeededNoise):
         self.geometry_changes += 1
         self._x0_set = False       # force_x0: the decisions buffer belongs to the geometry region
         self._sampled = False      # (so do the step record and the disagreement map)
+        self.clear_hints(_if_any=True)   # (and the hint map: another geometry or another buffer - unset hints are no hints)
         return self
 
     def out_shape(self):
@@ -550,8 +603,10 @@ class SampleGraph:
         self.workspace = engine.workspace
         self.workspace_ptr = engine.workspace.data_ptr()
 
-    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None):
-        """seeded engines: ``seed`` / ``image_base`` / ``call`` given here replace those words of the engine's device key (stream-
+    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None, hints=None):
+        """``hints`` (x0_hints engines): written to the engine's hint map in front of the launch (``DDPEngine.set_hints``); None: the
+        graph runs on what the map holds.
+        seeded engines: ``seed`` / ``image_base`` / ``call`` given here replace those words of the engine's device key (stream-
         ordered, in front of the launch); none given: the graph repeats the last key."""
         eng = self.engine
         if eng.seeded:
@@ -574,6 +629,8 @@ class SampleGraph:
             self.step_noise.copy_(step_noise.reshape(self.step_noise.shape), non_blocking=True)
         if seed is not None or image_base is not None or call is not None:
             eng._write_key(seed, image_base, None, call)
+        if hints is not None:
+            eng.set_hints(hints)
         self.graph.replay()
         return self.out
 
@@ -584,7 +641,9 @@ class FcnSamplerEngine(_SeededNoise):
 
     def __init__(self, state_dict, head, *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150, bit_scale=0.01,
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
-                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False):
+                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False, x0_hints=False):
+        if x0_hints:
+            raise ValueError('x0_hints is built for ddp_sample only (DDP_FLAG_X0_HINTS): the FCN-head loop takes no hints')
         self.lib = _lib.load(lib_path)
         if not torch.cuda.is_available():
             raise _lib.DdpError('no HIP device visible: ddp_amd has no CPU path')

@@ -72,6 +72,22 @@ class _SamplerMixin:
             return {}
         return dict(image_base=image_base, call=call)
 
+    @staticmethod
+    def _hint_map(hints, b, h, w, dtype):
+        """``hints`` (b, Hh, Wh) in the frame of the network input ``img`` (or a one-element augmentation list of it) -> the (b, h, w)
+        hint map of the engine (DDP_FLAG_X0_HINTS), brought to the map resolution with ``F.interpolate(mode='nearest')`` - the rule
+        ``forward_train`` resamples its label map with (segmentors/ddp.py:149).  Depth uses nearest too: a sparse map's holes (0 =
+        free) must not be averaged into their neighbours."""
+        if isinstance(hints, (list, tuple)):
+            if len(hints) != 1:
+                raise ValueError('hints: test-time augmentation takes no hints (one hint map per batch, not one per augmentation)')
+            hints = hints[0]
+        if not torch.is_tensor(hints) or hints.dim() != 3 or hints.shape[0] != b:
+            raise ValueError(f'hints must be a (batch, H, W) tensor for a batch of {b} images, got '
+                             f'{tuple(hints.shape) if torch.is_tensor(hints) else type(hints)}')
+        m = F.interpolate(hints[:, None].float(), size=(h, w), mode='nearest')[:, 0]
+        return m.to(dtype).contiguous()
+
     def _get_engine(self, key, factory, geometry=None):
         cache = self.__dict__.setdefault('_engine_cache', {})
         ver = self._weights_version()
@@ -150,7 +166,7 @@ class DDP(nn.Module, _SamplerMixin):
         return times
 
     def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample',
-                    record_steps=False, seeded=False):
+                    record_steps=False, seeded=False, hints=False):
         from ..decode_heads.fcn_head_with_time import FCNHeadWithTime
         K = self.timesteps if timesteps is None else timesteps
         r = self.randsteps if randsteps is None else randsteps
@@ -161,8 +177,10 @@ class DDP(nn.Module, _SamplerMixin):
                       record_steps=record_steps, seeded_noise=seeded)
         chain = bool(self.ddpm_chain) and sampler == 'ddpm'
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule, bool(record_steps), bool(seeded), chain)
+               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints))
         if isinstance(self.decode_head, FCNHeadWithTime):
+            if hints:
+                raise ValueError('hints are built for the deformable head\'s sampler: the FCNHeadWithTime loop takes none')
             if chain:
                 raise ValueError('ddpm_chain is a route of the deformable head\'s sampler: the FCNHeadWithTime loop has no u chain')
             # any registered head goes through _decode_head_forward_test in the reference (ddp.py:192-196); here the loop
@@ -176,7 +194,7 @@ class DDP(nn.Module, _SamplerMixin):
             from ..engine import DDPEngine, count_layers
             nl = count_layers(self.hot_path_state_dict())
             return DDPEngine(None, 'seg', h=h, w=w, feat_channels=256, weights=self._packed_weights(device, 'seg', nl),
-                             ddpm_chain=chain, **common)
+                             ddpm_chain=chain, x0_hints=bool(hints), **common)
         return self._get_engine(key, factory, geometry=(b, h, w))
 
     def hot_path_state_dict(self):
@@ -190,37 +208,53 @@ class DDP(nn.Module, _SamplerMixin):
             raise RuntimeError(f'expected {self.decode_head.in_channels[0]} feature channels, got {x.shape[1]}')
 
     @torch.no_grad()
-    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0):
-        """x (b,256,h,w) -> (b,K,h,w).  ``noise`` (b,r,256,h,w) may be injected (parity tests);
+    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None):
+        """``hints`` (b,Hh,Wh) uint8 in the frame of the network input (call-time only; DDP_FLAG_X0_HINTS): a class < num_classes is
+        fed back as x0 at that pixel in place of the argmax at every step, any other value (255) leaves the pixel free; resampled to
+        (h,w) with nearest.  The scores returned (and ``return_steps``' record) stay the model's own; ``timesteps=1``: no effect.
+        x (b,256,h,w) -> (b,K,h,w).  ``noise`` (b,r,256,h,w) may be injected (parity tests);
         by default it is drawn with torch.randn like the reference (ddp.py:220).
         With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
         ``return_steps``: -> (out, record (K,b,r,h,w) uint8 - every step's argmax class, the reference's ``outs`` as decisions -,
         disagreement (b,h,w) - the fraction of them that differ from the output's argmax)."""
         self._check_feature(x)
         b, c, h, w = x.shape
+        hk = {} if hints is None else dict(hints=True)
+        hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
         if noise is None and self.noise_seed is not None:
-            eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True)
+            eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True, **hk)
+            if hmap is not None:
+                eng.set_hints(hmap)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
             noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
-        eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps)
+        eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, **hk)
+        if hmap is not None:
+            eng.set_hints(hmap)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     @torch.no_grad()
-    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0):
+    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0, hints=None):
+        """``hints``: as ``ddim_sample``"""
         self._check_feature(x)
         b, c, h, w = x.shape
+        hk = {} if hints is None else dict(hints=True)
+        hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
         if noise is None and step_noise is None and self.noise_seed is not None:
-            eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True)
+            eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True, **hk)
+            if hmap is not None:
+                eng.set_hints(hmap)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
             noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
         if step_noise is None:
             step_noise = torch.randn((self.timesteps, b, self.randsteps, c, h, w), device=x.device)
-        eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps)
+        eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, **hk)
+        if hmap is not None:
+            eng.set_hints(hmap)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
@@ -295,8 +329,10 @@ class DDP(nn.Module, _SamplerMixin):
             out = tuple(img_meta[0]['ori_shape'][:2])
         return seg_slide_postprocess(scores, ys, xs, (ch, cw), img.shape[2:], keep, out, self.align_corners, flip, want)
 
-    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0):
+    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None):
         """encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
+        if hints is not None:
+            raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
         return self._slide(img, img_meta, rescale, 'scores', **self._seed_kw(image_base, call))
 
     def inference(self, img, img_meta, rescale, image_base=0, call=0):
@@ -322,8 +358,9 @@ class DDP(nn.Module, _SamplerMixin):
 
     AUG_CALL_STRIDE = 1 << 16            # seeded noise: augmentation a owns the call values [a * stride, (a + 1) * stride)
 
-    def aug_test(self, imgs, img_metas, rescale=True, image_base=0):
-        """With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None):
+        """``hints`` are not built for test-time augmentation (ValueError).
+        With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
         index), so no two augmentations of an image share noise.
         encoder_decoder.py:306-331: mean of the per-augmentation probabilities (multi-scale / flip), then argmax.
         Every augmentation runs the full sampling loop with its own noise, as in the reference; only the LOW-RESOLUTION
@@ -331,6 +368,8 @@ class DDP(nn.Module, _SamplerMixin):
         softmax -> flip-undo for all of them, the mean and the argmax per output pixel: the (1,K,H,W) tensors ``inference``
         materialises per augmentation and the running sum at ori_shape never exist."""
         from ..engine import seg_aug_postprocess
+        if hints is not None:
+            raise ValueError('hints are not built for aug_test (every augmentation has its own frame)')
         assert rescale, 'aug_test rescales every augmentation back to ori_shape'
         if len(imgs) != len(img_metas):
             raise ValueError(f'num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})')
@@ -369,13 +408,17 @@ class DDP(nn.Module, _SamplerMixin):
                 flip = meta.get('flip_direction', 'horizontal')
         return crop, out_size, flip
 
-    def simple_test(self, img, img_meta=None, rescale=True, image_base=0):
-        """encoder_decoder.py:250-304 (mode='whole'), post-loop epilogue fused into one kernel:
+    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None):
+        """``hints`` (b,Hh,Wh) uint8 in the frame of ``img``: see ``ddim_sample``; slide mode raises ValueError.
+        encoder_decoder.py:250-304 (mode='whole'), post-loop epilogue fused into one kernel:
         the (1,K,H,W) resized scores / probabilities of the reference are never materialised.  ``img`` may hold
         b >= 1 images (§8 f4): the loop runs once on the whole batch with independent noise per image, and every
         image gets the crop / rescale / flip of its OWN ``img_meta`` entry (one epilogue launch per distinct geometry)."""
         from ..engine import seg_postprocess
+        hk = {} if hints is None else dict(hints=hints)
         if self._mode() == 'slide':
+            if hints is not None:
+                raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
             if img_meta and any(self._epilogue_args(m, rescale) != self._epilogue_args(img_meta[0], rescale) for m in img_meta):
                 raise ValueError('slide inference: the images of a batch must share img_shape / ori_shape / flip')
             fl = self._epilogue_args(img_meta[0], rescale)[2] if img_meta else None
@@ -386,9 +429,9 @@ class DDP(nn.Module, _SamplerMixin):
             return list(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base)).cpu().numpy().astype('int64'))
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_meta, **self._seed_kw(image_base))
+            out = self.ddim_sample(x, img_meta, **self._seed_kw(image_base), **hk)
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_meta, **self._seed_kw(image_base))
+            out = self.ddpm_sample(x, img_meta, **self._seed_kw(image_base), **hk)
         else:
             raise NotImplementedError
         b = out.shape[0]
@@ -405,8 +448,9 @@ class DDP(nn.Module, _SamplerMixin):
             res.append(seg[0].cpu().numpy().astype('int64'))
         return res
 
-    def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, **kwargs):
-        """base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
+    def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, hints=None, **kwargs):
+        """``hints``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
+        base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
         augmentation lists the test pipeline produces."""
         if return_loss:
             raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
@@ -414,11 +458,13 @@ class DDP(nn.Module, _SamplerMixin):
             if len(img) != 1:
                 if img_metas is None or len(img_metas) != len(img):
                     raise ValueError(f'num of augmentations ({len(img)}) != num of image meta ({0 if img_metas is None else len(img_metas)})')
-                return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}))
+                return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
+                                     **({} if hints is None else {'hints': hints}))
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
-        return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}))
+        return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
+                                **({} if hints is None else {'hints': hints}))
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')

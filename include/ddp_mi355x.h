@@ -107,6 +107,11 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                      _GATHER_GUESS_ZERO as the ddim chain does.  Nothing new is carved: ddp_query_workspace and
                                      ddp_query_const_workspace return the bytes of the cfg without the flag.  Clear: launches, workspace
                                      sizes and outputs are unchanged */,
+       DDP_FLAG_X0_HINTS = 16384 /* model surface, seg and depth through ddp_sample, both samplers, both engines, every route: where the
+                                    caller knows the answer, that is fed back as x0 at every step in place of the model's own
+                                    prediction - see "x0 hints" below.  Refused (DDP_E_BADCFG) for bev, by ddp_sample_fcn and its
+                                    workspace query, together with DDP_FLAG_FORCE_X0 and for seg with 256 classes; ddp_head_forward
+                                    ignores it.  Clear: launches, workspace sizes and outputs are unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
@@ -305,6 +310,34 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * rule.  The buffer holds the (B, r, Cm, h, w) start noise of the LAST call until the next one.
  * Extra launches with the flag set: one k_noise_fill_nchw per call; per noise-adding ddpm step one k_noise_fill_tok in place of the
  * NCHW -> token-major transpose. */
+
+/* x0 hints (DDP_FLAG_X0_HINTS, seg and depth; csrc/ddp_hints.hip).  The replacement form of conditioning: the loop's only feedback
+ * into the next step is the x0 projection (segmentors/ddp.py:235-239, depther/ddp.py:240-246), and at the pixels where the caller
+ * knows the answer that answer is projected instead of the model's prediction.  The HINT MAP is per image at the map resolution,
+ * (B, h, w); all r replicas and all K steps share it:
+ *   seg    uint8.  A value < num_classes is fed back as the class in place of the argmax (ddp.py:235); any value >= num_classes
+ *          (255 by convention) leaves the pixel free.  num_classes <= 255 (256 classes are refused: no free value would be left)
+ *   depth  float32 metric depth.  A finite value > 0 replaces depth_pred in the x0 normalisation only (depther/ddp.py:240-241, with
+ *          the clamp of :224 - a hint outside [min_depth, max_depth] clamps like a prediction would); 0, a negative value, NaN or
+ *          +-inf leaves the pixel free
+ * What ddp_sample returns stays the model's own prediction (scores / depth), and the step record (DDP_FLAG_STEP_RECORD,
+ * DDP_FLAG_RECORD_X0) keeps the model's own decision of every step: a caller sees where the model disagrees with its hints.  Hints
+ * act through the update, i.e. from the SECOND step on: timesteps = 1 is accepted and the hints have no effect there.
+ * Sizes and places, as formulas of the cfg - two buffers, each rounded up to 256 bytes; ddp_query_workspace grows by exactly
+ * round256(hint_bytes) + round256(row_bytes), every other offset and ddp_query_const_workspace are those of the cfg without the flag:
+ *   hint_bytes = batch * h * w * (seg: 1, depth: 4)              the caller-written hint map, carved IMMEDIATELY IN FRONT of the
+ *                seeded-noise buffer; it starts at
+ *                ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)]
+ *                                         - [SEEDED_NOISE: round256(noise_bytes)] - round256(hint_bytes)
+ *   row_bytes  = batch * randsteps * h * w * (seg: 1, depth: 4)  library-private, immediately in front of the hint map: the hints per
+ *                row m = (b * r + rr) * N + n (the order of the x0 trace) with the "free" encodings normalised (seg 255, depth 0)
+ * The library never initialises the hint map: the caller writes it (all free = every byte 255 / every float 0) before the first
+ * ddp_sample; ddp_amd.engine.DDPEngine does so whenever it allocates the workspace or changes the geometry.  The kernels read the
+ * caller's buffer from device memory when they run, so a captured graph picks up new hints without being captured again.
+ * Extra launches with the flag set: one k_hint_rows_seg / k_hint_rows_depth per call, first.  seg runs the teacher-forcing
+ * instantiations of its decision kernels (the ones DDP_FLAG_FORCE_X0 runs, which have no non-temporal variant) with the row buffer
+ * as the forced class and "keep the argmax where the forced value is >= num_classes" semantics; depth the same kernels as without
+ * the flag, which read one more float per pixel and step. */
 
 /* ---- finer-grained entry points (unit tests, and the decode_head plugin surface) ------------- */
 

@@ -4,6 +4,7 @@ variants of one workload in ONE process (round 6: the fused BEV step boundary ti
 next while every tagged kernel took the same time - which calls are slow, and what does the clock do then?).
 
   python scripts/call_times.py --workload bev_fusion_k3_8x200x200 fused= unfused=DDP_TAIL_FUSED=0 --calls 40 --blocks 3
+  python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= free=DDP_X0_HINTS=free sparse=DDP_X0_HINTS=sparse
 
 Per variant and block: the sorted per-call HIP-event times, their median / min / max, the mean power and clock over the block."""
 import argparse
@@ -46,7 +47,19 @@ def main():
         env = dict(e.split('=', 1) for e in envs.split(',') if e)
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
-        engines[name] = DDPEngine(sd, task, **kw)
+        # DDP_X0_HINTS=free | sparse in a variant's environment: DDP_FLAG_X0_HINTS set, with every pixel free or ~5 % of the pixels hinted
+        # (seg: seeded classes, depth: seeded depths inside the range) - a switch of this script, not of the library
+        hk = os.environ.get('DDP_X0_HINTS')
+        engines[name] = DDPEngine(sd, task, **(dict(x0_hints=True) if hk else {}), **kw)
+        if hk == 'sparse':
+            g = torch.Generator().manual_seed(7)
+            shape = (wl['batch'], wl['h'], wl['w'])
+            on = torch.rand(shape, generator=g) < 0.05
+            if task == 'seg':
+                hints = torch.where(on, torch.randint(0, wl['num_classes'], shape, generator=g), torch.tensor(255)).to(torch.uint8)
+            else:
+                hints = torch.where(on, torch.rand(shape, generator=g) * 70.0 + 1.0, torch.tensor(0.0))
+            engines[name].set_hints(hints.to(dev))
         engines[name].prepare()
         engines[name].sample(dx, dn)
         for k, o in old.items():
