@@ -46,6 +46,8 @@ def _run_batch(model, data, device, batch_indices=None, **kwargs):
     data['img'] = _to_device(data['img'], device)
     if data.get('hints') is not None:      # x0 hints (DDP.forward(hints=)): in the frame of img, on its device; passed through with **data
         data['hints'] = _to_device(data['hints'], device)
+    if data.get('prior') is not None:      # prior start (DDP.forward(prior=, t_start=)): likewise
+        data['prior'] = _to_device(data['prior'], device)
     # seeded noise (model.noise_seed set): image i of the batch draws the noise of dataset index batch_indices[0] + i, whatever
     # samples_per_gpu is and whichever rank the batch landed on (a batch_sampler of a sequential or strided sampler hands out
     # increasing indices; the first one names the batch)

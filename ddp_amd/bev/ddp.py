@@ -79,8 +79,12 @@ class DDP(nn.Module, _SamplerMixin):
                                       nn.Linear(tmp_channels * 4, tmp_channels * 4))
 
     @torch.no_grad()
-    def ddim_sample(self, x, head, noise=None, return_steps=False, image_base=0, call=0, hints=None):
-        """``hints``: not built for the bev sampler (ValueError; DDP_FLAG_X0_HINTS is a seg / depth flag).
+    def ddim_sample(self, x, head, noise=None, return_steps=False, image_base=0, call=0, hints=None, prior=None, t_start=None):
+        """``prior`` (b,Hp,Wp) int32 bit words (bit c = class c present) with ``t_start`` in (0, 1] (call-time only;
+        DDP_FLAG_PRIOR_START): the chain starts from the prior map noised to ``t_start`` instead of from pure noise, and the K steps
+        divide [0, t_start]; brought to (h,w) with nearest resampling.  ``t_start`` alone: the same time grid on the given / drawn
+        ``noise`` as the start map.
+        ``hints``: not built for the bev sampler (ValueError; DDP_FLAG_X0_HINTS is a seg / depth flag).
         With ``self.noise_seed`` set and no ``noise``: image i of the batch gets the noise of (noise_seed, image_base + i, call).
         ``return_steps``: -> (out, record (K,b,r,head_h,head_w) int32 bit words - bit c = the step's prob_c > threshold
         (fusion_models/ddp.py:290) -, disagreement (b,head_h,head_w) - the fraction of recorded bits that differ from
@@ -91,6 +95,8 @@ class DDP(nn.Module, _SamplerMixin):
         if not x0.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')
         b, c, h, w = x0.shape
+        self._check_t_start(prior, t_start)
+        ts = 1.0 if t_start is None else float(t_start)
         seeded = noise is None and self.noise_seed is not None
         if noise is None and not seeded:
             noise = torch.randn((b, self.randsteps, 256, h, w), device=x0.device)
@@ -106,13 +112,15 @@ class DDP(nn.Module, _SamplerMixin):
                              bev_output_scope=head.grid_transform['output_scope'],
                              bev_prescale=getattr(head, 'prescale_factor', 1.0),
                              bev_seg_kernel=getattr(head, 'seg_conv_kernel', 1), device=x0.device,
-                             record_steps=return_steps, seeded_noise=seeded)
+                             record_steps=return_steps, seeded_noise=seeded, prior_start=prior is not None, t_start=ts)
         ver = sum(p._version for p in head.parameters())
         # everything of the head that shapes the engine: its identity, grid transform (scopes, prescale) and conv_seg kernel
         gt = head.grid_transform
         hkey = (id(head), repr(gt['input_scope']), repr(gt['output_scope']), getattr(head, 'prescale_factor', 1.0),
-                getattr(head, 'seg_conv_kernel', 1), bool(return_steps), seeded)
+                getattr(head, 'seg_conv_kernel', 1), bool(return_steps), seeded, prior is not None, ts)
         eng = self._get_engine((b, c, h, w, str(x0.device), self.timesteps, self.randsteps, ver) + hkey, factory)
+        if prior is not None:
+            eng.set_prior(self._prior_map(prior, b, h, w, torch.int32).to(x0.device))
         if seeded:
             out = eng.sample(x0.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
         else:

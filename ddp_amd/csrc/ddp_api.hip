@@ -100,6 +100,10 @@ struct Layout {
   // DDP_FLAG_X0_HINTS: the caller-written hint map (B, N) - seg uint8, depth fp32 - and its per-row form (M0), written by k_hint_rows_*
   void* hint_map = nullptr;
   void* hint_rows = nullptr;
+  // DDP_FLAG_PRIOR_START: the caller-written prior map (B, N) - seg uint8, depth fp32, bev uint32 - and the start map (B, r, Cm, h, w)
+  // k_prior_start_* writes (without DDP_FLAG_SEEDED_NOISE; with it seed_noise is the start map, mixed in place)
+  void* prior_map = nullptr;
+  float* prior_start = nullptr;
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
@@ -186,13 +190,18 @@ int validate(const ddp_cfg* c) {
     set_error("num_classes %d out of range [1,256]", c->num_classes);
     return DDP_E_BADCFG;
   }
+  if (c->task == DDP_TASK_BEV && c->num_classes > 32 && (c->flags & DDP_FLAG_PRIOR_START)) {
+    set_error("DDP_FLAG_PRIOR_START: a bev prior is one uint32 bit word per pixel (num_classes %d > 32)", c->num_classes);
+    return DDP_E_BADCFG;
+  }
   if (c->task == DDP_TASK_BEV && c->num_classes > 32) {
     set_error("bev supports at most 32 classes");
     return DDP_E_BADCFG;
   }
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
                    DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
-                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN | DDP_FLAG_X0_HINTS)) {
+                   DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN | DDP_FLAG_X0_HINTS |
+                   DDP_FLAG_PRIOR_START)) {
     set_error("unknown flags 0x%x", c->flags);
     return DDP_E_BADCFG;
   }
@@ -470,6 +479,12 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   }
   // seeded start noise: immediately in front of the step-record buffers (the end of the workspace without them), so that the record
   // and the map stay the last of the workspace and every other offset is the one of the cfg without the flag
+  // prior start: the start map (only without DDP_FLAG_SEEDED_NOISE), then the caller's prior map, in front of the x0-hint buffers
+  // (include/ddp_mi355x.h, "prior start")
+  if (c->flags & DDP_FLAG_PRIOR_START) {
+    if (!(c->flags & DDP_FLAG_SEEDED_NOISE)) o->prior_start = cv.take(o->M0 * o->Cm);
+    o->prior_map = cv.take(c->task == DDP_TASK_SEG ? (size_t(o->B) * o->N + 3) / 4 : size_t(o->B) * o->N);
+  }
   // x0 hints: the private row buffer, then the caller's map immediately in front of the seeded-noise buffer (include/ddp_mi355x.h)
   if (c->flags & DDP_FLAG_X0_HINTS) {
     const bool bytes1 = c->task == DDP_TASK_SEG;
@@ -1628,6 +1643,29 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     DDP_TRY(seeded_start_noise(key, o.seed_noise, o.B, size_t(o.r) * o.Cm * o.N, st));
     d_noise = o.seed_noise;
   }
+  // DDP_FLAG_PRIOR_START: the loop's first read comes from alpha(t_start) x0(prior) + sigma(t_start) eps, eps = what d_noise is by
+  // now.  The prior is read from device memory when the kernel runs (a captured graph replays this launch on the buffer's current
+  // content); the seeded-noise buffer is mixed in place
+  if (o.prior_map) {
+    PriorStartArgs pa;
+    pa.prior = o.prior_map;
+    pa.table = cfg->task == DDP_TASK_SEG ? o.lut : weights->embedding;
+    pa.eps = d_noise;
+    pa.out = seeded ? o.seed_noise : o.prior_start;
+    pa.task = cfg->task;
+    pa.B = o.B;
+    pa.r = o.r;
+    pa.N = o.N;
+    pa.num_classes = o.Kc;
+    pa.alpha = steps[0].alpha;
+    pa.sigma = steps[0].sigma;
+    pa.bit_scale = cfg->bit_scale;
+    pa.min_depth = cfg->min_depth;
+    pa.max_depth = cfg->max_depth;
+    prof_begin(TAG_GENERIC, st);
+    DDP_TRY(recorded(launch_prior_start(pa, st), st));
+    d_noise = pa.out;
+  }
   // loop-invariant half of the concat-conv: xproj = W_x x + b  (ddp.py:223-224 with the x columns hoisted)
   if (p.head7) {
     // (inside the first step's head)
@@ -1661,11 +1699,12 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
 
 int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float* d_feat, const float* d_temb,
                      float* d_out, void* d_workspace, void* stream) {
-  // one decoder pass has no x0 feedback: DDP_FLAG_X0_HINTS is ignored (the buffers it carves lie behind everything used here)
+  // one decoder pass has no x0 feedback and no start map: DDP_FLAG_X0_HINTS and DDP_FLAG_PRIOR_START are ignored (the buffers they
+  // carve lie behind everything used here)
   ddp_cfg no_hints;
-  if (cfg && (cfg->flags & DDP_FLAG_X0_HINTS)) {
+  if (cfg && (cfg->flags & (DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START))) {
     no_hints = *cfg;
-    no_hints.flags &= ~DDP_FLAG_X0_HINTS;
+    no_hints.flags &= ~(DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START);
     cfg = &no_hints;
   }
   DDP_TRY(validate(cfg));
@@ -2590,6 +2629,10 @@ int validate_fcn_loop(const ddp_cfg* cfg, int num_convs, int dilation) {
   }
   if (cfg->flags & DDP_FLAG_X0_HINTS) {
     set_error("sample_fcn: DDP_FLAG_X0_HINTS is built for ddp_sample only (the FCN loop takes no hints)");
+    return DDP_E_BADCFG;
+  }
+  if (cfg->flags & DDP_FLAG_PRIOR_START) {
+    set_error("sample_fcn: DDP_FLAG_PRIOR_START is built for ddp_sample only (the FCN loop starts from noise)");
     return DDP_E_BADCFG;
   }
   if (num_convs < 0 || num_convs > 8 || dilation < 1) {

@@ -445,4 +445,18 @@ int launch_u_noise(float* ubuf, const float* noise, const float* wm, int M, floa
 // "free" encodings normalised (seg: >= num_classes -> 255; depth: 0, negative, NaN, +-inf -> 0).  `rows` holds whole 256-byte granules
 int launch_hint_rows(const void* map, void* rows, int task, int B, int r, int N, int num_classes, hipStream_t st);
 
+// ---- ddp_prior_start.hip (DDP_FLAG_PRIOR_START) -----------------------------------------------------
+// out (B, r, Cm, N) = alpha x0(prior) + sigma eps (seg / bev; Cm = 256) or alpha x0(prior) + eps / sigma (depth; Cm = 1), eps
+// (B, r, Cm, N) - which may be `out` itself.  prior (B, N): seg uint8, depth fp32 metric depth, bev uint32 bit words.  table: seg the
+// x0 table of ddp_prepare (num_classes + 1, 256), bev the embedding (num_classes + 1, 256), depth unused
+struct PriorStartArgs {
+  const void* prior;
+  const float* table;
+  const float* eps;
+  float* out;
+  int task, B, r, N, num_classes;
+  float alpha, sigma, bit_scale, min_depth, max_depth;
+};
+int launch_prior_start(const PriorStartArgs& a, hipStream_t st);
+
 }  // namespace ddp

@@ -98,8 +98,12 @@ class DDP(nn.Module, _SamplerMixin):
                 for a, b in schedule.get_sampling_timesteps(self.timesteps, self.time_difference, 0.0)]
 
     @torch.no_grad()
-    def sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None):
-        """``hints`` (b,Hh,Wh) float32 metric depth in the frame of the network input (call-time only; DDP_FLAG_X0_HINTS) - sparse
+    def sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None, prior=None, t_start=None):
+        """``prior`` (b,Hp,Wp) float32 metric depth in the frame of the network input with ``t_start`` in (0, 1] (call-time only;
+        DDP_FLAG_PRIOR_START): the chain starts from the prior depth (the previous frame, the coarse scale; 0, negative, NaN or inf:
+        the middle of the range) noised to ``t_start`` instead of from pure noise, and the K steps divide [0, t_start]; resampled to
+        (h,w) with nearest.  ``t_start`` alone: the same time grid on the given / drawn ``noise`` as the start map.
+        ``hints`` (b,Hh,Wh) float32 metric depth in the frame of the network input (call-time only; DDP_FLAG_X0_HINTS) - sparse
         LiDAR depth turns prediction into completion: a finite value > 0 replaces ``depth_pred`` in the x0 normalisation of every
         step (depther/ddp.py:240-241, clamped like a prediction); 0, negative, NaN or inf leaves the pixel free.  Resampled to (h,w)
         with NEAREST (the rule of segmentors/ddp.py:149; bilinear would average the holes of a sparse map into their neighbours).
@@ -110,6 +114,8 @@ class DDP(nn.Module, _SamplerMixin):
         if not x.is_cuda:
             raise RuntimeError('ddp_amd has no CPU path: features must live on an MI355X (HIP) device')
         b, c, h, w = x.shape
+        self._check_t_start(prior, t_start)
+        ts = 1.0 if t_start is None else float(t_start)
         seeded = noise is None and self.noise_seed is not None
         if noise is None and not seeded:
             noise = torch.randn((b, self.randsteps, 1, h, w), device=x.device)
@@ -133,14 +139,17 @@ class DDP(nn.Module, _SamplerMixin):
                              timesteps=self.timesteps, bit_scale=self.bit_scale, time_difference=self.time_difference,
                              min_depth=self.min_depth, max_depth=self.max_depth, depth_scale_up=su, depth_use_eps=ue,
                              head_min_depth=hmin, head_max_depth=hmax, depth_bins=bins, depth_norm=norm, device=x.device,
-                             record_steps=return_steps, seeded_noise=seeded, x0_hints=hints is not None)
+                             record_steps=return_steps, seeded_noise=seeded, x0_hints=hints is not None,
+                             prior_start=prior is not None, t_start=ts)
         # keyed without the geometry: a new (b, h, w) re-uses the engine through set_geometry (no weight repacking)
         bins_key = None if bins is None else (getattr(head, 'bins_strategy', None), head.n_bins, norm)
         eng = self._get_engine(('depth', str(x.device), self.timesteps, self.randsteps, self.bit_scale, self.time_difference,
                                 self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key, bool(return_steps), seeded,
-                                hints is not None), factory, geometry=(b, h, w))
+                                hints is not None, prior is not None, ts), factory, geometry=(b, h, w))
         if hints is not None:
             eng.set_hints(self._hint_map(hints, b, h, w, torch.float32).to(x.device))
+        if prior is not None:
+            eng.set_prior(self._prior_map(prior, b, h, w, torch.float32).to(x.device))
         if seeded:
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
         else:
@@ -172,10 +181,10 @@ class DDP(nn.Module, _SamplerMixin):
         if mode == 'slide':
             raise NotImplementedError("test_cfg.mode='slide' (the reference raises here as well: encoder_decoder.py:186-187)")
 
-    def _low_res(self, img, img_metas, image_base=0, call=0, hints=None):
+    def _low_res(self, img, img_metas, image_base=0, call=0, hints=None, prior=None, t_start=None):
         """backbone + neck + the K-step loop: the (b,1,h/4,w/4) map every epilogue below starts from."""
         return self.sample(self.extract_feat(img)[0], img_metas, **self._seed_kw(image_base, call),
-                           **({} if hints is None else {'hints': hints}))
+                           **({} if hints is None else {'hints': hints}), **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
 
     def _post(self, maps, flips, size):
         from ..engine import depth_postprocess
@@ -203,30 +212,34 @@ class DDP(nn.Module, _SamplerMixin):
             return direction
         return None
 
-    def inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None):
-        """``hints``: see ``sample``.
+    def inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None, prior=None, t_start=None):
+        """``hints``, ``prior``, ``t_start``: see ``sample``.
         encoder_decoder.py:168-196 (mode 'whole'): ``whole_inference`` with the test-time flip undone, the flip folded into
         the same kernel (it reads the mirrored source pixel)."""
         self._check_mode()
         if img_meta:
             ori_shape = img_meta[0]['ori_shape']
             assert all(m['ori_shape'] == ori_shape for m in img_meta)
-        d = self._low_res(img, img_meta, **self._seed_kw(image_base, call), **({} if hints is None else {'hints': hints}))
+        d = self._low_res(img, img_meta, **self._seed_kw(image_base, call), **({} if hints is None else {'hints': hints}),
+                          **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
         return self._post([d], [self._flip_of(img_meta)], img.shape[2:] if rescale else d.shape[2:])
 
-    def simple_test(self, img, img_meta, rescale=True, image_base=0, hints=None):
+    def simple_test(self, img, img_meta, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
         """encoder_decoder.py:198-209: list (batch) of (1,H,W) float32 arrays.  ``img`` may hold b >= 1 images (independent
-        noise per image; the reference's sampler is b = 1 only, depther/ddp.py:232).  ``hints`` (b,Hh,Wh) float32: see ``sample``."""
+        noise per image; the reference's sampler is b = 1 only, depther/ddp.py:232).  ``hints`` (b,Hh,Wh) float32, ``prior`` (b,Hp,Wp)
+        float32 with ``t_start``: see ``sample``."""
         return list(self.inference(img, img_meta, rescale, **self._seed_kw(image_base),
-                                   **({} if hints is None else {'hints': hints})).cpu().numpy())
+                                   **({} if hints is None else {'hints': hints}), **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start})).cpu().numpy())
 
-    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None):
-        """``hints`` are not built for test-time augmentation (ValueError).
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
+        """``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
         encoder_decoder.py:210-229: mean over the augmentations (KITTI / NYU test pipelines: plain + horizontal flip,
         depth/configs/_base_/datasets/kitti.py:30-33).  Every augmentation runs the full sampling loop with its own noise; only the
         LOW-RESOLUTION maps are kept and ONE kernel does clamp -> resize -> flip-undo -> running sum -> / n per output pixel."""
         if hints is not None:
             raise ValueError('hints are not built for aug_test (every augmentation has its own frame)')
+        if prior is not None or t_start is not None:
+            raise ValueError('prior / t_start are not built for aug_test (every augmentation has its own frame)')
         assert rescale, 'aug_test rescales every augmentation back to the network input'
         self._check_mode()
         sizes = {tuple(img.shape[2:]) for img in imgs}

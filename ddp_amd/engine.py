@@ -186,6 +186,9 @@ class _SeededNoise:
         graph replay) generated; valid until the next call."""
         if not self.seeded:
             raise _lib.DdpError('last_noise() needs an engine built with seeded_noise=True')
+        if self.cfg.flags & _lib.FLAG_PRIOR_START:
+            raise _lib.DdpError('prior_start engine: the seeded-noise buffer is mixed in place and holds the start map after the '
+                                'call - use last_start() instead')
         if not getattr(self, '_sampled', False):
             raise _lib.DdpError('no noise yet: call sample() first')
         c = self.cfg
@@ -209,8 +212,16 @@ class DDPEngine(_SeededNoise):
                  weights=None, gemm=None, fused_layer=None, fused_prologue=None, lib_path=None, record_x0=False,
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
-                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None, x0_hints=False):
-        """``x0_hints`` (DDP_FLAG_X0_HINTS; seg and depth): where the caller knows the answer it is fed back as x0 at every step in
+                 bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None, x0_hints=False,
+                 prior_start=False, t_start=1.0):
+        """``prior_start`` (DDP_FLAG_PRIOR_START; all three tasks): the chain starts from the caller's prior map noised to ``t_start``
+        instead of from pure noise - ``set_prior()`` / ``prior_view()`` / ``clear_prior()``, ``SampleGraph.replay(prior=)``,
+        ``last_start()``.  seg: (B, h, w) uint8 classes, a value >= num_classes is the ignore row; depth: (B, h, w) float32 metric
+        depth, 0 / negative / NaN / inf is the middle of the range; bev: (B, h, w) int32 bit words, bit c = class c present.  The
+        engine clears the prior (seg 255, depth 0, bev 0) whenever it allocates the workspace and on every ``set_geometry``.
+        ``t_start`` in (sample_range0, 1]: the time the K steps begin at (``schedule.get_sampling_timesteps``); independent of
+        ``prior_start`` - a flag-clear engine with ``t_start < 1`` runs on whatever start map the caller passes as ``noise``.
+        ``x0_hints`` (DDP_FLAG_X0_HINTS; seg and depth): where the caller knows the answer it is fed back as x0 at every step in
         place of the model's own prediction - ``set_hints()`` / ``hints_view()`` / ``clear_hints()``, ``SampleGraph.replay(hints=)``.
         seg: (B, h, w) uint8 classes, a value >= num_classes (255) leaves the pixel free; depth: (B, h, w) float32 metric depth, 0 /
         negative / NaN / inf leaves it free.  Unset hints are no hints: the engine sets everything free whenever it allocates or
@@ -316,12 +327,17 @@ class DDPEngine(_SeededNoise):
             if force_x0:
                 raise ValueError('x0_hints cannot be combined with force_x0 (DDP_FLAG_X0_HINTS / DDP_FLAG_FORCE_X0)')
             cfg.flags |= _lib.FLAG_X0_HINTS
+        if prior_start:
+            if task == 'bev' and num_classes > 32:
+                raise ValueError('prior_start: a bev prior is one 32-bit word per pixel (DDP_FLAG_PRIOR_START, num_classes <= 32)')
+            cfg.flags |= _lib.FLAG_PRIOR_START
+        self.t_start = float(t_start)
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
         cfg.bit_scale, cfg.min_depth, cfg.max_depth, cfg.threshold = bit_scale, min_depth, max_depth, threshold
         self.cfg = cfg
         self.sampler = sampler
-        recs = schedule.step_records(task, timesteps, time_difference, sample_range0, noise_schedule, sampler)
+        recs = schedule.step_records(task, timesteps, time_difference, sample_range0, noise_schedule, sampler, t_start=self.t_start)
         self.steps = (_lib.DdpStep * timesteps)()
         for i, r in enumerate(recs):
             for k, v in r.items():
@@ -337,6 +353,7 @@ class DDPEngine(_SeededNoise):
         self.geometry_changes = 0
         self._init_key()
         self.clear_hints(_if_any=True)
+        self.clear_prior(_if_any=True)
 
     def _workspace_bytes(self):
         nbytes = C.c_size_t(0)
@@ -382,6 +399,54 @@ class DDPEngine(_SeededNoise):
         with torch.cuda.device(self.device):
             v.fill_(255 if v.dtype == torch.uint8 else 0)
 
+    # ---- DDP_FLAG_PRIOR_START ------------------------------------------------------------------
+    def _prior_places(self):
+        c = self.cfg
+        if not c.flags & _lib.FLAG_PRIOR_START:
+            raise _lib.DdpError('the prior map and last_start() need an engine built with prior_start=True')
+        return prior_start_places(c, self._workspace_bytes())
+
+    def prior_view(self):
+        """(B, h, w) VIEW of the caller-written prior map inside the workspace - uint8 (seg), float32 (depth) or int32 bit words
+        (bev; the C side's uint32); the kernel reads it when it runs (a captured graph picks up what it holds at replay).  Place:
+        include/ddp_mi355x.h, "prior start"."""
+        c = self.cfg
+        off, nbytes, _, _ = self._prior_places()
+        v = self.workspace.view(torch.uint8)[off:off + nbytes]
+        dtype = {_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32}[c.task]
+        return (v if dtype == torch.uint8 else v.view(dtype)).view(c.batch, c.h, c.w)
+
+    def set_prior(self, prior):
+        """copy ``prior`` (B, h, w) - uint8 for seg, float32 for depth, int32 for bev, on the engine's device - into the prior map
+        (stream-ordered)"""
+        v = self.prior_view()
+        if not isinstance(prior, torch.Tensor) or prior.dtype != v.dtype:
+            raise _lib.DdpError(f'prior must be a {v.dtype} tensor, got {getattr(prior, "dtype", type(prior))}')
+        if tuple(prior.shape) != tuple(v.shape):
+            raise _lib.DdpError(f'prior must have shape {tuple(v.shape)} (batch, h, w), got {tuple(prior.shape)}')
+        if prior.device != self.device:
+            raise _lib.DdpError(f'engine lives on {self.device}: the prior is on {prior.device}')
+        with torch.cuda.device(self.device):
+            v.copy_(prior, non_blocking=True)
+
+    def clear_prior(self, _if_any=False):
+        """no prior knowledge anywhere: seg 255 (the ignore row), depth 0 (the middle of the range), bev 0 (no class present)"""
+        if _if_any and not self.cfg.flags & _lib.FLAG_PRIOR_START:
+            return
+        v = self.prior_view()
+        with torch.cuda.device(self.device):
+            v.fill_(255 if v.dtype == torch.uint8 else 0)
+
+    def last_start(self):
+        """(B, r, Cm, h, w) float32 VIEW of the start map the LAST sample() call (or graph replay) formed from the prior and its
+        noise; valid until the next call.  (With ``seeded_noise`` this is the seeded-noise buffer, mixed in place.)"""
+        c = self.cfg
+        _, _, off, nbytes = self._prior_places()
+        if not getattr(self, '_sampled', False):
+            raise _lib.DdpError('no start map yet: call sample() first')
+        cm = 1 if c.task == _lib.TASK_DEPTH else 256
+        return self.workspace.view(torch.uint8)[off:off + nbytes].view(torch.float32).view(c.batch, c.randsteps, cm, c.h, c.w)
+
     # ------------------------------------------------------------------------------------------
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -424,6 +489,7 @@ class DDPEngine(_SeededNoise):
         self._x0_set = False       # force_x0: the decisions buffer belongs to the geometry region
         self._sampled = False      # (so do the step record and the disagreement map)
         self.clear_hints(_if_any=True)   # (and the hint map: another geometry or another buffer - unset hints are no hints)
+        self.clear_prior(_if_any=True)   # (and the prior map)
         return self
 
     def out_shape(self):
@@ -577,6 +643,29 @@ def _round256(n):
     return (n + 255) // 256 * 256
 
 
+def prior_start_places(cfg, workspace_bytes):
+    """(prior_offset, prior_bytes, start_offset, start_bytes) of include/ddp_mi355x.h ("prior start"), in bytes from the start of a
+    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): THE host-side derivation of where DDP_FLAG_PRIOR_START's buffers lie.
+    With DDP_FLAG_SEEDED_NOISE the start map is the seeded-noise buffer."""
+    seg, depth = cfg.task == _lib.TASK_SEG, cfg.task == _lib.TASK_DEPTH
+    n = cfg.batch * cfg.h * cfg.w
+    prior_bytes = n * (1 if seg else 4)
+    start_bytes = n * cfg.randsteps * (1 if depth else 256) * 4
+    end = workspace_bytes
+    if cfg.flags & _lib.FLAG_STEP_RECORD:
+        rec, smap = step_record_sizes(cfg)
+        end -= _round256(rec) + _round256(smap)
+    seeded_off = None
+    if cfg.flags & _lib.FLAG_SEEDED_NOISE:
+        end -= _round256(start_bytes)
+        seeded_off = end
+    if cfg.flags & _lib.FLAG_X0_HINTS:
+        end -= _round256(n * (1 if seg else 4)) + _round256(n * cfg.randsteps * (1 if seg else 4))
+    prior_off = end - _round256(prior_bytes)
+    start_off = seeded_off if seeded_off is not None else prior_off - _round256(start_bytes)
+    return prior_off, prior_bytes, start_off, start_bytes
+
+
 def step_record_view(workspace, base, cfg):
     dtype = {_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32}[cfg.task]
     nbytes = step_record_sizes(cfg)[0]
@@ -603,8 +692,10 @@ class SampleGraph:
         self.workspace = engine.workspace
         self.workspace_ptr = engine.workspace.data_ptr()
 
-    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None, hints=None):
-        """``hints`` (x0_hints engines): written to the engine's hint map in front of the launch (``DDPEngine.set_hints``); None: the
+    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None, hints=None, prior=None):
+        """``prior`` (prior_start engines): written to the engine's prior map in front of the launch (``DDPEngine.set_prior``); None:
+        the graph runs on what the map holds.
+        ``hints`` (x0_hints engines): written to the engine's hint map in front of the launch (``DDPEngine.set_hints``); None: the
         graph runs on what the map holds.
         seeded engines: ``seed`` / ``image_base`` / ``call`` given here replace those words of the engine's device key (stream-
         ordered, in front of the launch); none given: the graph repeats the last key."""
@@ -631,6 +722,8 @@ class SampleGraph:
             eng._write_key(seed, image_base, None, call)
         if hints is not None:
             eng.set_hints(hints)
+        if prior is not None:
+            eng.set_prior(prior)
         self.graph.replay()
         return self.out
 
@@ -641,7 +734,10 @@ class FcnSamplerEngine(_SeededNoise):
 
     def __init__(self, state_dict, head, *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150, bit_scale=0.01,
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
-                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False, x0_hints=False):
+                 device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False, x0_hints=False,
+                 prior_start=False):
+        if prior_start:
+            raise ValueError('prior_start is built for ddp_sample only (DDP_FLAG_PRIOR_START): the FCN-head loop starts from noise')
         if x0_hints:
             raise ValueError('x0_hints is built for ddp_sample only (DDP_FLAG_X0_HINTS): the FCN-head loop takes no hints')
         self.lib = _lib.load(lib_path)

@@ -38,23 +38,28 @@ def gamma(t, ns=0.0002, ds=0.00025):
 NOISE_SCHEDULES = {'linear': beta_linear_log_snr, 'cosine': alpha_cosine_log_snr}
 
 
-def get_sampling_timesteps(timesteps, time_difference=1, sample_range0=0.0):
-    """[(t_now, t_next)] as python floats (ddp.py:204-213)."""
+def get_sampling_timesteps(timesteps, time_difference=1, sample_range0=0.0, t_start=1.0):
+    """[(t_now, t_next)] as python floats (ddp.py:204-213).  ``t_start``: the time the chain begins at (the reference: 1); the K
+    steps divide [sample_range0, t_start].  In this operation order t_start = 1.0 gives the reference's floats bit for bit."""
+    if not sample_range0 < t_start <= 1:
+        raise ValueError(f't_start {t_start!r} must lie in (sample_range0 = {sample_range0!r}, 1]')
+    span = t_start - sample_range0
     times = []
     for step in range(timesteps):
-        t_now = 1 - (step / timesteps) * (1 - sample_range0)
-        t_next = max(1 - (step + 1 + time_difference) / timesteps * (1 - sample_range0), sample_range0)
+        t_now = t_start - (step / timesteps) * span
+        t_next = max(t_start - (step + 1 + time_difference) / timesteps * span, sample_range0)
         times.append((t_now, t_next))
     return times
 
 
-def step_records(task, timesteps, time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim'):
-    """-> list of dicts with the fields of ``ddp_step``."""
+def step_records(task, timesteps, time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', t_start=1.0):
+    """-> list of dicts with the fields of ``ddp_step``.  ``t_start``: see ``get_sampling_timesteps`` (record 0 then holds alpha and
+    sigma of t_start, what DDP_FLAG_PRIOR_START noises the prior map with)."""
     if noise_schedule not in NOISE_SCHEDULES:
         raise ValueError(f'invalid noise schedule {noise_schedule}')
     log_snr_fn = NOISE_SCHEDULES[noise_schedule]
     recs = []
-    for t_now, t_next in get_sampling_timesteps(timesteps, time_difference, 0.0 if task != 'seg' else sample_range0):
+    for t_now, t_next in get_sampling_timesteps(timesteps, time_difference, 0.0 if task != 'seg' else sample_range0, t_start):
         tn = torch.tensor([t_now], dtype=torch.float32)
         tx = torch.tensor([t_next], dtype=torch.float32)
         r = dict(time_in=0.0, alpha=0.0, sigma=0.0, alpha_next=0.0, sigma_next=0.0, ddpm_c=0.0, ddpm_std=0.0,

@@ -88,6 +88,32 @@ class _SamplerMixin:
         m = F.interpolate(hints[:, None].float(), size=(h, w), mode='nearest')[:, 0]
         return m.to(dtype).contiguous()
 
+    @classmethod
+    def _prior_map(cls, prior, b, h, w, dtype):
+        """``prior`` (b, Hp, Wp) in the frame of the network input -> the (b, h, w) prior map of the engine (DDP_FLAG_PRIOR_START),
+        brought to the map resolution with nearest resampling by the rule of ``_hint_map`` (classes and bit words cannot be averaged;
+        a depth map's holes must not leak into their neighbours).  Integer maps are resampled by index, so that bit words above 2^24
+        survive."""
+        if isinstance(prior, (list, tuple)):
+            if len(prior) != 1:
+                raise ValueError('prior: test-time augmentation takes no prior (one prior map per batch, not one per augmentation)')
+            prior = prior[0]
+        if not torch.is_tensor(prior) or prior.dim() != 3 or prior.shape[0] != b:
+            raise ValueError(f'prior must be a (batch, H, W) tensor for a batch of {b} images, got '
+                             f'{tuple(prior.shape) if torch.is_tensor(prior) else type(prior)}')
+        if prior.dtype.is_floating_point:
+            return cls._hint_map(prior, b, h, w, dtype)
+        # F.interpolate(mode='nearest'): src = min(floor(dst * (in / out)), in - 1), the scale in float32 as ATen computes it
+        H, W = prior.shape[1:]
+        iy = (torch.arange(h, dtype=torch.float32) * torch.tensor(H / h, dtype=torch.float32)).floor().long().clamp(max=H - 1)
+        ix = (torch.arange(w, dtype=torch.float32) * torch.tensor(W / w, dtype=torch.float32)).floor().long().clamp(max=W - 1)
+        return prior[:, iy.to(prior.device)][:, :, ix.to(prior.device)].to(dtype).contiguous()
+
+    @staticmethod
+    def _check_t_start(prior, t_start):
+        if prior is not None and t_start is None:
+            raise ValueError('prior= needs t_start= (the time the prior map is noised to; 1.0 drowns it in noise)')
+
     def _get_engine(self, key, factory, geometry=None):
         cache = self.__dict__.setdefault('_engine_cache', {})
         ver = self._weights_version()
@@ -166,7 +192,7 @@ class DDP(nn.Module, _SamplerMixin):
         return times
 
     def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample',
-                    record_steps=False, seeded=False, hints=False):
+                    record_steps=False, seeded=False, hints=False, prior=False, t_start=None):
         from ..decode_heads.fcn_head_with_time import FCNHeadWithTime
         K = self.timesteps if timesteps is None else timesteps
         r = self.randsteps if randsteps is None else randsteps
@@ -175,10 +201,13 @@ class DDP(nn.Module, _SamplerMixin):
                       time_difference=self.time_difference, sample_range0=self.sample_range[0],
                       noise_schedule=self.noise_schedule, sampler=sampler, accumulation=acc, device=device,
                       record_steps=record_steps, seeded_noise=seeded)
+        ts = 1.0 if t_start is None else float(t_start)
         chain = bool(self.ddpm_chain) and sampler == 'ddpm'
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints))
+               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints), bool(prior), ts)
         if isinstance(self.decode_head, FCNHeadWithTime):
+            if prior or ts != 1.0:
+                raise ValueError('prior / t_start are built for the deformable head\'s sampler: the FCNHeadWithTime loop starts from noise')
             if hints:
                 raise ValueError('hints are built for the deformable head\'s sampler: the FCNHeadWithTime loop takes none')
             if chain:
@@ -194,7 +223,7 @@ class DDP(nn.Module, _SamplerMixin):
             from ..engine import DDPEngine, count_layers
             nl = count_layers(self.hot_path_state_dict())
             return DDPEngine(None, 'seg', h=h, w=w, feat_channels=256, weights=self._packed_weights(device, 'seg', nl),
-                             ddpm_chain=chain, x0_hints=bool(hints), **common)
+                             ddpm_chain=chain, x0_hints=bool(hints), prior_start=bool(prior), t_start=ts, **common)
         return self._get_engine(key, factory, geometry=(b, h, w))
 
     def hot_path_state_dict(self):
@@ -208,8 +237,13 @@ class DDP(nn.Module, _SamplerMixin):
             raise RuntimeError(f'expected {self.decode_head.in_channels[0]} feature channels, got {x.shape[1]}')
 
     @torch.no_grad()
-    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None):
-        """``hints`` (b,Hh,Wh) uint8 in the frame of the network input (call-time only; DDP_FLAG_X0_HINTS): a class < num_classes is
+    def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None, prior=None,
+                    t_start=None):
+        """``prior`` (b,Hp,Wp) uint8 in the frame of the network input with ``t_start`` in (sample_range[0], 1] (call-time only;
+        DDP_FLAG_PRIOR_START): the chain starts from the prior's classes (a value >= num_classes: the ignore row) noised to
+        ``t_start`` instead of from pure noise, and the K steps divide [sample_range[0], t_start]; resampled to (h,w) with nearest.
+        ``t_start`` alone: the same time grid on the given / drawn ``noise`` as the start map.
+        ``hints`` (b,Hh,Wh) uint8 in the frame of the network input (call-time only; DDP_FLAG_X0_HINTS): a class < num_classes is
         fed back as x0 at that pixel in place of the argmax at every step, any other value (255) leaves the pixel free; resampled to
         (h,w) with nearest.  The scores returned (and ``return_steps``' record) stay the model's own; ``timesteps=1``: no effect.
         x (b,256,h,w) -> (b,K,h,w).  ``noise`` (b,r,256,h,w) may be injected (parity tests);
@@ -219,12 +253,18 @@ class DDP(nn.Module, _SamplerMixin):
         disagreement (b,h,w) - the fraction of them that differ from the output's argmax)."""
         self._check_feature(x)
         b, c, h, w = x.shape
+        self._check_t_start(prior, t_start)
         hk = {} if hints is None else dict(hints=True)
+        if prior is not None or t_start is not None:
+            hk.update(prior=prior is not None, t_start=t_start)
         hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
+        pmap = None if prior is None else self._prior_map(prior, b, h, w, torch.uint8).to(x.device)
         if noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True, **hk)
             if hmap is not None:
                 eng.set_hints(hmap)
+            if pmap is not None:
+                eng.set_prior(pmap)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
@@ -232,20 +272,29 @@ class DDP(nn.Module, _SamplerMixin):
         eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, **hk)
         if hmap is not None:
             eng.set_hints(hmap)
+        if pmap is not None:
+            eng.set_prior(pmap)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     @torch.no_grad()
-    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0, hints=None):
-        """``hints``: as ``ddim_sample``"""
+    def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0, hints=None,
+                    prior=None, t_start=None):
+        """``hints``, ``prior``, ``t_start``: as ``ddim_sample``"""
         self._check_feature(x)
         b, c, h, w = x.shape
+        self._check_t_start(prior, t_start)
         hk = {} if hints is None else dict(hints=True)
+        if prior is not None or t_start is not None:
+            hk.update(prior=prior is not None, t_start=t_start)
         hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
+        pmap = None if prior is None else self._prior_map(prior, b, h, w, torch.uint8).to(x.device)
         if noise is None and step_noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True, **hk)
             if hmap is not None:
                 eng.set_hints(hmap)
+            if pmap is not None:
+                eng.set_prior(pmap)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
@@ -255,6 +304,8 @@ class DDP(nn.Module, _SamplerMixin):
         eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, **hk)
         if hmap is not None:
             eng.set_hints(hmap)
+        if pmap is not None:
+            eng.set_prior(pmap)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
@@ -329,8 +380,10 @@ class DDP(nn.Module, _SamplerMixin):
             out = tuple(img_meta[0]['ori_shape'][:2])
         return seg_slide_postprocess(scores, ys, xs, (ch, cw), img.shape[2:], keep, out, self.align_corners, flip, want)
 
-    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None):
+    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None, prior=None, t_start=None):
         """encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
+        if prior is not None or t_start is not None:
+            raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
         if hints is not None:
             raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
         return self._slide(img, img_meta, rescale, 'scores', **self._seed_kw(image_base, call))
@@ -358,8 +411,8 @@ class DDP(nn.Module, _SamplerMixin):
 
     AUG_CALL_STRIDE = 1 << 16            # seeded noise: augmentation a owns the call values [a * stride, (a + 1) * stride)
 
-    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None):
-        """``hints`` are not built for test-time augmentation (ValueError).
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
+        """``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
         With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
         index), so no two augmentations of an image share noise.
         encoder_decoder.py:306-331: mean of the per-augmentation probabilities (multi-scale / flip), then argmax.
@@ -370,6 +423,8 @@ class DDP(nn.Module, _SamplerMixin):
         from ..engine import seg_aug_postprocess
         if hints is not None:
             raise ValueError('hints are not built for aug_test (every augmentation has its own frame)')
+        if prior is not None or t_start is not None:
+            raise ValueError('prior / t_start are not built for aug_test (every augmentation has its own frame)')
         assert rescale, 'aug_test rescales every augmentation back to ori_shape'
         if len(imgs) != len(img_metas):
             raise ValueError(f'num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})')
@@ -408,15 +463,20 @@ class DDP(nn.Module, _SamplerMixin):
                 flip = meta.get('flip_direction', 'horizontal')
         return crop, out_size, flip
 
-    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None):
-        """``hints`` (b,Hh,Wh) uint8 in the frame of ``img``: see ``ddim_sample``; slide mode raises ValueError.
+    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
+        """``prior`` (b,Hp,Wp) uint8 in the frame of ``img`` and ``t_start``: see ``ddim_sample``; slide mode raises ValueError.
+        ``hints`` (b,Hh,Wh) uint8 in the frame of ``img``: see ``ddim_sample``; slide mode raises ValueError.
         encoder_decoder.py:250-304 (mode='whole'), post-loop epilogue fused into one kernel:
         the (1,K,H,W) resized scores / probabilities of the reference are never materialised.  ``img`` may hold
         b >= 1 images (§8 f4): the loop runs once on the whole batch with independent noise per image, and every
         image gets the crop / rescale / flip of its OWN ``img_meta`` entry (one epilogue launch per distinct geometry)."""
         from ..engine import seg_postprocess
         hk = {} if hints is None else dict(hints=hints)
+        if prior is not None or t_start is not None:
+            hk.update(prior=prior, t_start=t_start)
         if self._mode() == 'slide':
+            if prior is not None or t_start is not None:
+                raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
             if hints is not None:
                 raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
             if img_meta and any(self._epilogue_args(m, rescale) != self._epilogue_args(img_meta[0], rescale) for m in img_meta):
@@ -448,8 +508,9 @@ class DDP(nn.Module, _SamplerMixin):
             res.append(seg[0].cpu().numpy().astype('int64'))
         return res
 
-    def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, hints=None, **kwargs):
-        """``hints``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
+    def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, hints=None, prior=None, t_start=None,
+                **kwargs):
+        """``hints``, ``prior``, ``t_start``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
         base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
         augmentation lists the test pipeline produces."""
         if return_loss:
@@ -459,12 +520,14 @@ class DDP(nn.Module, _SamplerMixin):
                 if img_metas is None or len(img_metas) != len(img):
                     raise ValueError(f'num of augmentations ({len(img)}) != num of image meta ({0 if img_metas is None else len(img_metas)})')
                 return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
-                                     **({} if hints is None else {'hints': hints}))
+                                     **({} if hints is None else {'hints': hints}),
+                                     **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
         return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
-                                **({} if hints is None else {'hints': hints}))
+                                **({} if hints is None else {'hints': hints}),
+                                **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')

@@ -112,6 +112,13 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                     prediction - see "x0 hints" below.  Refused (DDP_E_BADCFG) for bev, by ddp_sample_fcn and its
                                     workspace query, together with DDP_FLAG_FORCE_X0 and for seg with 256 classes; ddp_head_forward
                                     ignores it.  Clear: launches, workspace sizes and outputs are unchanged */,
+       DDP_FLAG_PRIOR_START = 65536 /* model surface, all three tasks, both samplers, both engines, every route, through ddp_sample
+                                       only: the chain starts from the caller's prior map noised to steps[0] (the time the host layer
+                                       calls t_start) instead of from pure noise - see "prior start" below.  Combines with every other
+                                       flag of ddp_sample.  Refused (DDP_E_BADCFG) by ddp_sample_fcn, ddp_prepare_fcn and
+                                       ddp_sample_fcn_workspace and for bev with more than 32 classes; ddp_head_forward ignores it.
+                                       (Bits 8192 and 32768 stay undefined.)  Clear: launches, workspace sizes and outputs are
+                                       unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
@@ -338,6 +345,41 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * instantiations of its decision kernels (the ones DDP_FLAG_FORCE_X0 runs, which have no non-temporal variant) with the row buffer
  * as the forced class and "keep the argmax where the forced value is >= num_classes" semantics; depth the same kernels as without
  * the flag, which read one more float per pixel and step. */
+
+/* prior start (DDP_FLAG_PRIOR_START, all three tasks; csrc/ddp_prior_start.hip).  forward_train noises a known map to a time t and asks
+ * the head to recover it (segmentors/ddp.py:149-165, depther/ddp.py:133-143, the bev model likewise); with the flag set the same
+ * arithmetic starts the sampling chain: the loop's first read comes from the caller's PRIOR MAP noised to steps[0], and a caller who
+ * holds a good estimate (the previous frame, the coarse scale, an edited map) runs fewer steps from a smaller time.  The library
+ * takes alpha and sigma from steps[0] as passed to ddp_sample; the host layer evaluates the whole steps array on a time grid that
+ * begins at t_start instead of 1 (ddp_amd.schedule, t_start=).  The steps are independent of the flag: a flag-clear call with such a
+ * steps array and a caller-made start map in d_noise is legal.
+ * The prior map is per image at the map resolution, (B, h, w); all r replicas share it, each keeps its own noise:
+ *   seg    uint8.  A value < num_classes is that class; any other value is the ignore row embedding[num_classes] (ddp.py:151).  With
+ *          256 classes every value is a class
+ *   depth  float32 metric depth.  Finite and > 0: x0 = clamp(((d - min_depth) / (max_depth - min_depth) * 2 - 1) * bit_scale,
+ *          +-bit_scale) with the depther's range, clamped like a prediction; anything else (0, negative, NaN, +-inf): x0 = 0, the
+ *          middle of the range
+ *   bev    uint32.  Bit c set = class c present, bits >= num_classes are ignored:
+ *          x0 = (sigmoid(mean_c embedding[bit_c ? c + 1 : 0]) * 2 - 1) * bit_scale (fusion_models/ddp.py)
+ * Start map, for image b, replica rr, channel ch, pixel n, eps = the caller's d_noise or the seeded start noise:
+ *   seg / bev   m0 = steps[0].alpha * x0[b][ch][n] + steps[0].sigma * eps[b][rr][ch][n]
+ *   depth       m0 = steps[0].alpha * x0[b][n]     + eps[b][rr][0][n] / steps[0].sigma     (depth's ddp_step.sigma is 1 / sqrt(1 - gamma))
+ * each as ONE fused multiply-add on the rounded second term.  Every route then reads m0 where it would read d_noise.
+ * Sizes and places, as formulas of the cfg - each buffer rounded up to 256 bytes; ddp_query_workspace grows by exactly
+ * round256(prior_bytes) + [SEEDED_NOISE clear: round256(start_bytes)], every other offset and ddp_query_const_workspace are those of
+ * the cfg without the flag:
+ *   prior_bytes = batch * h * w * (seg: 1, depth / bev: 4)        the caller-written prior map, carved IMMEDIATELY IN FRONT of the
+ *                 x0-hint buffers (of the seeded-noise buffer without them); it starts at
+ *                 ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)]
+ *                                          - [SEEDED_NOISE: round256(noise_bytes)]
+ *                                          - [X0_HINTS: round256(hint_bytes) + round256(row_bytes)] - round256(prior_bytes)
+ *   start_bytes = batch * randsteps * Cm * h * w * 4              the start map m0 (B, r, Cm, h, w), immediately in front of the prior
+ *                 map; carved only when DDP_FLAG_SEEDED_NOISE is clear.  With both flags set the seeded-noise buffer is the start
+ *                 buffer: it is filled with eps and then mixed in place, and after the call it holds m0, not eps
+ * The library never initialises the prior map: the caller writes it before ddp_sample (ddp_amd.engine.DDPEngine clears it - seg
+ * 255, depth 0, bev 0 - whenever it allocates the workspace or changes the geometry).  The kernel reads it from device memory when it
+ * runs, so a captured graph picks up a new prior on replay.
+ * Extra launches with the flag set: one k_prior_start_tab (seg, bev) / k_prior_start_depth per call, behind the hint-row launch and the noise fill. */
 
 /* ---- finer-grained entry points (unit tests, and the decode_head plugin surface) ------------- */
 

@@ -5,6 +5,7 @@ next while every tagged kernel took the same time - which calls are slow, and wh
 
   python scripts/call_times.py --workload bev_fusion_k3_8x200x200 fused= unfused=DDP_TAIL_FUSED=0 --calls 40 --blocks 3
   python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= free=DDP_X0_HINTS=free sparse=DDP_X0_HINTS=sparse
+  python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= prior=DDP_PRIOR_START=1.0 --tags
 
 Per variant and block: the sorted per-call HIP-event times, their median / min / max, the mean power and clock over the block."""
 import argparse
@@ -29,6 +30,7 @@ def main():
     ap.add_argument('--calls', type=int, default=40)
     ap.add_argument('--blocks', type=int, default=3)
     ap.add_argument('--idle', type=float, default=0.0, help='seconds of idle GPU in front of every block')
+    ap.add_argument('--tags', action='store_true', help='one more call per variant under the library\'s launch records: ms and launches per tag')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     wl = bench.WORKLOADS[args.workload]
@@ -50,7 +52,21 @@ def main():
         # DDP_X0_HINTS=free | sparse in a variant's environment: DDP_FLAG_X0_HINTS set, with every pixel free or ~5 % of the pixels hinted
         # (seg: seeded classes, depth: seeded depths inside the range) - a switch of this script, not of the library
         hk = os.environ.get('DDP_X0_HINTS')
-        engines[name] = DDPEngine(sd, task, **(dict(x0_hints=True) if hk else {}), **kw)
+        # DDP_PRIOR_START=<t_start>: DDP_FLAG_PRIOR_START set, the chain started from a seeded prior map noised to t_start (1.0: the same
+        # K steps as the default path, so the difference between the variants is the start-map kernel) - likewise a switch of this script
+        pk = os.environ.get('DDP_PRIOR_START')
+        engines[name] = DDPEngine(sd, task, **(dict(x0_hints=True) if hk else {}), **(dict(prior_start=True, t_start=float(pk)) if pk else {}),
+                                  **kw)
+        if pk:
+            g = torch.Generator().manual_seed(8)
+            shape = (wl['batch'], wl['h'], wl['w'])
+            if task == 'seg':
+                prior = torch.randint(0, wl['num_classes'] + 1, shape, generator=g).to(torch.uint8)
+            elif task == 'depth':
+                prior = torch.rand(shape, generator=g) * 70.0 + 1.0
+            else:
+                prior = torch.randint(0, 1 << wl['num_classes'], shape, generator=g).to(torch.int32)
+            engines[name].set_prior(prior.to(dev))
         if hk == 'sparse':
             g = torch.Generator().manual_seed(7)
             shape = (wl['batch'], wl['h'], wl['w'])
@@ -92,6 +108,21 @@ def main():
             res.append(rec)
             print(json.dumps(rec), flush=True)
     ps.stop()
+    if args.tags:      # the library's own launch records (ddp_profile_*): tag 0 holds the untagged helper launches, the start-map kernel among them
+        import ctypes as C
+        for name, eng in engines.items():
+            ms, n = C.c_float(0), C.c_int(0)
+            torch.cuda.synchronize()
+            eng.lib.ddp_profile_begin(255)
+            eng.sample(dx, dn, out=out)
+            torch.cuda.synchronize()
+            eng.lib.ddp_profile_end(C.byref(ms), C.byref(n))
+            tags = {}
+            for tag in range(11):
+                eng.lib.ddp_profile_read(tag, C.byref(ms), C.byref(n))
+                if n.value:
+                    tags[tag] = [round(ms.value, 4), n.value]
+            print(json.dumps(dict(variant=name, tag_ms_launches=tags)), flush=True)
     # clock trace: (seconds since the first block, W, MHz) every ~50 ms - what the power controller did over the whole run
     if ps.samples:
         t00 = ps.samples[0][0]
