@@ -2488,6 +2488,36 @@ int fcn_conv_prepare(const ddp_fcn_conv& c, int i, const float* d_temb, const Fc
   DDP_TRY(launch_split_weights(o.wpack, 2304, 256, 2304, o.wsplit, st));
   return launch_build_stages(o.wsplit, size_t(256) * 2304, 2304, 256, 0, 1, 72, 0, 2, 1, 0, stream_dst, st);
 }
+// bn_w and bn_b set, both running statistics NULL: a GroupNorm(32, 256) convolution (include/ddp_mi355x.h, ddp_fcn_conv)
+inline bool fcn_conv_is_gn(const ddp_fcn_conv& c) { return c.bn_w && c.bn_b && !c.bn_mean && !c.bn_var; }
+// GroupNorm scratch of one head evaluation, inside FcnLayout::a_sb (dead while the head's convolutions run: nothing of the
+// head reads it and the sampler stages its concat-conv input in its own in_sb): the fp64 partial sums first - 16 B per token
+// on the fused route, 512 B per 256-token chunk of a map otherwise, either way <= 512 Mp bytes - then {mean, rstd} per
+// (map, group), 256 B per map <= 256 Mp bytes; the region holds 1536 Mp bytes
+struct FcnGnScratch {
+  double* partial;
+  float* stats;
+};
+FcnGnScratch fcn_gn_scratch(const FcnLayout& o, int M) {
+  const size_t Mp = (size_t(M) + 255) / 256 * 256;
+  char* base = reinterpret_cast<char*>(o.a_sb);
+  return {reinterpret_cast<double*>(base), reinterpret_cast<float*>(base + Mp * 512)};
+}
+// the weight-side constants of a GroupNorm conv: the stage images of the PLAIN 3x3 weights and the accumulator bias (conv
+// bias or zeros) - neither depends on the time embedding.  scratch = o.{wpack, wsplit}
+int fcn_gn_conv_prepare(const ddp_fcn_conv& c, const FcnLayout& o, unsigned char* stream_dst, float* bias_dst, hipStream_t st) {
+  DDP_TRY(check_ptr(c.conv_w, "conv weight"));
+  DDP_TRY(launch_pack_conv3x3_scaled(c.conv_w, nullptr, o.wpack, 256, 256, st));
+  DDP_TRY(launch_split_weights(o.wpack, 2304, 256, 2304, o.wsplit, st));
+  DDP_TRY(launch_build_stages(o.wsplit, size_t(256) * 2304, 2304, 256, 0, 1, 72, 0, 2, 1, 0, stream_dst, st));
+  const hipError_t e = c.conv_b ? hipMemcpyAsync(bias_dst, c.conv_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, st)
+                                : hipMemsetAsync(bias_dst, 0, 256 * sizeof(float), st);
+  if (e != hipSuccess) {
+    set_error("fcn_head: GroupNorm conv bias copy failed");
+    return DDP_E_LAUNCH;
+  }
+  return DDP_OK;
+}
 // conv_seg (cls_seg; dropout is the identity in eval mode): 1x1, the class rows zero-padded to the GEMM's 256 outputs
 int fcn_cls_prepare(const float* d_cls_w, const float* d_cls_b, int num_classes, const FcnLayout& o, unsigned char* stream_dst,
                     float* bias_dst, hipStream_t st) {
@@ -2507,6 +2537,8 @@ int fcn_cls_prepare(const float* d_cls_w, const float* d_cls_b, int num_classes,
 // `prep`: the weight-side constants built beforehand (the sampler loop: ddp_prepare_fcn); NULL: the time embedding is a
 // run-time input (ddp_fcn_head_forward) and they are built here, one conv at a time through the workspace's single stream
 // buffer (conv i's images are consumed - stream order - before conv i + 1's are written).
+// A GroupNorm conv (fcn_conv_is_gn) cannot fold its norm into the weights - the statistics are of the activations: plain GEMM with
+// the statistics fused into its epilogue where h * w % 32 == 0, then k_gn_film_relu_blk in place (ddp_fcn_gn.hip).
 int fcn_head_tokens(const ddp_fcn_conv* convs, int num_convs, int dilation, const float* d_cls_w, const float* d_cls_b,
                     int num_classes, const float* d_temb, int maps, int h, int w, const FcnLayout& o, hipStream_t st,
                     const FcnPrepared* prep = nullptr) {
@@ -2520,7 +2552,11 @@ int fcn_head_tokens(const ddp_fcn_conv* convs, int num_convs, int dilation, cons
   pr.nchw_N = 0;
   pr.M = M;
   for (int i = 0; i < num_convs; ++i) {
-    if (!prep) DDP_TRY(fcn_conv_prepare(convs[i], i, d_temb, o, o.stream, o.aff + 256, st));
+    const bool gn = fcn_conv_is_gn(convs[i]);
+    if (!prep) {
+      if (gn) DDP_TRY(fcn_gn_conv_prepare(convs[i], o, o.stream, o.aff + 256, st));
+      else DDP_TRY(fcn_conv_prepare(convs[i], i, d_temb, o, o.stream, o.aff + 256, st));
+    }
     pr.A = cur;
     pr.out = nxt;
     pr.stream = prep ? prep->conv_stream[i] : o.stream;
@@ -2528,7 +2564,28 @@ int fcn_head_tokens(const ddp_fcn_conv* convs, int num_convs, int dilation, cons
     pr.conv_h = h;
     pr.conv_w = w;
     pr.bias = prep ? prep->conv_shift[i] : o.aff + 256;
-    DDP_TRY(launch_b3_sgemm(&pr, 1, 2, dilation, st));
+    if (gn) {
+      // GroupNorm: plain convolution (+ bias, inside the accumulators the fused statistics are formed from) -> statistics per
+      // map -> one in-place pass norm x FiLM + ReLU.  The FiLM vector is evaluated here, also in the sampler loop: it needs
+      // 512 floats per (step, conv), conv_shifts holds 256.
+      const float* film = nullptr;
+      if (d_temb && convs[i].time_w) {
+        DDP_TRY(launch_matvec(convs[i].time_w, convs[i].time_b, d_temb, o.film, DDP_TIME_DIM, 512, 1, DDP_TIME_DIM, 512, 2, 0, st));
+        film = o.film;
+      }
+      const FcnGnScratch gs = fcn_gn_scratch(o, M);
+      const bool fused = N % 32 == 0;
+      pr.gn_partial = fused ? gs.partial : nullptr;
+      pr.gn_N = fused ? N : 0;
+      DDP_TRY(launch_b3_sgemm(&pr, 1, 0, dilation, st));
+      pr.gn_partial = nullptr;
+      pr.gn_N = 0;
+      if (fused) DDP_TRY(launch_gn_final32(gs.partial, gs.stats, maps, N, convs[i].bn_eps, st));
+      else DDP_TRY(launch_gn_stats_blk(nxt, gs.partial, gs.stats, maps, N, convs[i].bn_eps, st));
+      DDP_TRY(launch_gn_film_relu_blk(nxt, gs.stats, convs[i].bn_w, convs[i].bn_b, film, maps, N, st));
+    } else {
+      DDP_TRY(launch_b3_sgemm(&pr, 1, 2, dilation, st));
+    }
     float* t = cur;
     cur = nxt;
     nxt = t;
@@ -2598,13 +2655,15 @@ int fcn_loop_layout(const ddp_cfg* c, int num_convs, char* base, FcnLoopLayout* 
   o->bytes = off;
   return DDP_OK;
 }
-FcnPrepared fcn_prepared_of(const FcnLoopLayout& o, int num_convs, int step) {
+// a GroupNorm conv's images and bias do not depend on the step: its slot of step 0 serves every step (its other slots stay unused)
+FcnPrepared fcn_prepared_of(const FcnLoopLayout& o, const ddp_fcn_conv* convs, int num_convs, int step) {
   FcnPrepared p;
   const size_t per_conv = size_t(72) * b3_stage_bytes();
   for (int i = 0; i < 8; ++i) {
     const bool live = i < num_convs;
-    p.conv_stream[i] = live ? o.conv_streams + (size_t(step) * num_convs + i) * per_conv : nullptr;
-    p.conv_shift[i] = live ? o.conv_shifts + (size_t(step) * num_convs + i) * 256 : nullptr;
+    const size_t slot = live ? size_t(fcn_conv_is_gn(convs[i]) ? 0 : step) * num_convs + i : 0;
+    p.conv_stream[i] = live ? o.conv_streams + slot * per_conv : nullptr;
+    p.conv_shift[i] = live ? o.conv_shifts + slot * 256 : nullptr;
   }
   p.cls_stream = o.cls_stream;
   p.cls_bias = o.cls_bias;
@@ -2706,11 +2765,14 @@ int prepare_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn_co
   DDP_TRY(launch_split_weights(o.wm, 256, 256, 256, o.wm_split, st));
   // the head's weight-side constants: one set of scaled-weight images per (step, conv) - the FiLM scale depends on the step
   const size_t per_conv = size_t(72) * b3_stage_bytes();
+  // (a GroupNorm conv: plain weights, one set for every step in its slot of step 0; its FiLM vector is evaluated in the loop)
   for (int s = 0; s < K; ++s)
-    for (int i = 0; i < num_convs; ++i)
-      DDP_TRY(fcn_conv_prepare(convs[i], i, o.temb + size_t(s) * DDP_TIME_DIM, o.head,
-                               o.conv_streams + (size_t(s) * num_convs + i) * per_conv,
-                               o.conv_shifts + (size_t(s) * num_convs + i) * 256, st));
+    for (int i = 0; i < num_convs; ++i) {
+      unsigned char* images = o.conv_streams + (size_t(s) * num_convs + i) * per_conv;
+      float* shift = o.conv_shifts + (size_t(s) * num_convs + i) * 256;
+      if (!fcn_conv_is_gn(convs[i])) DDP_TRY(fcn_conv_prepare(convs[i], i, o.temb + size_t(s) * DDP_TIME_DIM, o.head, images, shift, st));
+      else if (s == 0) DDP_TRY(fcn_gn_conv_prepare(convs[i], o.head, images, shift, st));
+    }
   return fcn_cls_prepare(weights->head_w, weights->head_b, Kc, o.head, o.cls_stream, o.cls_bias, st);
 }
 }  // namespace
@@ -2759,7 +2821,7 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
     // feat = transform(cat[x, mask_t]) -> the head's token-major input
     DDP_TRY(launch_row_to_sb(o.mask, 256, o.in_sb, M, 256, st));
     DDP_TRY(launch_b3_linear(o.in_sb, wpm, nullptr, o.xproj, 256, r * N, N, o.head.x0, 256, M, 256, 256, st, TAG_XPROJ));
-    const FcnPrepared prep = fcn_prepared_of(o, num_convs, s);
+    const FcnPrepared prep = fcn_prepared_of(o, convs, num_convs, s);
     DDP_TRY(fcn_head_tokens(convs, num_convs, dilation, weights->head_w, weights->head_b, Kc, o.temb + size_t(s) * DDP_TIME_DIM, R,
                             cfg->h, cfg->w, o.head, st, &prep));
     SegUpdateArgs a = seg_update_args(o.head.logits, o.head.ldl, Kc, o.lut, o.mask, o.prob, cfg->accumulation ? (s == 0 ? 1 : 2) : 0,

@@ -315,6 +315,11 @@ int launch_gn_final32_multi(const double* const* partial, float* const* stats, c
 int launch_pack_conv3x3_scaled(const float* w, const float* scale, float* out, int cout, int cin, hipStream_t st);
 int launch_fcn_fold(const float* bn_w, const float* bn_b, const float* bn_mean, const float* bn_var, float bn_eps,
                     const float* conv_bias, const float* film, float* scale, float* shift, hipStream_t st);
+// ddp_fcn_gn.hip: GroupNorm ConvWithTimeModule, the apply pass in place on the convolution's blk result:
+// y = ReLU(y * a + b), a = rstd * gamma * (1 + s), b = (beta - mean * rstd * gamma) * (1 + s) + t per (map, channel);
+// stats (B, 32) {mean, rstd}; film (512) = (s | t) or nullptr (0 | 0); N tokens per map
+int launch_gn_film_relu_blk(float* y_blk, const float* stats, const float* gamma, const float* beta, const float* film, int B, int N,
+                            hipStream_t st);
 // out[b][k][n] = (1/div) * sum_ri prob[(b*r+ri)*N + n][k]
 // frag_nch > 0: prob is fragment-major as the layer kernel's seg tails write it (per 32-token group frag_nch * 2048 floats)
 int launch_finalize_nchw(const float* prob, int ldl, float* out, int B, int r, int N, int K, float div,

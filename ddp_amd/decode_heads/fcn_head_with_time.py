@@ -3,7 +3,9 @@
 ``conv_seg.*``) and ``forward(inputs, times)`` contract as
 segmentation/mmseg/models/decode_heads/fcn_head_with_time.py:229-305, with the compute done by libddp_mi355x.so
 (``ddp_fcn_head_forward``): every ConvWithTimeModule is ONE bf16x3 GEMM (K = 9 x 256) whose weights carry the
-eval-mode norm x FiLM scale and whose epilogue carries the shift and the ReLU.  Inference only (eval-mode BatchNorm);
+eval-mode norm x FiLM scale and whose epilogue carries the shift and the ReLU.  With ``norm_cfg=dict(type='GN',
+num_groups=32)`` (keys ``convs.i.gn.*``) the statistics are of the activations: the GEMM runs on the plain weights and leaves
+the per-map statistics, one streaming pass applies norm x FiLM + ReLU.  Inference only (eval-mode BatchNorm or GroupNorm(32));
 CUDA tensors only - no CPU path.  The nn.Modules below only HOLD parameters in the reference's layout.
 """
 import ctypes as C
@@ -15,22 +17,28 @@ from .. import _lib
 from ..registry import HEADS
 
 
+def _add_norm(module, norm, cout, eps):
+    """norm: None | 'bn' | 'gn' - the attribute name mmcv's build_norm_layer gives the layer (BN / SyncBN -> 'bn', GN -> 'gn')"""
+    if norm == 'bn':
+        module.bn = nn.BatchNorm2d(cout) if eps is None else nn.BatchNorm2d(cout, eps=eps)
+    elif norm == 'gn':
+        module.gn = nn.GroupNorm(32, cout) if eps is None else nn.GroupNorm(32, cout, eps=eps)
+
+
 class _ConvWithTimeParams(nn.Module):
-    def __init__(self, cin, cout, with_norm, time_in_channels=1024):
+    def __init__(self, cin, cout, norm, time_in_channels=1024, eps=None):
         super().__init__()
-        self.conv = nn.Conv2d(cin, cout, 3, padding=1, bias=not with_norm)      # ConvModule bias='auto'
-        if with_norm:
-            self.bn = nn.BatchNorm2d(cout)                                       # norm name 'bn' for BN / SyncBN
+        self.conv = nn.Conv2d(cin, cout, 3, padding=1, bias=norm is None)       # ConvModule bias='auto'
+        _add_norm(self, norm, cout, eps)
         self.time_mlp = nn.Sequential(nn.SiLU(), nn.Linear(time_in_channels, cout * 2))
         nn.init.kaiming_normal_(self.conv.weight, a=0, nonlinearity='relu')
 
 
 class _ConvParams(nn.Module):
-    def __init__(self, cin, cout, k, with_norm):
+    def __init__(self, cin, cout, k, norm, eps=None):
         super().__init__()
-        self.conv = nn.Conv2d(cin, cout, k, padding=k // 2, bias=not with_norm)
-        if with_norm:
-            self.bn = nn.BatchNorm2d(cout)
+        self.conv = nn.Conv2d(cin, cout, k, padding=k // 2, bias=norm is None)
+        _add_norm(self, norm, cout, eps)
 
 
 @HEADS.register_module()
@@ -44,18 +52,26 @@ class FCNHeadWithTime(nn.Module):
             in_channels = in_channels[0]
         if in_channels != 256 or channels != 256 or kernel_size != 3 or input_transform is not None:
             raise NotImplementedError('ddp_amd FCNHeadWithTime: 256 -> 256 channels, 3x3 convs, single input')
-        if norm_cfg is not None and norm_cfg.get('type') not in ('BN', 'SyncBN'):
-            raise NotImplementedError('ddp_amd FCNHeadWithTime: norm_cfg None or (Sync)BN (eval-mode running statistics)')
+        norm = None
+        if norm_cfg is not None:
+            kind = norm_cfg.get('type')
+            if kind in ('BN', 'SyncBN'):
+                norm = 'bn'
+            elif kind == 'GN' and norm_cfg.get('num_groups') == 32:
+                norm = 'gn'
+            else:
+                raise NotImplementedError(f'ddp_amd FCNHeadWithTime: norm_cfg {norm_cfg!r} - supported: None, BN / SyncBN '
+                                          '(eval-mode running statistics) and GN with num_groups=32')
         if act_cfg is None or act_cfg.get('type') != 'ReLU':
             raise NotImplementedError('ddp_amd FCNHeadWithTime: act_cfg=ReLU')
         assert num_convs >= 0 and dilation > 0
         self.num_convs, self.kernel_size, self.concat_input, self.dilation = num_convs, kernel_size, concat_input, dilation
         self.in_channels, self.channels, self.num_classes = [in_channels], channels, num_classes
         self.in_index, self.align_corners = in_index, align_corners
-        with_norm = norm_cfg is not None
-        self.convs = nn.ModuleList([_ConvWithTimeParams(256, 256, with_norm) for _ in range(num_convs)])
+        eps = norm_cfg.get('eps') if norm_cfg is not None else None
+        self.convs = nn.ModuleList([_ConvWithTimeParams(256, 256, norm, eps=eps) for _ in range(num_convs)])
         if concat_input:          # built by the reference, never called by its _forward_feature (:285-299)
-            self.conv_cat = _ConvParams(512, 256, kernel_size, with_norm)
+            self.conv_cat = _ConvParams(512, 256, kernel_size, norm, eps=eps)
         self.conv_seg = nn.Conv2d(channels, num_classes, kernel_size=1)
         self._ws = None
 
@@ -71,13 +87,16 @@ class FCNHeadWithTime(nn.Module):
             return t.data_ptr()
         arr = (_lib.DdpFcnConv * max(self.num_convs, 1))()
         for i, m in enumerate(self.convs):
-            bn = getattr(m, 'bn', None)
+            bn, gn = getattr(m, 'bn', None), getattr(m, 'gn', None)
             arr[i].conv_w, arr[i].conv_b = ptr(m.conv.weight), ptr(m.conv.bias)
-            arr[i].bn_w = ptr(bn.weight) if bn is not None else None
-            arr[i].bn_b = ptr(bn.bias) if bn is not None else None
-            arr[i].bn_mean = ptr(bn.running_mean) if bn is not None else None
-            arr[i].bn_var = ptr(bn.running_var) if bn is not None else None
-            arr[i].bn_eps = bn.eps if bn is not None else 0.0
+            if gn is not None:          # GroupNorm(32): weight / bias with NULL running statistics (include/ddp_mi355x.h)
+                arr[i].bn_w, arr[i].bn_b, arr[i].bn_mean, arr[i].bn_var, arr[i].bn_eps = ptr(gn.weight), ptr(gn.bias), None, None, gn.eps
+            else:
+                arr[i].bn_w = ptr(bn.weight) if bn is not None else None
+                arr[i].bn_b = ptr(bn.bias) if bn is not None else None
+                arr[i].bn_mean = ptr(bn.running_mean) if bn is not None else None
+                arr[i].bn_var = ptr(bn.running_var) if bn is not None else None
+                arr[i].bn_eps = bn.eps if bn is not None else 0.0
             arr[i].time_w, arr[i].time_b = ptr(m.time_mlp[1].weight), ptr(m.time_mlp[1].bias)
         return arr, keep
 

@@ -200,12 +200,18 @@ def make_levels(batch, h, w, seed):
     return out
 
 
-def make_fcn_state_dict(num_convs, num_classes, with_norm, concat_input, seed):
-    """FCNHeadWithTime parameters / buffers with the reference's key names (decode_heads/fcn_head_with_time.py)."""
+def make_fcn_state_dict(num_convs, num_classes, with_norm, concat_input, seed, norm='bn'):
+    """FCNHeadWithTime parameters / buffers with the reference's key names (decode_heads/fcn_head_with_time.py).
+    ``norm`` (with ``with_norm``): 'bn' - BatchNorm with running statistics; 'gn' - GroupNorm, keys ``*.gn.weight|bias``."""
+    assert norm in ('bn', 'gn')
     g = torch.Generator().manual_seed(40_000 + seed)
     sd = {}
 
     def bn(prefix):
+        if norm == 'gn':
+            sd[prefix + 'gn.weight'] = 1.0 + 0.2 * torch.randn((256,), generator=g)
+            sd[prefix + 'gn.bias'] = 0.1 * torch.randn((256,), generator=g)
+            return
         sd[prefix + 'bn.weight'] = 1.0 + 0.2 * torch.randn((256,), generator=g)
         sd[prefix + 'bn.bias'] = 0.1 * torch.randn((256,), generator=g)
         sd[prefix + 'bn.running_mean'] = 0.2 * torch.randn((256,), generator=g)
@@ -231,11 +237,11 @@ def make_fcn_state_dict(num_convs, num_classes, with_norm, concat_input, seed):
     return sd
 
 
-def make_fcn_segmentor_state_dict(num_convs, num_classes, with_norm, concat_input, seed):
+def make_fcn_segmentor_state_dict(num_convs, num_classes, with_norm, concat_input, seed, norm='bn'):
     """Hot-path state_dict of ``DDP(decode_head=FCNHeadWithTime)``: the segmentor's own parameters
     (transform, time_mlp, embedding_table) + the FCN head's under ``decode_head.``."""
     sd = {k: v for k, v in make_state_dict('seg', num_classes, 0, 256, seed=seed).items() if not k.startswith('decode_head.')}
-    sd.update({'decode_head.' + k: v for k, v in make_fcn_state_dict(num_convs, num_classes, with_norm, concat_input, seed).items()})
+    sd.update({'decode_head.' + k: v for k, v in make_fcn_state_dict(num_convs, num_classes, with_norm, concat_input, seed, norm=norm).items()})
     return sd
 
 

@@ -537,12 +537,24 @@ int ddp_neck_fpn_msm(const ddp_fpn_level* levels, int batch, const float* const*
 /* FCNHeadWithTime.forward (decode_heads/fcn_head_with_time.py:285-305), eval mode:
  *   x = inputs[0]; for each ConvWithTimeModule: x = ReLU( norm(conv3x3(x)) * (scale + 1) + shift ),
  *   (scale, shift) = Linear(SiLU(temb)).chunk(2)  (:205-225);  out = conv_seg(x)  (cls_seg, dropout is identity in eval).
- * 256 channels in and out; the norm is an eval-mode BatchNorm (running statistics) or absent.  The reference's
- * conv_cat is constructed but never called by _forward_feature (:285-299) and is therefore not part of the path. */
+ * 256 channels in and out; per conv the norm is an eval-mode BatchNorm (running statistics), a GroupNorm(32, 256) or absent - a
+ * head may mix them.  The reference's conv_cat is constructed but never called by _forward_feature (:285-299) and is
+ * therefore not part of the path.
+ * The norm of a conv is told by its four bn_* pointers:
+ *   all four set                          eval-mode BatchNorm, eps = bn_eps (folded with the FiLM into the weights and the bias)
+ *   bn_w, bn_b set, bn_mean = bn_var = NULL
+ *                                         GroupNorm(32 groups of 8 channels), gamma = bn_w, beta = bn_b, eps = bn_eps; the
+ *                                         statistics are taken per map m = b * r + rr on its own, over the conv output with its
+ *                                         bias:  y = ReLU( (conv(x) + conv_b - mu[m,g]) * rstd[m,g] * gamma * (scale + 1)
+ *                                                          + beta * (scale + 1) + shift )
+ *   bn_w NULL                             no norm
+ *   anything else (bn_b missing, only one of bn_mean / bn_var)    DDP_E_NULL, "incomplete norm"
+ * The scratch of a GroupNorm conv lies inside the bytes ddp_fcn_head_workspace / ddp_sample_fcn_workspace return for any head. */
 typedef struct ddp_fcn_conv {
   const float* conv_w;   /* convs.i.conv.weight (256,256,3,3) */
   const float* conv_b;   /* convs.i.conv.bias (256) or NULL (bias='auto' with a norm) */
-  const float* bn_w;     /* convs.i.bn.weight / bias / running_mean / running_var (256 each), or all NULL */
+  const float* bn_w;     /* convs.i.bn.weight / bias / running_mean / running_var (256 each), or all NULL; GroupNorm:
+                          * convs.i.gn.weight / bias with bn_mean = bn_var = NULL (see above) */
   const float* bn_b;
   const float* bn_mean;
   const float* bn_var;
@@ -567,7 +579,11 @@ int ddp_sample_fcn_workspace(const ddp_cfg* cfg, int num_convs, int dilation, si
  * step has its own images), plus conv_seg's images - written once into the model region of the workspace.  A caller that
  * samples repeatedly through the same workspace buffer (same stream, or after synchronising with this call) passes
  * DDP_FLAG_FCN_PREPARED in cfg->flags to ddp_sample_fcn and none of these ~12 kernels per (step, conv) runs again; without
- * the flag ddp_sample_fcn calls this itself. */
+ * the flag ddp_sample_fcn calls this itself.
+ * A GroupNorm conv has ONE set of images, of its plain weights, for all steps (slot (step 0, conv i); its other slots stay
+ * unused) and its bias vector; nothing of it is rebuilt under DDP_FLAG_FCN_PREPARED either.  Its FiLM vector (512 floats; the
+ * prepared region holds 256 per (step, conv)) is evaluated inside the loop, one matvec per (step, conv), from convs[i].time_w /
+ * time_b, and the apply pass reads convs[i].bn_w / bn_b: those four tensors must stay valid during ddp_sample_fcn. */
 int ddp_prepare_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn_conv* convs, int num_convs, int dilation,
                     const ddp_step* steps, void* d_workspace, void* stream);
 int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn_conv* convs, int num_convs, int dilation,

@@ -126,7 +126,10 @@ for wl in ('ade_swin_t_k3_8x512x1024', 'city_swin_l_k10_4x1024x2048', 'bev_fusio
 f = glob.glob(os.path.join(src, 'prof_fcn', '**', '*kernel_stats.csv'), recursive=True)
 if f:
     shutil.copy(f[0], os.path.join(dst, f'{tag}_fcn_sampler_6_calls_kernel_stats.csv'))
-for name in ('power_components.json', 'fcn_calls.log', 'call_times_bev.jsonl', 'call_times_kitti.jsonl', 'gather_by_position_init.json',
+f = glob.glob(os.path.join(src, 'prof_fcn_gn', '**', '*kernel_stats.csv'), recursive=True)
+if f:
+    shutil.copy(f[0], os.path.join(dst, f'{tag}_fcn_gn_head_kernel_stats.csv'))
+for name in ('power_components.json', 'fcn_calls.log', 'fcn_gn_times.jsonl', 'call_times_bev.jsonl', 'call_times_kitti.jsonl', 'gather_by_position_init.json',
              'gather_by_position_trained.json', 'hbm_calib.jsonl', 'bench_bev_fusion_k3_r4_2x200x200.json'):
     f = os.path.join(src, name)
     if os.path.exists(f) and os.path.getsize(f):

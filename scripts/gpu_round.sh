@@ -97,6 +97,12 @@ done
 # FCN-head sampler: the loop-invariant kernels run once per engine, not per call (ddp_prepare_fcn)
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_fcn -o fcn -- python $REPO/scripts/fcn_launch_count.py > $REPO/$OUT/fcn_calls.log 2>&1 )
 grep "^call" $OUT/fcn_calls.log
+# the GroupNorm FCN head next to the BatchNorm head at the C2-sized shape (HIP-event times per call), and under a kernel trace:
+# k_gn_film_relu_blk next to k_gn_apply_add_blk on the same rows (scripts/fcn_gn_times.py --trace)
+timeout 200 python scripts/fcn_gn_times.py > $OUT/fcn_gn_times.jsonl 2> $OUT/fcn_gn_times.err
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_fcn_gn -o fcngn -- python $REPO/scripts/fcn_gn_times.py > $REPO/$OUT/fcn_gn_prof.log 2>&1 )
+python scripts/fcn_gn_times.py --trace "$(find $OUT/prof_fcn_gn -name '*kernel_trace.csv' | head -1)" >> $OUT/fcn_gn_times.jsonl 2>> $OUT/fcn_gn_times.err
+cat $OUT/fcn_gn_times.jsonl
 # what costs what under the cap: MFMA alone, + LDS fragment reads + VALU fillers, + the LDS-DMA weight stream, + the HBM streams
 timeout 300 python scripts/power_calibration.py --components --seconds 3 > $OUT/power_components.json 2> $OUT/power_components.err
 # what this box gives the matrix pipes under its package power cap: vendor bf16 GEMM, MFMA-only loops
