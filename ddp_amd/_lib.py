@@ -22,6 +22,7 @@ FLAG_SEEDED_NOISE = 2048
 FLAG_DDPM_CHAIN = 4096
 FLAG_X0_HINTS = 16384      # (8192 stays undefined)
 FLAG_PRIOR_START = 65536   # (so does 32768)
+FLAG_CLASS_PRIOR = 131072
 DEPTH_NORM_LINEAR, DEPTH_NORM_SOFTMAX, DEPTH_NORM_SIGMOID = 0, 1, 2
 MAX_DEPTH_BINS = 256
 BEV_MAX_PRESCALE_AREA = 16

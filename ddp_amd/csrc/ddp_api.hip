@@ -104,6 +104,10 @@ struct Layout {
   // k_prior_start_* writes (without DDP_FLAG_SEEDED_NOISE; with it seed_noise is the start map, mixed in place)
   void* prior_map = nullptr;
   float* prior_start = nullptr;
+  // DDP_FLAG_CLASS_PRIOR: the caller-written table (B, 256) and the per-image vectors k_class_prior writes: (B, 256) bias + prior rows
+  // (the seg tails' accumulator start), then (B, 256) prior rows (k_seg_update's addend)
+  float* cprior_table = nullptr;
+  float* cprior_rows = nullptr;
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
@@ -201,8 +205,12 @@ int validate(const ddp_cfg* c) {
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
                    DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
                    DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN | DDP_FLAG_X0_HINTS |
-                   DDP_FLAG_PRIOR_START)) {
+                   DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR)) {
     set_error("unknown flags 0x%x", c->flags);
+    return DDP_E_BADCFG;
+  }
+  if ((c->flags & DDP_FLAG_CLASS_PRIOR) && c->task != DDP_TASK_SEG) {
+    set_error("DDP_FLAG_CLASS_PRIOR exists for the segmentation sampler only (task %d: no depth or bev prior is built)", c->task);
     return DDP_E_BADCFG;
   }
   if (c->flags & DDP_FLAG_X0_HINTS) {
@@ -481,6 +489,12 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   // and the map stay the last of the workspace and every other offset is the one of the cfg without the flag
   // prior start: the start map (only without DDP_FLAG_SEEDED_NOISE), then the caller's prior map, in front of the x0-hint buffers
   // (include/ddp_mi355x.h, "prior start")
+  // class prior: the private per-image vectors, then the caller's table, in front of the prior-start buffers (include/ddp_mi355x.h,
+  // "class prior")
+  if (c->flags & DDP_FLAG_CLASS_PRIOR) {
+    o->cprior_rows = cv.take(size_t(2) * o->B * 256);
+    o->cprior_table = cv.take(size_t(o->B) * 256);
+  }
   if (c->flags & DDP_FLAG_PRIOR_START) {
     if (!(c->flags & DDP_FLAG_SEEDED_NOISE)) o->prior_start = cv.take(o->M0 * o->Cm);
     o->prior_map = cv.take(c->task == DDP_TASK_SEG ? (size_t(o->B) * o->N + 3) / 4 : size_t(o->B) * o->N);
@@ -1236,6 +1250,8 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
       tl.x0_force = x0.force;
       tl.x0_keep = x0.keep;
       tl.x0_idx = x0.idx;
+      tl.cp_bias = o.cprior_rows;                        // (nullptr without DDP_FLAG_CLASS_PRIOR)
+      tl.cp_rn = o.r * o.N;
       tl.M = M;
       tl.num_classes = o.Kc;
       tl.ldl = o.ldl;
@@ -1278,6 +1294,8 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
     a.x0_force = x0.force;
     a.x0_keep = x0.keep;
     a.x0_idx = x0.idx;
+    a.cp_delta = o.cprior_rows ? o.cprior_rows + size_t(o.B) * 256 : nullptr;
+    a.cp_rn = o.r * o.N;
     if (c->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
       if (key) {   // DDP_FLAG_SEEDED_NOISE: the step's noise is generated token-major - no NCHW tensor, no transpose
         prof_begin(TAG_GENERIC, st);
@@ -1637,6 +1655,12 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     prof_begin(TAG_GENERIC, st);
     DDP_TRY(recorded(launch_hint_rows(o.hint_map, o.hint_rows, cfg->task, o.B, o.r, o.N, o.Kc, st), st));
   }
+  // DDP_FLAG_CLASS_PRIOR: the caller's table as read NOW -> the per-image bias / prior rows of the seg decision kernels
+  if (o.cprior_rows) {
+    prof_begin(TAG_GENERIC, st);
+    DDP_TRY(recorded(launch_class_prior(o.cprior_table, weights->head_b, o.cprior_rows, o.cprior_rows + size_t(o.B) * 256, o.B, o.Kc, st),
+                     st));
+  }
   const uint32_t* key = nullptr;
   if (seeded) {
     key = reinterpret_cast<const uint32_t*>(d_noise);
@@ -1699,12 +1723,12 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
 
 int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float* d_feat, const float* d_temb,
                      float* d_out, void* d_workspace, void* stream) {
-  // one decoder pass has no x0 feedback and no start map: DDP_FLAG_X0_HINTS and DDP_FLAG_PRIOR_START are ignored (the buffers they
-  // carve lie behind everything used here)
+  // one decoder pass has no x0 feedback and no start map: DDP_FLAG_X0_HINTS, DDP_FLAG_PRIOR_START and DDP_FLAG_CLASS_PRIOR are ignored
+  // (the buffers they carve lie behind everything used here)
   ddp_cfg no_hints;
-  if (cfg && (cfg->flags & (DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START))) {
+  if (cfg && (cfg->flags & (DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR))) {
     no_hints = *cfg;
-    no_hints.flags &= ~(DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START);
+    no_hints.flags &= ~(DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR);
     cfg = &no_hints;
   }
   DDP_TRY(validate(cfg));
@@ -2692,6 +2716,10 @@ int validate_fcn_loop(const ddp_cfg* cfg, int num_convs, int dilation) {
   }
   if (cfg->flags & DDP_FLAG_PRIOR_START) {
     set_error("sample_fcn: DDP_FLAG_PRIOR_START is built for ddp_sample only (the FCN loop starts from noise)");
+    return DDP_E_BADCFG;
+  }
+  if (cfg->flags & DDP_FLAG_CLASS_PRIOR) {
+    set_error("sample_fcn: DDP_FLAG_CLASS_PRIOR is built for ddp_sample only (the FCN loop takes no class prior)");
     return DDP_E_BADCFG;
   }
   if (num_convs < 0 || num_convs > 8 || dilation < 1) {

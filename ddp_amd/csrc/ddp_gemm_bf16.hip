@@ -205,10 +205,11 @@ int launch_tail_tf(const b3::LayerArgs& la, int grid, hipStream_t st) {
   prof_end(TAG_HEAD, st);
   return check_launch(MODE == 4 ? "b3::k_layer (seg tail + next step head)" : "b3::k_layer (seg tail)");
 }
-// la.x0_force (DDP_FLAG_FORCE_X0, a test instrument) selects the teacher-forcing instantiation; the product path runs <.., false>
+// la.x0_force (DDP_FLAG_FORCE_X0, a test instrument; DDP_FLAG_X0_HINTS) or la.cp_bias (DDP_FLAG_CLASS_PRIOR) selects the conditioned
+// instantiation; the product path runs <.., false>
 template <int MODE, int NCH>
 int launch_tail_t(const b3::LayerArgs& la, int grid, hipStream_t st) {
-  return la.x0_force ? launch_tail_tf<MODE, NCH, true>(la, grid, st) : launch_tail_tf<MODE, NCH, false>(la, grid, st);
+  return (la.x0_force || la.cp_bias) ? launch_tail_tf<MODE, NCH, true>(la, grid, st) : launch_tail_tf<MODE, NCH, false>(la, grid, st);
 }
 }  // namespace
 
@@ -226,6 +227,8 @@ int launch_b3_tail(const TailLaunch& a, hipStream_t st) {
   la.x0_idx = a.x0_idx;
   la.x0_force = a.x0_force;
   la.x0_keep = a.x0_keep;
+  la.cp_bias = a.cp_bias;
+  la.cp_rn = a.cp_rn;
   la.num_classes = a.num_classes;
   la.ldl = a.ldl;
   la.prob_mode = a.prob_mode;

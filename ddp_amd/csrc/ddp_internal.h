@@ -133,6 +133,8 @@ struct TailLaunch {
   unsigned char* x0_idx;        // optional: argmax class per token (diagnostic trace)
   const unsigned char* x0_force;  // optional (DDP_FLAG_FORCE_X0): the class to feed back instead of the argmax
   int x0_keep;                    // DDP_FLAG_X0_HINTS: x0_force is the hint row buffer - a value >= num_classes keeps the argmax
+  const float* cp_bias;           // DDP_FLAG_CLASS_PRIOR: (B, 256) per-image conv_seg bias rows (bias + prior), the row of token m is
+  int cp_rn;                      //   m / cp_rn (cp_rn = r * N); nullptr: the one bias of bias_ext / seg_bias
   int M, num_classes, ldl, prob_mode;
   float alpha, sigma, alpha_next, sigma_next;
   // fuse_next: this launch is also the head of the NEXT step (k_layer MODE 4): mask_sb = nullptr, the update runs on
@@ -276,6 +278,10 @@ struct SegUpdateArgs {
   int sampler;
   ddp_step st;
   int rows;
+  // DDP_FLAG_CLASS_PRIOR: (B, 256) per-image prior rows, clamped; row m / cp_rn (cp_rn = r * N) is added to the scores of token m as
+  // they are read and the sums are written back to `logits` (the last step's are the output without accumulation); nullptr: none
+  const float* cp_delta;
+  int cp_rn;
 };
 int launch_seg_update(const SegUpdateArgs& a, hipStream_t st);
 // x0 = (sigmoid(E[argmax_k scores]) * 2 - 1) * bit_scale, NCHW (B,K,N) -> (B,256,N)
@@ -449,6 +455,12 @@ int launch_u_noise(float* ubuf, const float* noise, const float* wm, int M, floa
 // the caller's hint map (B, N) - seg uint8, depth fp32 - expanded to the rows m = (b * r + rr) * N + n the decision kernels read, the
 // "free" encodings normalised (seg: >= num_classes -> 255; depth: 0, negative, NaN, +-inf -> 0).  `rows` holds whole 256-byte granules
 int launch_hint_rows(const void* map, void* rows, int task, int B, int r, int N, int num_classes, hipStream_t st);
+
+// ---- ddp_class_prior.hip (DDP_FLAG_CLASS_PRIOR) -----------------------------------------------------
+// the caller's table (B, 256) normalised (NaN -> 0, clamp to +-1e30) into the two per-image forms the decision kernels read:
+// bias_rows (B, 256) = head_b + prior (zero beyond num_classes), delta_rows (B, 256) = prior (zero beyond num_classes)
+int launch_class_prior(const float* table, const float* head_b, float* bias_rows, float* delta_rows, int B, int num_classes,
+                       hipStream_t st);
 
 // ---- ddp_prior_start.hip (DDP_FLAG_PRIOR_START) -----------------------------------------------------
 // out (B, r, Cm, N) = alpha x0(prior) + sigma eps (seg / bev; Cm = 256) or alpha x0(prior) + eps / sigma (depth; Cm = 1), eps

@@ -1641,6 +1641,10 @@ __global__ void __launch_bounds__(256) k_seg_update(SegUpdateArgs a) {
   for (int q = 0; q < 4; ++q) {
     const int k = lane + 64 * q;
     v[q] = (k < K) ? lg[k] : -INFINITY;
+    if (a.cp_delta && k < K) {      // DDP_FLAG_CLASS_PRIOR: the image's prior row in front of every reader of the score, the output included
+      v[q] += a.cp_delta[size_t(m / a.cp_rn) * 256 + k];
+      const_cast<float*>(lg)[k] = v[q];
+    }
     if (k < K && (v[q] > best)) {   // strict >: keeps the first (smallest k) maximum within the lane
       best = v[q];
       bi = k;

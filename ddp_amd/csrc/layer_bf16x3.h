@@ -172,6 +172,11 @@ struct LayerArgs {
   // > 0 replaces the prediction in the x0 normalisation; nullptr: none
   const float* dhint;
   int x0_keep;
+  // DDP_FLAG_CLASS_PRIOR (behind the hint fields: every other argument keeps its place).  cp_bias: (B, 256) per-image conv_seg bias
+  // rows, bias + prior, zero padded; the FORCE instantiations of the seg tails start a token's conv_seg accumulators from the row of
+  // its image, m / cp_rn (cp_rn = r * N), instead of the one row in LDS - a 32-token group may straddle two images.  nullptr: none
+  const float* cp_bias;
+  int cp_rn;
 };
 
 // vmcnt(12): everything but the 12 newest vector-memory ops (= the DMA pieces of the stage just issued) is done
@@ -1552,7 +1557,25 @@ k_layer(LayerArgs la) {
       f32x16 lg[NCH > 0 ? NCH : 1][2];
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        bias_init(lg[c], MODE == 6 ? LYR_T_SEG / 64 + c : c);
+        bool own_row = false;
+        if constexpr (FORCE) {
+          // DDP_FLAG_CLASS_PRIOR: the accumulators of this lane's token start from the bias row of the token's image (bias + prior);
+          // a padding token of the last group reads the last image's row, in range
+          if (la.cp_bias) {
+            own_row = true;
+            const int mi = m_base + j < M ? m_base + j : M - 1;
+            const float* row = la.cp_bias + size_t(mi / la.cp_rn) * 256 + c * 64 + 4 * h;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                const f32x4 b = *reinterpret_cast<const f32x4*>(row + t * 32 + 8 * g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) lg[c][t][4 * g + e] = b[e];
+              }
+          }
+        }
+        if (!own_row) bias_init(lg[c], MODE == 6 ? LYR_T_SEG / 64 + c : c);
         tall_pair(lg[c][0], lg[c][1], I1);
       }
       const int m = m_base + j;
@@ -1587,7 +1610,7 @@ k_layer(LayerArgs la) {
       if (!valid || bi >= K) bi = 0;
       if (la.x0_idx && valid && h == 0) la.x0_idx[m] = (unsigned char)bi;
       if constexpr (FORCE) {      // teacher forcing: a test instrument in its own instantiations, the product's tails do not have it
-        if (valid) {
+        if (valid && la.x0_force) {                             // (nullptr: DDP_FLAG_CLASS_PRIOR alone runs these instantiations)
           const int f = la.x0_force[m];
           if (la.x0_keep) {       // DDP_FLAG_X0_HINTS: the hint rows - a value >= K leaves the pixel to the argmax
             if (f < K) bi = f;

@@ -213,8 +213,12 @@ class DDPEngine(_SeededNoise):
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
                  bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None, x0_hints=False,
-                 prior_start=False, t_start=1.0):
-        """``prior_start`` (DDP_FLAG_PRIOR_START; all three tasks): the chain starts from the caller's prior map noised to ``t_start``
+                 prior_start=False, t_start=1.0, class_prior=False):
+        """``class_prior`` (DDP_FLAG_CLASS_PRIOR; seg): a per-image additive prior on the conv_seg scores, in front of everything that
+        reads them at every step - ``set_class_prior()`` / ``class_prior_view()`` / ``clear_class_prior()``,
+        ``SampleGraph.replay(class_prior=)``.  (B, num_classes) float32; ``-inf`` excludes a class (``class_mask_to_prior``), NaN
+        reads as 0.  The engine writes zeros (no prior) whenever it allocates or regrows the workspace and on every ``set_geometry``.
+        ``prior_start`` (DDP_FLAG_PRIOR_START; all three tasks): the chain starts from the caller's prior map noised to ``t_start``
         instead of from pure noise - ``set_prior()`` / ``prior_view()`` / ``clear_prior()``, ``SampleGraph.replay(prior=)``,
         ``last_start()``.  seg: (B, h, w) uint8 classes, a value >= num_classes is the ignore row; depth: (B, h, w) float32 metric
         depth, 0 / negative / NaN / inf is the middle of the range; bev: (B, h, w) int32 bit words, bit c = class c present.  The
@@ -331,6 +335,10 @@ class DDPEngine(_SeededNoise):
             if task == 'bev' and num_classes > 32:
                 raise ValueError('prior_start: a bev prior is one 32-bit word per pixel (DDP_FLAG_PRIOR_START, num_classes <= 32)')
             cfg.flags |= _lib.FLAG_PRIOR_START
+        if class_prior:
+            if task != 'seg':
+                raise ValueError(f'class_prior is built for the segmentation sampler (DDP_FLAG_CLASS_PRIOR): task {task!r} takes none')
+            cfg.flags |= _lib.FLAG_CLASS_PRIOR
         self.t_start = float(t_start)
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
@@ -354,6 +362,7 @@ class DDPEngine(_SeededNoise):
         self._init_key()
         self.clear_hints(_if_any=True)
         self.clear_prior(_if_any=True)
+        self.clear_class_prior(_if_any=True)
 
     def _workspace_bytes(self):
         nbytes = C.c_size_t(0)
@@ -447,6 +456,38 @@ class DDPEngine(_SeededNoise):
         cm = 1 if c.task == _lib.TASK_DEPTH else 256
         return self.workspace.view(torch.uint8)[off:off + nbytes].view(torch.float32).view(c.batch, c.randsteps, cm, c.h, c.w)
 
+    # ---- DDP_FLAG_CLASS_PRIOR ------------------------------------------------------------------
+    def class_prior_view(self):
+        """(B, 256) float32 VIEW of the caller-written class prior table inside the workspace; columns >= num_classes are ignored.
+        The library reads it when ddp_sample runs (a captured graph picks up what it holds at replay).  Place:
+        include/ddp_mi355x.h, "class prior"."""
+        c = self.cfg
+        if not c.flags & _lib.FLAG_CLASS_PRIOR:
+            raise _lib.DdpError('the class prior needs an engine built with class_prior=True')
+        off, nbytes, _, _ = class_prior_places(c, self._workspace_bytes())
+        return self.workspace.view(torch.uint8)[off:off + nbytes].view(torch.float32).view(c.batch, 256)
+
+    def set_class_prior(self, prior):
+        """copy ``prior`` (B, num_classes) - a floating-point tensor on the engine's device - into the table (stream-ordered)"""
+        v = self.class_prior_view()
+        c = self.cfg
+        if not isinstance(prior, torch.Tensor) or not prior.dtype.is_floating_point:
+            raise _lib.DdpError(f'class_prior must be a floating-point tensor, got {getattr(prior, "dtype", type(prior))}')
+        if tuple(prior.shape) != (c.batch, c.num_classes):
+            raise _lib.DdpError(f'class_prior must have shape {(c.batch, c.num_classes)} (batch, num_classes), got {tuple(prior.shape)}')
+        if prior.device != self.device:
+            raise _lib.DdpError(f'engine lives on {self.device}: the class prior is on {prior.device}')
+        with torch.cuda.device(self.device):
+            v[:, :c.num_classes].copy_(prior, non_blocking=True)
+
+    def clear_class_prior(self, _if_any=False):
+        """no prior: every entry 0 (the bits of the flag-clear call)"""
+        if _if_any and not self.cfg.flags & _lib.FLAG_CLASS_PRIOR:
+            return
+        v = self.class_prior_view()
+        with torch.cuda.device(self.device):
+            v.zero_()
+
     # ------------------------------------------------------------------------------------------
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -490,6 +531,7 @@ class DDPEngine(_SeededNoise):
         self._sampled = False      # (so do the step record and the disagreement map)
         self.clear_hints(_if_any=True)   # (and the hint map: another geometry or another buffer - unset hints are no hints)
         self.clear_prior(_if_any=True)   # (and the prior map)
+        self.clear_class_prior(_if_any=True)   # (and the class prior table)
         return self
 
     def out_shape(self):
@@ -666,6 +708,40 @@ def prior_start_places(cfg, workspace_bytes):
     return prior_off, prior_bytes, start_off, start_bytes
 
 
+def class_prior_places(cfg, workspace_bytes):
+    """(table_offset, table_bytes, bias_offset, bias_bytes) of include/ddp_mi355x.h ("class prior"), in bytes from the start of a
+    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): THE host-side derivation of where DDP_FLAG_CLASS_PRIOR's buffers lie -
+    the caller's table immediately in front of the prior-start, hint, seeded-noise and step-record buffers (whichever exist), the
+    library's per-image vectors immediately in front of it."""
+    table_bytes = cfg.batch * 256 * 4
+    bias_bytes = 2 * table_bytes
+    end = workspace_bytes
+    if cfg.flags & _lib.FLAG_PRIOR_START:
+        prior_off, _, start_off, _ = prior_start_places(cfg, workspace_bytes)
+        end = prior_off if cfg.flags & _lib.FLAG_SEEDED_NOISE else min(prior_off, start_off)
+    else:
+        seg = cfg.task == _lib.TASK_SEG
+        n = cfg.batch * cfg.h * cfg.w
+        if cfg.flags & _lib.FLAG_STEP_RECORD:
+            rec, smap = step_record_sizes(cfg)
+            end -= _round256(rec) + _round256(smap)
+        if cfg.flags & _lib.FLAG_SEEDED_NOISE:
+            end -= _round256(n * cfg.randsteps * (256 if seg else 1) * 4)
+        if cfg.flags & _lib.FLAG_X0_HINTS:
+            end -= _round256(n * (1 if seg else 4)) + _round256(n * cfg.randsteps * (1 if seg else 4))
+    table_off = end - _round256(table_bytes)
+    return table_off, table_bytes, table_off - _round256(bias_bytes), bias_bytes
+
+
+def class_mask_to_prior(mask):
+    """bool (B, K) "class k can occur in image b" -> the float32 class prior that says exactly that: 0 where True, -inf where False"""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() != 2:
+        raise ValueError(f'class_mask_to_prior takes a bool (B, K) tensor, got {getattr(mask, "dtype", type(mask))} '
+                         f'{tuple(getattr(mask, "shape", ()))}')
+    out = torch.zeros(mask.shape, dtype=torch.float32, device=mask.device)
+    return out.masked_fill_(~mask, float('-inf'))
+
+
 def step_record_view(workspace, base, cfg):
     dtype = {_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32}[cfg.task]
     nbytes = step_record_sizes(cfg)[0]
@@ -692,8 +768,11 @@ class SampleGraph:
         self.workspace = engine.workspace
         self.workspace_ptr = engine.workspace.data_ptr()
 
-    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None, hints=None, prior=None):
-        """``prior`` (prior_start engines): written to the engine's prior map in front of the launch (``DDPEngine.set_prior``); None:
+    def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None, hints=None, prior=None,
+               class_prior=None):
+        """``class_prior`` (class_prior engines): written to the engine's table in front of the launch (``DDPEngine.set_class_prior``);
+        None: the graph runs on what the table holds.
+        ``prior`` (prior_start engines): written to the engine's prior map in front of the launch (``DDPEngine.set_prior``); None:
         the graph runs on what the map holds.
         ``hints`` (x0_hints engines): written to the engine's hint map in front of the launch (``DDPEngine.set_hints``); None: the
         graph runs on what the map holds.
@@ -724,6 +803,8 @@ class SampleGraph:
             eng.set_hints(hints)
         if prior is not None:
             eng.set_prior(prior)
+        if class_prior is not None:
+            eng.set_class_prior(class_prior)
         self.graph.replay()
         return self.out
 
@@ -735,7 +816,9 @@ class FcnSamplerEngine(_SeededNoise):
     def __init__(self, state_dict, head, *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150, bit_scale=0.01,
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
                  device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False, x0_hints=False,
-                 prior_start=False):
+                 prior_start=False, class_prior=False):
+        if class_prior:
+            raise ValueError('class_prior is built for ddp_sample only (DDP_FLAG_CLASS_PRIOR): the FCN-head loop takes no class prior')
         if prior_start:
             raise ValueError('prior_start is built for ddp_sample only (DDP_FLAG_PRIOR_START): the FCN-head loop starts from noise')
         if x0_hints:

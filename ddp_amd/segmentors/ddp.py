@@ -109,6 +109,23 @@ class _SamplerMixin:
         ix = (torch.arange(w, dtype=torch.float32) * torch.tensor(W / w, dtype=torch.float32)).floor().long().clamp(max=W - 1)
         return prior[:, iy.to(prior.device)][:, :, ix.to(prior.device)].to(dtype).contiguous()
 
+    def _class_prior_table(self, class_prior, b, device, repeat=1):
+        """``class_prior`` (b, num_classes) float -> the float32 rows of the engine's class prior table (DDP_FLAG_CLASS_PRIOR) on
+        ``device``.  An image-level prior has no frame: ``repeat`` > 1 tiles the rows for the windows of a slide chunk (window-major,
+        the order of the chunk's maps), every window of image i getting row i."""
+        if not torch.is_tensor(class_prior) or class_prior.dim() != 2 or tuple(class_prior.shape) != (b, self.num_classes) \
+                or not class_prior.dtype.is_floating_point:
+            raise ValueError(f'class_prior must be a float (batch, num_classes) = ({b}, {self.num_classes}) tensor, got '
+                             f'{tuple(class_prior.shape) if torch.is_tensor(class_prior) else type(class_prior)}')
+        t = class_prior.to(device=device, dtype=torch.float32)
+        return (t.repeat(repeat, 1) if repeat > 1 else t).contiguous()
+
+    @staticmethod
+    def _cp_kw(class_prior):
+        """the keyword that carries a class prior down the call chain - none without one, so that a model without a prior calls its
+        (possibly replaced) members exactly as before"""
+        return {} if class_prior is None else dict(class_prior=class_prior)
+
     @staticmethod
     def _check_t_start(prior, t_start):
         if prior is not None and t_start is None:
@@ -192,7 +209,7 @@ class DDP(nn.Module, _SamplerMixin):
         return times
 
     def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample',
-                    record_steps=False, seeded=False, hints=False, prior=False, t_start=None):
+                    record_steps=False, seeded=False, hints=False, prior=False, t_start=None, class_prior=False):
         from ..decode_heads.fcn_head_with_time import FCNHeadWithTime
         K = self.timesteps if timesteps is None else timesteps
         r = self.randsteps if randsteps is None else randsteps
@@ -204,8 +221,10 @@ class DDP(nn.Module, _SamplerMixin):
         ts = 1.0 if t_start is None else float(t_start)
         chain = bool(self.ddpm_chain) and sampler == 'ddpm'
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints), bool(prior), ts)
+               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints), bool(prior), ts, bool(class_prior))
         if isinstance(self.decode_head, FCNHeadWithTime):
+            if class_prior:
+                raise ValueError('class_prior is built for the deformable head\'s sampler: the FCNHeadWithTime loop takes none')
             if prior or ts != 1.0:
                 raise ValueError('prior / t_start are built for the deformable head\'s sampler: the FCNHeadWithTime loop starts from noise')
             if hints:
@@ -223,7 +242,8 @@ class DDP(nn.Module, _SamplerMixin):
             from ..engine import DDPEngine, count_layers
             nl = count_layers(self.hot_path_state_dict())
             return DDPEngine(None, 'seg', h=h, w=w, feat_channels=256, weights=self._packed_weights(device, 'seg', nl),
-                             ddpm_chain=chain, x0_hints=bool(hints), prior_start=bool(prior), t_start=ts, **common)
+                             ddpm_chain=chain, x0_hints=bool(hints), prior_start=bool(prior), t_start=ts,
+                             class_prior=bool(class_prior), **common)
         return self._get_engine(key, factory, geometry=(b, h, w))
 
     def hot_path_state_dict(self):
@@ -238,8 +258,12 @@ class DDP(nn.Module, _SamplerMixin):
 
     @torch.no_grad()
     def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None, prior=None,
-                    t_start=None):
-        """``prior`` (b,Hp,Wp) uint8 in the frame of the network input with ``t_start`` in (sample_range[0], 1] (call-time only;
+                    t_start=None, class_prior=None):
+        """``class_prior`` (b, num_classes) float (call-time only; DDP_FLAG_CLASS_PRIOR): row i is added to the conv_seg scores of
+        image i at every step, in front of the argmax that is fed back, the accumulated softmax and the scores returned - what a
+        model with ``conv_seg.bias + class_prior[i]`` would compute for image i.  ``-inf`` excludes a class
+        (``ddp_amd.engine.class_mask_to_prior``); NaN reads as 0.
+        ``prior`` (b,Hp,Wp) uint8 in the frame of the network input with ``t_start`` in (sample_range[0], 1] (call-time only;
         DDP_FLAG_PRIOR_START): the chain starts from the prior's classes (a value >= num_classes: the ignore row) noised to
         ``t_start`` instead of from pure noise, and the K steps divide [sample_range[0], t_start]; resampled to (h,w) with nearest.
         ``t_start`` alone: the same time grid on the given / drawn ``noise`` as the start map.
@@ -259,12 +283,17 @@ class DDP(nn.Module, _SamplerMixin):
             hk.update(prior=prior is not None, t_start=t_start)
         hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
         pmap = None if prior is None else self._prior_map(prior, b, h, w, torch.uint8).to(x.device)
+        cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
+        if cp is not None:
+            hk.update(class_prior=True)
         if noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True, **hk)
             if hmap is not None:
                 eng.set_hints(hmap)
             if pmap is not None:
                 eng.set_prior(pmap)
+            if cp is not None:
+                eng.set_class_prior(cp)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
@@ -274,13 +303,15 @@ class DDP(nn.Module, _SamplerMixin):
             eng.set_hints(hmap)
         if pmap is not None:
             eng.set_prior(pmap)
+        if cp is not None:
+            eng.set_class_prior(cp)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     @torch.no_grad()
     def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0, hints=None,
-                    prior=None, t_start=None):
-        """``hints``, ``prior``, ``t_start``: as ``ddim_sample``"""
+                    prior=None, t_start=None, class_prior=None):
+        """``hints``, ``prior``, ``t_start``, ``class_prior``: as ``ddim_sample``"""
         self._check_feature(x)
         b, c, h, w = x.shape
         self._check_t_start(prior, t_start)
@@ -289,12 +320,17 @@ class DDP(nn.Module, _SamplerMixin):
             hk.update(prior=prior is not None, t_start=t_start)
         hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
         pmap = None if prior is None else self._prior_map(prior, b, h, w, torch.uint8).to(x.device)
+        cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
+        if cp is not None:
+            hk.update(class_prior=True)
         if noise is None and step_noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True, **hk)
             if hmap is not None:
                 eng.set_hints(hmap)
             if pmap is not None:
                 eng.set_prior(pmap)
+            if cp is not None:
+                eng.set_class_prior(cp)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
@@ -306,26 +342,28 @@ class DDP(nn.Module, _SamplerMixin):
             eng.set_hints(hmap)
         if pmap is not None:
             eng.set_prior(pmap)
+        if cp is not None:
+            eng.set_class_prior(cp)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)
 
-    def encode_decode(self, img, img_metas=None, image_base=0, call=0):
+    def encode_decode(self, img, img_metas=None, image_base=0, call=0, class_prior=None):
         """ddp.py:114-129."""
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_metas, **self._seed_kw(image_base, call))
+            out = self.ddim_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_metas, **self._seed_kw(image_base, call))
+            out = self.ddpm_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
         else:
             raise NotImplementedError
         return F.interpolate(out, size=img.shape[2:], mode='bilinear', align_corners=self.align_corners)
 
-    def whole_inference(self, img, img_meta=None, rescale=False, image_base=0, call=0):
+    def whole_inference(self, img, img_meta=None, rescale=False, image_base=0, call=0, class_prior=None):
         """encoder_decoder.py:229-248: crop to img_shape and resize to ori_shape when rescale."""
-        seg_logit = self.encode_decode(img, img_meta, **self._seed_kw(image_base, call))
+        seg_logit = self.encode_decode(img, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
         if rescale and img_meta:
             rs = img_meta[0]['img_shape'][:2]
             seg_logit = seg_logit[:, :, :rs[0], :rs[1]]
@@ -342,16 +380,16 @@ class DDP(nn.Module, _SamplerMixin):
             raise AssertionError(f"test_cfg.mode must be 'slide' or 'whole', got {mode!r}")
         return mode or 'whole'
 
-    def _sample(self, x, img_meta=None, image_base=0, call=0):
+    def _sample(self, x, img_meta=None, image_base=0, call=0, class_prior=None):
         if self.diffusion == 'ddim':
-            return self.ddim_sample(x, img_meta, **self._seed_kw(image_base, call))
+            return self.ddim_sample(x, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
         if self.diffusion == 'ddpm':
-            return self.ddpm_sample(x, img_meta, **self._seed_kw(image_base, call))
+            return self.ddpm_sample(x, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
         raise NotImplementedError
 
     SLIDE_WINDOWS_PER_CALL = 16          # windows x images sampled in one call of the loop (memory bound of the workspace)
 
-    def _slide(self, img, img_meta, rescale, want, flip=None, image_base=0, call=0):
+    def _slide(self, img, img_meta, rescale, want, flip=None, image_base=0, call=0, class_prior=None):
         """Sliding-window inference (encoder_decoder.py:180-227).  The reference runs ``encode_decode`` - backbone, neck and a
         K-step loop - window by window; the windows all have one size, so here they go through backbone + loop as ONE batch
         (chunks of SLIDE_WINDOWS_PER_CALL maps, independent noise per window as in the reference) and only their LOW-RESOLUTION
@@ -372,7 +410,9 @@ class DDP(nn.Module, _SamplerMixin):
         for i in range(0, len(crops), per):
             chunk = crops[i:i + per]
             x = self.extract_feat(torch.cat(chunk, dim=0))[0]
-            lows.append(self._sample(x, img_meta, **self._seed_kw(image_base, call + i // per)).reshape(len(chunk), b, self.num_classes, x.shape[2], x.shape[3]))
+            # (a class prior is image-level: every window of image i gets row i - the chunk's maps are window-major)
+            cpk = {} if class_prior is None else dict(class_prior=self._class_prior_table(class_prior, b, x.device, repeat=len(chunk)))
+            lows.append(self._sample(x, img_meta, **self._seed_kw(image_base, call + i // per), **cpk).reshape(len(chunk), b, self.num_classes, x.shape[2], x.shape[3]))
         scores = torch.cat(lows, dim=0)
         keep = out = None
         if rescale and img_meta:
@@ -380,16 +420,18 @@ class DDP(nn.Module, _SamplerMixin):
             out = tuple(img_meta[0]['ori_shape'][:2])
         return seg_slide_postprocess(scores, ys, xs, (ch, cw), img.shape[2:], keep, out, self.align_corners, flip, want)
 
-    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None, prior=None, t_start=None):
-        """encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
+    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None, prior=None, t_start=None, class_prior=None):
+        """``class_prior`` (b, num_classes): every window of image i samples with row i (see ``ddim_sample``).
+        encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
         if prior is not None or t_start is not None:
             raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
         if hints is not None:
             raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
-        return self._slide(img, img_meta, rescale, 'scores', **self._seed_kw(image_base, call))
+        return self._slide(img, img_meta, rescale, 'scores', **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
 
-    def inference(self, img, img_meta, rescale, image_base=0, call=0):
-        """encoder_decoder.py:251-287, mode 'whole' (what every DDP config sets): class probabilities at ``ori_shape`` with
+    def inference(self, img, img_meta, rescale, image_base=0, call=0, class_prior=None):
+        """``class_prior`` (b, num_classes): see ``ddim_sample``.
+        encoder_decoder.py:251-287, mode 'whole' (what every DDP config sets): class probabilities at ``ori_shape`` with
         the test-time flip undone - the building block of ``aug_test``.  ``simple_test`` does not go through here: its
         fused epilogue never materialises these (B,K,H,W) tensors."""
         mode = self._mode()
@@ -401,8 +443,8 @@ class DDP(nn.Module, _SamplerMixin):
             if img_meta and img_meta[0].get('flip', False):
                 fl = img_meta[0].get('flip_direction', 'horizontal')
                 assert fl in ('horizontal', 'vertical')
-            return self._slide(img, img_meta, rescale, 'prob', fl, **self._seed_kw(image_base, call))
-        output = F.softmax(self.whole_inference(img, img_meta, rescale, **self._seed_kw(image_base, call)), dim=1)
+            return self._slide(img, img_meta, rescale, 'prob', fl, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+        output = F.softmax(self.whole_inference(img, img_meta, rescale, **self._seed_kw(image_base, call), **self._cp_kw(class_prior)), dim=1)
         if img_meta and img_meta[0].get('flip', False):
             direction = img_meta[0].get('flip_direction', 'horizontal')
             assert direction in ('horizontal', 'vertical')
@@ -411,8 +453,9 @@ class DDP(nn.Module, _SamplerMixin):
 
     AUG_CALL_STRIDE = 1 << 16            # seeded noise: augmentation a owns the call values [a * stride, (a + 1) * stride)
 
-    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
-        """``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None):
+        """``class_prior`` (b, num_classes): an image-level prior has no frame - every augmentation of image i samples with row i.
+        ``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
         With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
         index), so no two augmentations of an image share noise.
         encoder_decoder.py:306-331: mean of the per-augmentation probabilities (multi-scale / flip), then argmax.
@@ -431,9 +474,9 @@ class DDP(nn.Module, _SamplerMixin):
         if self._mode() == 'slide':
             # no shipped config combines sliding windows with test-time augmentation: the reference's own composition
             # (running mean of ``inference``, encoder_decoder.py:306-331) over the fused per-augmentation slide epilogue
-            prob = self.inference(imgs[0], img_metas[0], rescale, **self._seed_kw(image_base, 0))
+            prob = self.inference(imgs[0], img_metas[0], rescale, **self._seed_kw(image_base, 0), **self._cp_kw(class_prior))
             for a, (img, meta) in enumerate(zip(imgs[1:], img_metas[1:]), 1):
-                prob += self.inference(img, meta, rescale, **self._seed_kw(image_base, a * self.AUG_CALL_STRIDE))
+                prob += self.inference(img, meta, rescale, **self._seed_kw(image_base, a * self.AUG_CALL_STRIDE), **self._cp_kw(class_prior))
             prob /= len(imgs)
             return list(prob.argmax(dim=1).cpu().numpy().astype('int64'))
         ori_shape = tuple(img_metas[0][0]['ori_shape'][:2])
@@ -442,9 +485,9 @@ class DDP(nn.Module, _SamplerMixin):
             assert all(tuple(m['ori_shape'][:2]) == ori_shape for m in meta)
             x = self.extract_feat(img)[0]
             if self.diffusion == 'ddim':
-                scores.append(self.ddim_sample(x, meta, **self._seed_kw(image_base, a)))
+                scores.append(self.ddim_sample(x, meta, **self._seed_kw(image_base, a), **self._cp_kw(class_prior)))
             elif self.diffusion == 'ddpm':
-                scores.append(self.ddpm_sample(x, meta, **self._seed_kw(image_base, a)))
+                scores.append(self.ddpm_sample(x, meta, **self._seed_kw(image_base, a), **self._cp_kw(class_prior)))
             else:
                 raise NotImplementedError
             metas.append(dict(img_size=tuple(img.shape[2:]), crop_size=tuple(meta[0]['img_shape'][:2]),
@@ -463,8 +506,9 @@ class DDP(nn.Module, _SamplerMixin):
                 flip = meta.get('flip_direction', 'horizontal')
         return crop, out_size, flip
 
-    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
-        """``prior`` (b,Hp,Wp) uint8 in the frame of ``img`` and ``t_start``: see ``ddim_sample``; slide mode raises ValueError.
+    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None):
+        """``class_prior`` (b, num_classes) float: see ``ddim_sample``; in slide mode every window of image i gets row i.
+        ``prior`` (b,Hp,Wp) uint8 in the frame of ``img`` and ``t_start``: see ``ddim_sample``; slide mode raises ValueError.
         ``hints`` (b,Hh,Wh) uint8 in the frame of ``img``: see ``ddim_sample``; slide mode raises ValueError.
         encoder_decoder.py:250-304 (mode='whole'), post-loop epilogue fused into one kernel:
         the (1,K,H,W) resized scores / probabilities of the reference are never materialised.  ``img`` may hold
@@ -474,6 +518,7 @@ class DDP(nn.Module, _SamplerMixin):
         hk = {} if hints is None else dict(hints=hints)
         if prior is not None or t_start is not None:
             hk.update(prior=prior, t_start=t_start)
+        hk.update(self._cp_kw(class_prior))
         if self._mode() == 'slide':
             if prior is not None or t_start is not None:
                 raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
@@ -486,7 +531,7 @@ class DDP(nn.Module, _SamplerMixin):
             # softmax is monotone, so the two agree except where fp32 rounding of exp / the division makes two probabilities EQUAL
             # that came from different scores - the reference then returns the lower class index, this path the class with the
             # larger score.  test_slide_epilogue_golden bounds it: identical wherever the reference's top-2 margin exceeds 1e-5.)
-            return list(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base)).cpu().numpy().astype('int64'))
+            return list(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base), **self._cp_kw(class_prior)).cpu().numpy().astype('int64'))
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
             out = self.ddim_sample(x, img_meta, **self._seed_kw(image_base), **hk)
@@ -509,8 +554,9 @@ class DDP(nn.Module, _SamplerMixin):
         return res
 
     def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, hints=None, prior=None, t_start=None,
-                **kwargs):
-        """``hints``, ``prior``, ``t_start``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
+                class_prior=None, **kwargs):
+        """``class_prior``: see ``simple_test`` / ``aug_test``.
+        ``hints``, ``prior``, ``t_start``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
         base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
         augmentation lists the test pipeline produces."""
         if return_loss:
@@ -521,13 +567,15 @@ class DDP(nn.Module, _SamplerMixin):
                     raise ValueError(f'num of augmentations ({len(img)}) != num of image meta ({0 if img_metas is None else len(img_metas)})')
                 return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
                                      **({} if hints is None else {'hints': hints}),
-                                     **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
+                                     **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
+                                     **self._cp_kw(class_prior))
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
         return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
                                 **({} if hints is None else {'hints': hints}),
-                                **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
+                                **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
+                                **self._cp_kw(class_prior))
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
@@ -542,8 +590,9 @@ class SelfAlignedDDP(DDP):
     (:150-164) - is exposed as ``self_aligned_predict``."""
 
     @torch.no_grad()
-    def self_aligned_predict(self, x, noise=None, return_logits=False, image_base=0, call=0):
-        """self_aligned_ddp.py:150-164: ONE decoder pass at t = 1 on pure noise, then the x0 projection:
+    def self_aligned_predict(self, x, noise=None, return_logits=False, image_base=0, call=0, class_prior=None):
+        """``class_prior`` (b, num_classes): added to the pass's scores in front of the argmax (see ``ddim_sample``).
+        self_aligned_ddp.py:150-164: ONE decoder pass at t = 1 on pure noise, then the x0 projection:
             feat = transform(cat[x, noise]); logits = decode_head(feat, time_mlp(log_snr(1)))
             preds = (sigmoid(embedding_table(argmax(logits))) * 2 - 1) * bit_scale
         x (b,256,h,w) -> preds (b,256,h,w) [, logits (b,K,h,w)].  ``noise`` (b,256,h,w) replaces ``torch.randn_like(x)``.
@@ -554,15 +603,21 @@ class SelfAlignedDDP(DDP):
         from .. import _lib
         self._check_feature(x)
         b, c, h, w = x.shape
+        cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
+        ck = {} if cp is None else dict(class_prior=True)
         # the head dispatch of _engine_for (the reference's pre-pass goes through the generic _decode_head_forward_test)
         if noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned',
-                                   seeded=True)
+                                   seeded=True, **ck)
+            if cp is not None:
+                eng.set_class_prior(cp)
             logits = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
         else:
             if noise is None:
                 noise = torch.randn_like(x)
-            eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned')
+            eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned', **ck)
+            if cp is not None:
+                eng.set_class_prior(cp)
             logits = eng.sample(x.contiguous().float(), noise.reshape(b, 1, c, h, w).contiguous().float())
         preds = torch.empty((b, 256, h, w), dtype=torch.float32, device=x.device)
         emb = self.embedding_table.weight.detach().float().contiguous()

@@ -119,6 +119,13 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                        ddp_sample_fcn_workspace and for bev with more than 32 classes; ddp_head_forward ignores it.
                                        (Bits 8192 and 32768 stay undefined.)  Clear: launches, workspace sizes and outputs are
                                        unchanged */,
+       DDP_FLAG_CLASS_PRIOR = 131072 /* model surface, seg through ddp_sample, both samplers, both engines, every route: a per-image
+                                        additive prior on the conv_seg scores, read from a caller-written table (B, 256) and applied
+                                        in front of everything that reads the scores - see "class prior" below.  Combines with every
+                                        other flag of ddp_sample.  Refused (DDP_E_BADCFG) for depth and bev and by ddp_sample_fcn,
+                                        ddp_prepare_fcn and ddp_sample_fcn_workspace; ddp_head_forward ignores it.  (Bits 8192 and
+                                        32768 stay undefined, every bit above this one is refused.)  Clear: launches, workspace sizes
+                                        and outputs are unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
@@ -380,6 +387,39 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * 255, depth 0, bev 0 - whenever it allocates the workspace or changes the geometry).  The kernel reads it from device memory when it
  * runs, so a captured graph picks up a new prior on replay.
  * Extra launches with the flag set: one k_prior_start_tab (seg, bev) / k_prior_start_depth per call, behind the hint-row launch and the noise fill. */
+
+/* class prior (DDP_FLAG_CLASS_PRIOR, seg; csrc/ddp_class_prior.hip).  Image-level knowledge about the answer: which classes can
+ * occur in image b and how likely each is (a tagger's candidate list, logit adjustment log p_target / p_train, classes a user
+ * switched off).  The CLASS PRIOR TABLE is (B, 256) float32; row b, entry k < num_classes is added to the conv_seg score of class k
+ * at every token of image b, for all r replicas and all K steps, in front of everything that reads the score: the argmax fed back
+ * as x0 (segmentors/ddp.py:235-239), the accumulated softmax, the returned last-step scores, the step record and the
+ * DDP_FLAG_RECORD_X0 trace.  The call computes what B one-image calls with conv_seg.bias + prior[b] would compute.  Entries
+ * k >= num_classes are ignored.  With DDP_FLAG_FORCE_X0 the forced decision is fed back and the returned scores carry the prior.
+ * One launch per call (k_class_prior, behind the hint-row launch) normalises the table as read THEN - NaN reads as 0, every value is
+ * clamped to [-1e30, 1e30] - so -inf (anything <= -1e30) means "class excluded": its score stays finite, its softmax term is
+ * exactly 0 and the returned scores never hold an infinity (the bilinear epilogues would turn 0 * inf into NaN).  An image with
+ * every class excluded is a uniform shift.
+ * Sizes and places, as formulas of the cfg - two buffers, each rounded up to 256 bytes; ddp_query_workspace grows by exactly
+ * round256(table_bytes) + round256(bias_bytes), every other offset and ddp_query_const_workspace are those of the cfg without the
+ * flag:
+ *   table_bytes = batch * 256 * 4       the caller-written table, carved IMMEDIATELY IN FRONT of the prior-start buffers (of the
+ *                 x0-hint, seeded-noise, step-record buffers - whichever come first - or the end of the workspace); it starts at
+ *                 ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)]
+ *                                          - [SEEDED_NOISE: round256(noise_bytes)]
+ *                                          - [X0_HINTS: round256(hint_bytes) + round256(row_bytes)]
+ *                                          - [PRIOR_START: round256(prior_bytes) + (SEEDED_NOISE clear: round256(start_bytes))]
+ *                                          - round256(table_bytes)
+ *   bias_bytes  = 2 * batch * 256 * 4   library-private, immediately in front of the table: per image the vector
+ *                 fl32(conv_seg.bias + clamp(prior[b])), zero padded to 256 (the accumulator start of conv_seg in the layer
+ *                 kernel's seg tails, which a lane reads for the image of its token, m / (r N) - a 32-token tile may straddle two
+ *                 images), then per image clamp(prior[b]) (added to the head GEMM's scores by k_seg_update on the routes that run
+ *                 conv_seg as a tile GEMM: the fp32 engine, DDP_FLAG_UNFUSED_LAYER, ddpm without DDP_FLAG_DDPM_CHAIN)
+ * The library never initialises the table: the caller writes it (all zeros = no prior, the bits of the flag-clear call) before the
+ * first ddp_sample; ddp_amd.engine.DDPEngine does so whenever it allocates the workspace or changes the geometry.  The kernel
+ * reads the caller's table from device memory when it runs, so a captured graph picks up a new table on replay.
+ * Extra launches with the flag set: one k_class_prior per call.  The layer kernel's seg tails run their conditioned instantiations
+ * (the ones DDP_FLAG_FORCE_X0 and DDP_FLAG_X0_HINTS run, which have no non-temporal variant); the flag-clear instantiations are
+ * untouched. */
 
 /* ---- finer-grained entry points (unit tests, and the decode_head plugin surface) ------------- */
 

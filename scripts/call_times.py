@@ -6,6 +6,7 @@ next while every tagged kernel took the same time - which calls are slow, and wh
   python scripts/call_times.py --workload bev_fusion_k3_8x200x200 fused= unfused=DDP_TAIL_FUSED=0 --calls 40 --blocks 3
   python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= free=DDP_X0_HINTS=free sparse=DDP_X0_HINTS=sparse
   python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= prior=DDP_PRIOR_START=1.0 --tags
+  python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= cprior=DDP_CLASS_PRIOR=1 --calls 20 --blocks 2 --tags
 
 Per variant and block: the sorted per-call HIP-event times, their median / min / max, the mean power and clock over the block."""
 import argparse
@@ -55,8 +56,17 @@ def main():
         # DDP_PRIOR_START=<t_start>: DDP_FLAG_PRIOR_START set, the chain started from a seeded prior map noised to t_start (1.0: the same
         # K steps as the default path, so the difference between the variants is the start-map kernel) - likewise a switch of this script
         pk = os.environ.get('DDP_PRIOR_START')
+        # DDP_CLASS_PRIOR=1: DDP_FLAG_CLASS_PRIOR set (seg), a seeded soft table (+-3 on a third of the classes, another row per image) -
+        # likewise a switch of this script
+        ck = os.environ.get('DDP_CLASS_PRIOR', '0') not in ('', '0')
         engines[name] = DDPEngine(sd, task, **(dict(x0_hints=True) if hk else {}), **(dict(prior_start=True, t_start=float(pk)) if pk else {}),
-                                  **kw)
+                                  **(dict(class_prior=True) if ck else {}), **kw)
+        if ck:
+            g = torch.Generator().manual_seed(9)
+            shape = (wl['batch'], wl['num_classes'])
+            on = torch.rand(shape, generator=g) < 1.0 / 3.0
+            table = torch.where(on, torch.where(torch.rand(shape, generator=g) < 0.5, torch.tensor(3.0), torch.tensor(-3.0)), torch.tensor(0.0))
+            engines[name].set_class_prior(table.to(dev))
         if pk:
             g = torch.Generator().manual_seed(8)
             shape = (wl['batch'], wl['h'], wl['w'])
