@@ -68,17 +68,39 @@ namespace {
 
 inline size_t align64(size_t floats) { return (floats + 63) & ~size_t(63); }  // 256-byte granules
 
-struct Carve {
-  float* base;
+// The one workspace carver: consecutive regions of `count` elements of T, each rounded up to a 256-byte granule.  A null base
+// carves sizes only - every take() returns nullptr and `off` ends at the byte count (the *_workspace queries).  With a base,
+// take(0) is a non-null pointer of zero length: "carved but empty" and "not carved" (nullptr) stay different things.
+struct Carver {
+  char* base;
   size_t off = 0;
-  float* take(size_t floats) {
-    float* p = base ? base + off : nullptr;
-    off += align64(floats);
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += (count * sizeof(T) + 255) / 256 * 256;
     return p;
   }
 };
 
-struct Layout {
+// The caller-visible tail of a sampler workspace (ddp_sample and ddp_sample_fcn): the buffers the caller reads or writes directly,
+// each present only with its flag (include/ddp_mi355x.h, at ddp_query_workspace)
+struct CallerRegions {
+  // DDP_FLAG_CLASS_PRIOR: the caller-written table (B, 256) and the per-image vectors k_class_prior writes: (B, 256) bias + prior rows
+  // (the seg tails' accumulator start), then (B, 256) prior rows (k_seg_update's addend)
+  float *cprior_rows = nullptr, *cprior_table = nullptr;
+  // DDP_FLAG_PRIOR_START: the caller-written prior map (B, N) - seg uint8, depth fp32, bev uint32 - and the start map (B, r, Cm, h, w)
+  // k_prior_start_* writes (without DDP_FLAG_SEEDED_NOISE; with it seed_noise is the start map, mixed in place)
+  float* prior_start = nullptr;
+  void* prior_map = nullptr;
+  // DDP_FLAG_X0_HINTS: the caller-written hint map (B, N) - seg uint8, depth fp32 - and its per-row form (M0), written by k_hint_rows_*
+  void *hint_rows = nullptr, *hint_map = nullptr;
+  float* seed_noise = nullptr;   // DDP_FLAG_SEEDED_NOISE: (B, r, Cm, h, w) start noise of the call, written by k_noise_fill_nchw
+  // DDP_FLAG_STEP_RECORD: the record (K, M) - seg uint8, depth fp32, bev uint32 - and the disagreement map (B, Nh)
+  unsigned char* step_rec = nullptr;
+  float* step_map = nullptr;
+};
+
+struct Layout : CallerRegions {
   // dims
   int B, r, K, L, Kc, Cx, Cm, h, w, hh, wh, N, Nh, R;
   size_t M0, M;   // tokens at (h,w) and at the head grid, over all B*r maps
@@ -92,22 +114,7 @@ struct Layout {
         *s = nullptr, *samp = nullptr, *hbuf = nullptr, *logits = nullptr, *prob = nullptr, *snoise = nullptr, *xtok = nullptr;
   // bf16x3 mode: split weights and split fragment-major activations
   int b3;
-  unsigned char* x0_trace = nullptr;   // DDP_FLAG_RECORD_X0: (K, M) argmax class of every step
-  // DDP_FLAG_STEP_RECORD: the record (K, M) - seg uint8 (== x0_trace), depth fp32, bev uint32 - and the disagreement map (B, Nh)
-  unsigned char* step_rec = nullptr;
-  float* step_map = nullptr;
-  float* seed_noise = nullptr;   // DDP_FLAG_SEEDED_NOISE: (B, r, Cm, h, w) start noise of the call, written by k_noise_fill_nchw
-  // DDP_FLAG_X0_HINTS: the caller-written hint map (B, N) - seg uint8, depth fp32 - and its per-row form (M0), written by k_hint_rows_*
-  void* hint_map = nullptr;
-  void* hint_rows = nullptr;
-  // DDP_FLAG_PRIOR_START: the caller-written prior map (B, N) - seg uint8, depth fp32, bev uint32 - and the start map (B, r, Cm, h, w)
-  // k_prior_start_* writes (without DDP_FLAG_SEEDED_NOISE; with it seed_noise is the start map, mixed in place)
-  void* prior_map = nullptr;
-  float* prior_start = nullptr;
-  // DDP_FLAG_CLASS_PRIOR: the caller-written table (B, 256) and the per-image vectors k_class_prior writes: (B, 256) bias + prior rows
-  // (the seg tails' accumulator start), then (B, 256) prior rows (k_seg_update's addend)
-  float* cprior_table = nullptr;
-  float* cprior_rows = nullptr;
+  unsigned char* x0_trace = nullptr;   // DDP_FLAG_RECORD_X0: (K, M) argmax class of every step (seg with DDP_FLAG_STEP_RECORD: == step_rec)
   bool fused_layer, fused_pro;   // bf16x3: persistent layer kernel / step-prologue kernel in use (cfg->flags)
   bool guess_zero;               // DDP_FLAG_GATHER_GUESS_ZERO
   SplitW wp_x, wp_m, wp_head, wp_v[DDP_MAX_LAYERS], wp_cat[DDP_MAX_LAYERS], wp_o[DDP_MAX_LAYERS], wp_f0[DDP_MAX_LAYERS],
@@ -307,8 +314,42 @@ inline size_t step_record_bytes(const ddp_cfg* c) {
   return size_t(c->timesteps) * c->batch * c->randsteps * c->head_h * c->head_w * (c->task == DDP_TASK_SEG ? 1 : 4);
 }
 
-void carve(const ddp_cfg* c, float* base, Layout* o) {
-  Carve cv{base};
+// The tail of a sampler workspace, in its one fixed order (the ordered list of include/ddp_mi355x.h at ddp_query_workspace; the same
+// table on the host side: ddp_amd.engine.caller_regions).  Every group exists only with its flag, so every offset in front of a group
+// is the one of the cfg without that flag:
+//   class prior    the private per-image vectors, then the caller's table
+//   prior start    the start map (only without DDP_FLAG_SEEDED_NOISE: with it the seeded-noise buffer is the start map), then the
+//                  caller's prior map
+//   x0 hints       the private row buffer, then the caller's map
+//   seeded noise   the start noise of the call
+//   step record    the record, then the disagreement map: the LAST two buffers
+// ddp_sample_fcn refuses the first three flags (validate_fcn_loop): its tail is the last two groups.
+void carve_caller_regions(const ddp_cfg* c, Carver& cv, CallerRegions* o) {
+  const size_t B = c->batch, BN = B * c->h * c->w, M0 = BN * c->randsteps;
+  const size_t Cm = c->task == DDP_TASK_DEPTH ? 1 : 256;      // channels of the noisy map
+  const size_t px = c->task == DDP_TASK_SEG ? 1 : 4;          // bytes per pixel of a hint / prior map: uint8 classes, else fp32 / uint32
+  if (c->flags & DDP_FLAG_CLASS_PRIOR) {
+    o->cprior_rows = cv.take<float>(2 * B * 256);
+    o->cprior_table = cv.take<float>(B * 256);
+  }
+  if (c->flags & DDP_FLAG_PRIOR_START) {
+    if (!(c->flags & DDP_FLAG_SEEDED_NOISE)) o->prior_start = cv.take<float>(M0 * Cm);
+    o->prior_map = cv.take<unsigned char>(BN * px);
+  }
+  if (c->flags & DDP_FLAG_X0_HINTS) {
+    o->hint_rows = cv.take<unsigned char>(M0 * px);
+    o->hint_map = cv.take<unsigned char>(BN * px);
+  }
+  if (c->flags & DDP_FLAG_SEEDED_NOISE) o->seed_noise = cv.take<float>(M0 * Cm);
+  if (c->flags & DDP_FLAG_STEP_RECORD) {
+    o->step_rec = cv.take<unsigned char>(step_record_bytes(c));
+    o->step_map = cv.take<float>(B * c->head_h * c->head_w);
+  }
+}
+
+void carve(const ddp_cfg* c, char* base, Layout* o) {
+  Carver cv{base};
+  auto takeb = [&](size_t nbytes) { return cv.take<unsigned char>(nbytes); };
   o->B = c->batch;
   o->r = c->randsteps;
   o->K = c->timesteps;
@@ -329,27 +370,27 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   // ---- region A: MODEL constants.  Sizes depend on (task, K, L, K_cls, Cx, gemm_mode) only - not on batch, r or the map
   // size - so this prefix of the workspace stays valid when only the geometry changes (ddp_prepare_geometry): the
   // reference's own test protocol is one image per call with a new (h, w) almost every call (tools/test.py:214-219)
-  o->tin = cv.take(DDP_MAX_STEPS);
-  o->u = cv.take(size_t(o->K) * DDP_SINU_FEATS);
-  o->hid = cv.take(size_t(o->K) * DDP_TIME_DIM);
-  o->temb = cv.take(size_t(o->K) * DDP_TIME_DIM);
-  o->film = cv.take(size_t(o->K) * o->L * 512);
-  o->aff = cv.take(size_t(o->K) * o->L * 512);   // norms.1 affine x FiLM per (step, layer)
-  o->lut = cv.take(size_t(o->Kc + 1) * 256);
-  o->wx = cv.take(size_t(256) * o->Cx);
-  o->wm = cv.take(size_t(256) * o->Cm);
-  o->wtap = cv.take(size_t(9) * 256);
+  o->tin = cv.take<float>(DDP_MAX_STEPS);
+  o->u = cv.take<float>(size_t(o->K) * DDP_SINU_FEATS);
+  o->hid = cv.take<float>(size_t(o->K) * DDP_TIME_DIM);
+  o->temb = cv.take<float>(size_t(o->K) * DDP_TIME_DIM);
+  o->film = cv.take<float>(size_t(o->K) * o->L * 512);
+  o->aff = cv.take<float>(size_t(o->K) * o->L * 512);   // norms.1 affine x FiLM per (step, layer)
+  o->lut = cv.take<float>(size_t(o->Kc + 1) * 256);
+  o->wx = cv.take<float>(size_t(256) * o->Cx);
+  o->wm = cv.take<float>(size_t(256) * o->Cm);
+  o->wtap = cv.take<float>(size_t(9) * 256);
   o->nbins = c->task == DDP_TASK_DEPTH ? c->depth_n_bins : 0;
   o->seg3 = c->task == DDP_TASK_BEV && c->bev_seg_kernel == 3;
   o->prescale = c->task == DDP_TASK_BEV && bev_prescaled(c);
   const bool conv3 = o->nbins || o->seg3;     // a 3x3 head convolution to more than one channel
-  o->bins_tab = o->nbins ? cv.take(DDP_MAX_DEPTH_BINS) : nullptr;
-  o->bins_bias = conv3 ? cv.take(256) : nullptr;
-  o->bins_wpack = conv3 ? cv.take(size_t(256) * 2304) : nullptr;
+  o->bins_tab = o->nbins ? cv.take<float>(DDP_MAX_DEPTH_BINS) : nullptr;
+  o->bins_bias = conv3 ? cv.take<float>(256) : nullptr;
+  o->bins_wpack = conv3 ? cv.take<float>(size_t(256) * 2304) : nullptr;
   for (int l = 0; l < DDP_MAX_LAYERS; ++l) {
     const bool on = l < o->L;
-    o->wcat[l] = on ? cv.take(96 * 256) : nullptr;
-    o->bcat[l] = on ? cv.take(96) : nullptr;
+    o->wcat[l] = on ? cv.take<float>(96 * 256) : nullptr;
+    o->bcat[l] = on ? cv.take<float>(96) : nullptr;
   }
   o->b3 = c->gemm_mode == DDP_GEMM_BF16X3;
   o->guess_zero = (c->flags & DDP_FLAG_GATHER_GUESS_ZERO) != 0;
@@ -357,10 +398,10 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   o->fused_pro = o->fused_layer && !(c->flags & DDP_FLAG_UNFUSED_PROLOGUE);
   const bool segp = c->task == DDP_TASK_SEG;
   if (o->b3) {
-    // split weights: 3 bf16 per fp32 = 1.5 floats per element
+    // split weights: 3 bf16 planes per fp32 element = 6 bytes
     auto takew = [&](size_t rows, size_t K) {
       SplitW w;
-      w.p = reinterpret_cast<unsigned short*>(cv.take((rows * K * 3 + 1) / 2));
+      w.p = cv.take<unsigned short>(rows * K * 3);
       w.comp_stride = rows * K;
       return w;
     };
@@ -375,56 +416,57 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
       o->wp_o[l] = takew(256, 256);
       o->wp_f0[l] = takew(DDP_FFN, 256);
       o->wp_f1[l] = takew(256, DDP_FFN);
-      o->wstream[l] = reinterpret_cast<unsigned char*>(cv.take(b3_layer_stream_bytes() / sizeof(float)));
-      o->bias_ext[l] = cv.take(size_t(b3_layer_bias_floats()));
+      o->wstream[l] = takeb(b3_layer_stream_bytes());
+      o->bias_ext[l] = cv.take<float>(size_t(b3_layer_bias_floats()));
     }
-    o->tail_stream = reinterpret_cast<unsigned char*>(cv.take(size_t(8) * 48 * 1024 / sizeof(float)));
-    o->tail_bias = cv.take(size_t(b3_layer_bias_floats()));
-    o->pro_stream = reinterpret_cast<unsigned char*>(cv.take(b3_prologue_stream_bytes() / sizeof(float)));
-    o->pro_bias = cv.take(size_t(b3_layer_bias_floats()));
-    o->tail4_stream = reinterpret_cast<unsigned char*>(cv.take(segp ? size_t(8 + 11) * 48 * 1024 / sizeof(float) : 0));
-    o->tail4_bias = cv.take(segp ? size_t(b3_layer_bias_floats()) : 0);
-    o->head7_stream = (segp && o->Cx == 256) ? reinterpret_cast<unsigned char*>(cv.take(size_t(8 + 8 + 11) * 48 * 1024 / sizeof(float))) : nullptr;
+    o->tail_stream = takeb(size_t(8) * 48 * 1024);
+    o->tail_bias = cv.take<float>(size_t(b3_layer_bias_floats()));
+    o->pro_stream = takeb(b3_prologue_stream_bytes());
+    o->pro_bias = cv.take<float>(size_t(b3_layer_bias_floats()));
+    o->tail4_stream = takeb(segp ? size_t(8 + 11) * 48 * 1024 : 0);
+    o->tail4_bias = cv.take<float>(segp ? size_t(b3_layer_bias_floats()) : 0);
+    o->head7_stream = (segp && o->Cx == 256) ? takeb(size_t(8 + 8 + 11) * 48 * 1024) : nullptr;
     // last layer + tail (k_layer MODE 6 / 8 / 9): seg 72 + 2 * chunks + 11 images, bev (<= 32 classes) and depth (9 taps) 72 + 2
     // (not for the 3x3 conv_seg of the bev head: its last layer is a plain layer, no tail stream is built or read)
     const bool lt = o->L >= 1 && (segp ? b3_layer_tail_supported(o->Kc) : o->Kc <= 32) && !o->seg3;
-    o->lt_stream = lt ? reinterpret_cast<unsigned char*>(cv.take(size_t(segp ? 72 + 8 + 11 : 72 + 2) * 48 * 1024 / sizeof(float))) : nullptr;
-    o->lt_bias = lt ? cv.take(size_t(b3_layer_bias_floats())) : nullptr;
+    o->lt_stream = lt ? takeb(size_t(segp ? 72 + 8 + 11 : 72 + 2) * 48 * 1024) : nullptr;
+    o->lt_bias = lt ? cv.take<float>(size_t(b3_layer_bias_floats())) : nullptr;
     const bool bev_tab = c->task == DDP_TASK_BEV && o->Kc <= 8;
-    o->tlut = cv.take(segp ? size_t(o->Kc + 1) * 256 : bev_tab ? (size_t(1) << o->Kc) * 256 : 0);
-    o->lut64 = bev_tab ? cv.take((size_t(1) << o->Kc) * 256) : nullptr;
-    o->wvs = c->task == DDP_TASK_DEPTH ? cv.take(512) : nullptr;
-    o->bins_wsplit = conv3 ? reinterpret_cast<unsigned short*>(cv.take(size_t(256) * 2304 * 3 / 2)) : nullptr;
-    o->bins_stream = conv3 ? reinterpret_cast<unsigned char*>(cv.take(size_t(72) * 48 * 1024 / sizeof(float))) : nullptr;
+    o->tlut = cv.take<float>(segp ? size_t(o->Kc + 1) * 256 : bev_tab ? (size_t(1) << o->Kc) * 256 : 0);
+    o->lut64 = bev_tab ? cv.take<float>((size_t(1) << o->Kc) * 256) : nullptr;
+    o->wvs = c->task == DDP_TASK_DEPTH ? cv.take<float>(512) : nullptr;
+    o->bins_wsplit = conv3 ? cv.take<unsigned short>(size_t(256) * 2304 * 3) : nullptr;
+    o->bins_stream = conv3 ? takeb(size_t(72) * 48 * 1024) : nullptr;
   }
-  o->const_bytes = cv.off * sizeof(float);
+  o->const_bytes = cv.off;
   // ---- region B: everything that depends on the geometry (batch, r, map size): positional tables, activations
   for (int l = 0; l < DDP_MAX_LAYERS; ++l) {
     const bool on = l < o->L;
-    o->py[l] = on ? cv.take(size_t(o->hh) * 96) : nullptr;
-    o->px[l] = on ? cv.take(size_t(o->wh) * 96) : nullptr;
+    o->py[l] = on ? cv.take<float>(size_t(o->hh) * 96) : nullptr;
+    o->px[l] = on ? cv.take<float>(size_t(o->wh) * 96) : nullptr;
   }
-  o->xproj = cv.take((size_t(o->B) * o->N + 127) / 128 * 128 * 256);      // (whole tiles: the first step's head may write it fragment-major)
-  o->mask = cv.take(o->M0 * (c->task == DDP_TASK_DEPTH ? 1 : 256));
-  o->pred = cv.take(c->task == DDP_TASK_DEPTH ? o->M0 : 0);
-  o->feat0 = cv.take(c->task == DDP_TASK_BEV ? o->M0 * 256 : 0);
-  const size_t Mp = (o->M + 255) / 256 * 256;        // fragment-major buffers hold whole block tiles (128 / 256 tokens)
-  o->q = cv.take(Mp * 256);                          // fragment-major
-  o->q1 = cv.take(Mp * 256);                         // fragment-major
-  o->v = cv.take(o->M * 256);                        // row-major (gather taps want a head's 128 B contiguous)
-  o->s = cv.take(o->M * 256);                        // row-major
-  o->samp = cv.take(o->M * DDP_SAMP_STRIDE);
-  size_t hb = Mp * DDP_FFN;                          // fragment-major
+  // (xproj in whole tiles: the first step's head may write it fragment-major)
+  o->xproj = cv.take<float>((size_t(o->B) * o->N + 127) / 128 * 128 * 256);
+  o->mask = cv.take<float>(o->M0 * (c->task == DDP_TASK_DEPTH ? 1 : 256));
+  o->pred = cv.take<float>(c->task == DDP_TASK_DEPTH ? o->M0 : 0);
+  o->feat0 = cv.take<float>(c->task == DDP_TASK_BEV ? o->M0 * 256 : 0);
+  const size_t Mp = (o->M + 255) / 256 * 256;               // fragment-major buffers hold whole block tiles (128 / 256 tokens)
+  o->q = cv.take<float>(Mp * 256);                          // fragment-major
+  o->q1 = cv.take<float>(Mp * 256);                         // fragment-major
+  o->v = cv.take<float>(o->M * 256);                        // row-major (gather taps want a head's 128 B contiguous)
+  o->s = cv.take<float>(o->M * 256);                        // row-major
+  o->samp = cv.take<float>(o->M * DDP_SAMP_STRIDE);
+  size_t hb = Mp * DDP_FFN;                                 // fragment-major
   const size_t xt = size_t(o->B) * o->N * o->Cx;
   if (xt > hb) hb = xt;
-  o->hbuf = cv.take(hb);
+  o->hbuf = cv.take<float>(hb);
   o->xtok = o->hbuf;  // x in token-major form is dead once xproj exists
   // (seg: the layer kernel's tails keep scores / probabilities fragment-major: whole 128-token TILES x whole 64-class chunks -
   // the wholly invalid waves of the last tile pre-load their groups' accumulators like every other wave)
   const size_t pfl = c->task == DDP_TASK_SEG ? (o->M + 127) / 128 * 128 * size_t((o->Kc + 63) / 64 * 64) : 0;
-  o->logits = cv.take(o->M * o->ldl > pfl ? o->M * o->ldl : pfl);
-  o->prob = cv.take(o->M * o->ldl > pfl ? o->M * o->ldl : pfl);
-  o->snoise = cv.take(c->sampler == DDP_SAMPLER_DDPM ? o->M0 * 256 : 0);
+  o->logits = cv.take<float>(o->M * o->ldl > pfl ? o->M * o->ldl : pfl);
+  o->prob = cv.take<float>(o->M * o->ldl > pfl ? o->M * o->ldl : pfl);
+  o->snoise = cv.take<float>(c->sampler == DDP_SAMPLER_DDPM ? o->M0 * 256 : 0);
   // binned depth head: bf16x3 - the stream GEMM writes the logits fp32 fragment-major with 256 channels (rows padded to 256);
   // fp32 engine - the layer output on a zero-bordered grid (+ guard rows: the nine taps are row offsets of up to w + 3) and the
   // logits on that grid, rows of bins_ld floats
@@ -434,10 +476,10 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
   if (conv3) {
     const size_t padded = size_t(o->R) * (o->hh + 2) * (o->wh + 2);
     if (o->b3) {
-      o->bins_logits = cv.take(Mp * 256);
+      o->bins_logits = cv.take<float>(Mp * 256);
     } else {
-      o->bins_in = cv.take((padded + 2 * size_t(o->bins_guard)) * 256);
-      o->bins_logits = cv.take(padded * o->bins_ld);
+      o->bins_in = cv.take<float>((padded + 2 * size_t(o->bins_guard)) * 256);
+      o->bins_logits = cv.take<float>(padded * o->bins_ld);
     }
   }
   // prescaled map: R row-major maps of (hp, wp) x 256 floats, whole 4-token blocks as k_bev_prescale writes them
@@ -445,22 +487,21 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
     o->hp = int(bev_prescaled_len(c, c->h));
     o->wp = int(bev_prescaled_len(c, c->w));
     o->pre_rscale = float(1.0 / double(c->bev_prescale));
-    o->pre = cv.take((size_t(o->R) * o->hp * o->wp + 3) / 4 * 4 * 256);
+    o->pre = cv.take<float>((size_t(o->R) * o->hp * o->wp + 3) / 4 * 4 * 256);
   }
-  o->x0_trace = reinterpret_cast<unsigned char*>(
-      cv.take((c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) && c->task == DDP_TASK_SEG && !(c->flags & DDP_FLAG_STEP_RECORD)
-                  ? ((c->flags & DDP_FLAG_FORCE_X0 ? 2 : 1) * size_t(o->K) * o->M + 3) / 4
-                  : 0));
+  o->x0_trace = takeb((c->flags & (DDP_FLAG_RECORD_X0 | DDP_FLAG_FORCE_X0)) && c->task == DDP_TASK_SEG && !(c->flags & DDP_FLAG_STEP_RECORD)
+                           ? (c->flags & DDP_FLAG_FORCE_X0 ? 2 : 1) * size_t(o->K) * o->M
+                           : 0);
   if (o->b3) {
     auto takesb = [&](size_t rows, size_t C) {       // SB: 6 bytes per element, rows padded to 256
       const size_t rp = (rows + 255) / 256 * 256;
-      return reinterpret_cast<unsigned short*>(cv.take((rp * C * 3 + 1) / 2));
+      return cv.take<unsigned short>(rp * C * 3);
     };
     // + one more zero row: a sample clamped to y = h reads (with weight 0) the row below the bottom border, which for the
     // last map would otherwise be whatever follows in the workspace (0 x NaN = NaN)
     o->vpad_floats = (size_t(o->R) * (o->hh + 2) + 1) * (o->wh + 2) * 256 + 256;
-    o->vpad = cv.take(o->vpad_floats);
-    o->ubuf = cv.take(segp ? (o->M + 255) / 256 * 256 * 256 : 0);
+    o->vpad = cv.take<float>(o->vpad_floats);
+    o->ubuf = cv.take<float>(segp ? (o->M + 255) / 256 * 256 * 256 : 0);
     o->q_sb = takesb(o->M, 256);
     o->q1_sb = takesb(o->M, 256);
     o->s_sb = takesb(o->M, 256);
@@ -485,35 +526,10 @@ void carve(const ddp_cfg* c, float* base, Layout* o) {
       o->rvpad = o->rs0 + align64(o->M * 96);
     }
   }
-  // seeded start noise: immediately in front of the step-record buffers (the end of the workspace without them), so that the record
-  // and the map stay the last of the workspace and every other offset is the one of the cfg without the flag
-  // prior start: the start map (only without DDP_FLAG_SEEDED_NOISE), then the caller's prior map, in front of the x0-hint buffers
-  // (include/ddp_mi355x.h, "prior start")
-  // class prior: the private per-image vectors, then the caller's table, in front of the prior-start buffers (include/ddp_mi355x.h,
-  // "class prior")
-  if (c->flags & DDP_FLAG_CLASS_PRIOR) {
-    o->cprior_rows = cv.take(size_t(2) * o->B * 256);
-    o->cprior_table = cv.take(size_t(o->B) * 256);
-  }
-  if (c->flags & DDP_FLAG_PRIOR_START) {
-    if (!(c->flags & DDP_FLAG_SEEDED_NOISE)) o->prior_start = cv.take(o->M0 * o->Cm);
-    o->prior_map = cv.take(c->task == DDP_TASK_SEG ? (size_t(o->B) * o->N + 3) / 4 : size_t(o->B) * o->N);
-  }
-  // x0 hints: the private row buffer, then the caller's map immediately in front of the seeded-noise buffer (include/ddp_mi355x.h)
-  if (c->flags & DDP_FLAG_X0_HINTS) {
-    const bool bytes1 = c->task == DDP_TASK_SEG;
-    o->hint_rows = cv.take(bytes1 ? (o->M0 + 3) / 4 : o->M0);
-    o->hint_map = cv.take(bytes1 ? (size_t(o->B) * o->N + 3) / 4 : size_t(o->B) * o->N);
-  }
-  if (c->flags & DDP_FLAG_SEEDED_NOISE) o->seed_noise = cv.take(o->M0 * o->Cm);
-  // step record + disagreement map: the LAST two buffers, so that every offset in front of them is the one of the cfg without
-  // the flag.  (seg with DDP_FLAG_RECORD_X0 as well: one buffer serves both flags - the x0 trace moves here)
-  if (c->flags & DDP_FLAG_STEP_RECORD) {
-    o->step_rec = reinterpret_cast<unsigned char*>(cv.take((step_record_bytes(c) + 3) / 4));
-    o->step_map = cv.take(size_t(o->B) * o->Nh);
-    if (c->task == DDP_TASK_SEG) o->x0_trace = o->step_rec;
-  }
-  o->total = cv.off * sizeof(float);
+  // (seg with DDP_FLAG_STEP_RECORD and DDP_FLAG_RECORD_X0: one buffer serves both flags - the x0 trace moves into the record)
+  carve_caller_regions(c, cv, o);
+  if (o->step_rec && c->task == DDP_TASK_SEG) o->x0_trace = o->step_rec;
+  o->total = cv.off;
 }
 
 // `o` given: the geometry of the grid RESAMPLING, whose source is the prescaled map when there is one
@@ -530,6 +546,15 @@ BevGeom bev_geom(const ddp_cfg* c, const Layout* o = nullptr) {
     g.out_step[a] = c->bev_out_step[a];
   }
   return g;
+}
+
+// the out-parameter of a *_workspace query
+int check_bytes(const size_t* bytes) {
+  if (!bytes) {
+    set_error("bytes is NULL");
+    return DDP_E_NULL;
+  }
+  return DDP_OK;
 }
 
 int check_ptr(const void* p, const char* name) {
@@ -1151,7 +1176,8 @@ int seeded_start_noise(const uint32_t* key, float* buf, int B, size_t per_image,
   return recorded(launch_noise_fill_nchw(key, buf, B, per_image, st), st);
 }
 
-int step_disagreement(const ddp_cfg* c, const Layout& o, const float* d_out, hipStream_t st) {
+// (`threshold` is read for bev only; ddp_sample passes cfg->threshold, the FCN loop 0)
+int step_disagreement(const ddp_cfg* c, const CallerRegions& o, float threshold, const float* d_out, hipStream_t st) {
   if (!o.step_rec) return DDP_OK;
   prof_begin(TAG_GENERIC, st);
   StepDisagreementArgs a{};
@@ -1159,13 +1185,23 @@ int step_disagreement(const ddp_cfg* c, const Layout& o, const float* d_out, hip
   a.out = d_out;
   a.map = o.step_map;
   a.task = c->task;
-  a.B = o.B;
-  a.r = o.r;
-  a.K = o.K;
-  a.N = o.Nh;
-  a.num_classes = o.Kc;
-  a.threshold = c->threshold;
+  a.B = c->batch;
+  a.r = c->randsteps;
+  a.K = c->timesteps;
+  a.N = c->head_h * c->head_w;
+  a.num_classes = c->task == DDP_TASK_DEPTH ? 1 : c->num_classes;
+  a.threshold = threshold;
   return recorded(launch_step_disagreement(a, st), st);
+}
+
+// DDPM: the noise added after step s, token-major (B * r * N, 256) in `snoise`.  DDP_FLAG_SEEDED_NOISE (key): generated that way - no
+// NCHW tensor, no transpose; else the transpose of slice s of the caller's (K, B, r, 256, h, w) tensor
+int stage_step_noise(const uint32_t* key, const float* d_step_noise, float* snoise, int B, int r, int N, int s, hipStream_t st) {
+  if (key) {
+    prof_begin(TAG_GENERIC, st);
+    return recorded(launch_noise_fill_tok(key, snoise, B, r, N, s, st), st);
+  }
+  return launch_nchw_to_tok(d_step_noise + size_t(s) * B * r * N * 256, snoise, B * r, 256, N, st);
 }
 
 // the segmentation sampler after the xproj hoist: noise staging, K steps, reduction
@@ -1264,14 +1300,9 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
         const float ua = (1.0f - sp.ddpm_c) / sp.alpha * sp.alpha_next, uc = sp.ddpm_c * sp.alpha_next;
         const bool noisy = sp.ddpm_add_noise != 0;
         if (noisy) {
-          // the step's noise token-major (seeded: generated that way), then U <- ua' U + std (E W_m^T): u_s is complete (step 0's head
-          // / the previous tail wrote it) and this step's tail, inside the last layer's kernel or behind it, has not run yet
-          if (key) {
-            prof_begin(TAG_GENERIC, st);
-            DDP_TRY(recorded(launch_noise_fill_tok(key, o.snoise, o.B, o.r, o.N, s, st), st));
-          } else {
-            DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
-          }
+          // the step's noise token-major, then U <- ua' U + std (E W_m^T): u_s is complete (step 0's head / the previous tail wrote
+          // it) and this step's tail, inside the last layer's kernel or behind it, has not run yet
+          DDP_TRY(stage_step_noise(key, d_step_noise, o.snoise, o.B, o.r, o.N, s, st));
           prof_begin(TAG_GENERIC, st);
           DDP_TRY(recorded(launch_u_noise(o.ubuf, o.snoise, o.wm, M0, ua, sp.ddpm_std, st), st));
         }
@@ -1297,12 +1328,7 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
     a.cp_delta = o.cprior_rows ? o.cprior_rows + size_t(o.B) * 256 : nullptr;
     a.cp_rn = o.r * o.N;
     if (c->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
-      if (key) {   // DDP_FLAG_SEEDED_NOISE: the step's noise is generated token-major - no NCHW tensor, no transpose
-        prof_begin(TAG_GENERIC, st);
-        DDP_TRY(recorded(launch_noise_fill_tok(key, o.snoise, o.B, o.r, o.N, s, st), st));
-      } else {
-        DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M0 * 256, o.snoise, o.R, 256, o.N, st));
-      }
+      DDP_TRY(stage_step_noise(key, d_step_noise, o.snoise, o.B, o.r, o.N, s, st));
       a.step_noise = o.snoise;
     }
     DDP_TRY(launch_seg_update(a, st));
@@ -1311,7 +1337,7 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
   const int frag_nch = p.seg_tail ? (o.Kc + 63) / 64 : 0;
   if (c->accumulation) DDP_TRY(launch_finalize_nchw(o.prob, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st, frag_nch));
   else DDP_TRY(launch_finalize_nchw(o.logits, o.ldl, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r), st, frag_nch));
-  return step_disagreement(c, o, d_out, st);
+  return step_disagreement(c, o, c->threshold, d_out, st);
 }
 
 // the depth sampler after the xproj hoist: noise staging, loop invariants of the chain, K steps, mean over r
@@ -1411,7 +1437,7 @@ int sample_depth(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, 
     }
   }
   DDP_TRY(launch_mean_r(pred, d_out, o.B, o.r, o.N, st));
-  return step_disagreement(c, o, d_out, st);
+  return step_disagreement(c, o, c->threshold, d_out, st);
 }
 
 // the BEV sampler after the xproj hoist: noise staging (u_0 on the chain), K steps, reduction
@@ -1504,7 +1530,7 @@ int sample_bev(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
     DDP_TRY(launch_bev_update(bev_update_args(c, w, o, o.mask, s == 0, sp), st));
   }
   DDP_TRY(launch_finalize_nchw(o.prob, 32, d_out, o.B, o.r, o.Nh, o.Kc, float(o.r * o.K), st));
-  return step_disagreement(c, o, d_out, st);
+  return step_disagreement(c, o, c->threshold, d_out, st);
 }
 
 }  // namespace
@@ -1580,10 +1606,7 @@ int ddp_profile_read(int tag, float* total_ms, int* launches) {
 
 int ddp_query_workspace(const ddp_cfg* cfg, size_t* bytes) {
   DDP_TRY(validate(cfg));
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   Layout o;
   carve(cfg, nullptr, &o);
   *bytes = o.total;
@@ -1601,7 +1624,7 @@ int ddp_prepare(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* 
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout o;
-  carve(cfg, static_cast<float*>(d_workspace), &o);
+  carve(cfg, static_cast<char*>(d_workspace), &o);
   DDP_TRY(prepare_model(cfg, weights, o, st));
   DDP_TRY(prepare_geometry(o, st));
   float tin[DDP_MAX_STEPS];
@@ -1614,10 +1637,7 @@ int ddp_prepare(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* 
 
 int ddp_query_const_workspace(const ddp_cfg* cfg, size_t* bytes) {
   DDP_TRY(validate(cfg));
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   Layout o;
   carve(cfg, nullptr, &o);
   *bytes = o.const_bytes;
@@ -1628,7 +1648,7 @@ int ddp_prepare_geometry(const ddp_cfg* cfg, void* d_workspace, void* stream) {
   DDP_TRY(validate(cfg));
   DDP_TRY(check_ptr(d_workspace, "workspace"));
   Layout o;
-  carve(cfg, static_cast<float*>(d_workspace), &o);
+  carve(cfg, static_cast<char*>(d_workspace), &o);
   return prepare_geometry(o, static_cast<hipStream_t>(stream));
 }
 
@@ -1648,7 +1668,7 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
   if (cfg->sampler == DDP_SAMPLER_DDPM && !seeded) DDP_TRY(check_ptr(d_step_noise, "step_noise"));
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout o;
-  carve(cfg, static_cast<float*>(d_workspace), &o);
+  carve(cfg, static_cast<char*>(d_workspace), &o);
   const Plan p = plan_of(cfg, o);
   // DDP_FLAG_X0_HINTS: the caller's map as read NOW (a captured graph replays this launch on the buffer's current content) -> rows
   if (o.hint_rows) {
@@ -1716,7 +1736,7 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
     return DDP_E_BADCFG;
   }
   Layout o;
-  carve(cfg, static_cast<float*>(d_workspace), &o);
+  carve(cfg, static_cast<char*>(d_workspace), &o);
   *d_idx = step_rec ? o.step_rec : o.x0_trace;
   return DDP_OK;
 }
@@ -1738,7 +1758,7 @@ int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float
   DDP_TRY(check_ptr(d_out, "out"));
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout o;
-  carve(cfg, static_cast<float*>(d_workspace), &o);
+  carve(cfg, static_cast<char*>(d_workspace), &o);
   DDP_TRY(prepare_model(cfg, weights, o, st));
   DDP_TRY(prepare_geometry(o, st));
   const float* film = nullptr;
@@ -1799,29 +1819,21 @@ int msda_lds_layout(int rows, int h, int w, char* base, MsdaLdsLayout* o) {
     set_error("msda_lds: rows=%d must be a positive multiple of h*w=%d", rows, h * w);
     return DDP_E_BADCFG;
   }
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off += (nbytes + 255) / 256 * 256;
-    return p;
-  };
+  Carver cv{base};
   const size_t R = size_t(rows) / (size_t(h) * w);
   o->vpad_floats = (R * (h + 2) + 1) * (w + 2) * 256 + 256;      // + one zero row below the last map, as in the sampler's workspace
-  o->vpad = reinterpret_cast<float*>(take(o->vpad_floats * 4));
-  o->samp_hm = reinterpret_cast<float*>(take(size_t(rows) * DDP_SAMP_STRIDE * 4));
-  o->tab_y = reinterpret_cast<float*>(take(size_t(h) * 96 * 4));
-  o->tab_x = reinterpret_cast<float*>(take(size_t(w) * 96 * 4));
-  o->out_sb = reinterpret_cast<unsigned short*>(take((size_t(rows) + 255) / 256 * 256 * 256 * 6));
-  o->bytes = off;
+  o->vpad = cv.take<float>(o->vpad_floats);
+  o->samp_hm = cv.take<float>(size_t(rows) * DDP_SAMP_STRIDE);
+  o->tab_y = cv.take<float>(size_t(h) * 96);
+  o->tab_x = cv.take<float>(size_t(w) * 96);
+  o->out_sb = cv.take<unsigned short>((size_t(rows) + 255) / 256 * 256 * 256 * 3);
+  o->bytes = cv.off;
   return DDP_OK;
 }
 }  // namespace
 
 int ddp_msda_forward_lds_workspace(int rows, int h, int w, size_t* bytes) {
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   MsdaLdsLayout o;
   DDP_TRY(msda_lds_layout(rows, h, w, nullptr, &o));
   *bytes = o.bytes;
@@ -1874,24 +1886,16 @@ int linb3_layout(int m, int n, int k, char* base, LinB3Layout* o) {
     return DDP_E_BADCFG;
   }
   const size_t mp = (size_t(m) + 255) / 256 * 256;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off += (nbytes + 255) / 256 * 256;
-    return p;
-  };
-  o->a_sb = reinterpret_cast<unsigned short*>(take(mp * k * 6));
-  o->wsplit = reinterpret_cast<unsigned short*>(take(size_t(3) * n * k * 2));
-  o->bytes = off;
+  Carver cv{base};
+  o->a_sb = cv.take<unsigned short>(mp * k * 3);
+  o->wsplit = cv.take<unsigned short>(size_t(3) * n * k);
+  o->bytes = cv.off;
   return DDP_OK;
 }
 }  // namespace
 
 int ddp_linear_b3_workspace(int m, int n, int k, size_t* bytes) {
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   LinB3Layout o;
   DDP_TRY(linb3_layout(m, n, k, nullptr, &o));
   *bytes = o.bytes;
@@ -2104,37 +2108,26 @@ static int msm_layout(int batch, const int* lh, const int* lw, char* wbase, char
       set_error("neck_msm: level %d has size %dx%d", l, lh[l], lw[l]);
       return DDP_E_BADCFG;
     }
-  char* base = wbase;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off += (nbytes + 255) / 256 * 256;
-    return p;
-  };
-  o->wsplit = reinterpret_cast<unsigned short*>(take(size_t(3) * 256 * 256 * 2));
-  for (int l = 0; l < 4; ++l) o->stream[l] = reinterpret_cast<unsigned char*>(take(size_t(8) * b3_stage_bytes()));
-  o->wbytes = off;
-  base = abase;
-  off = 0;
+  Carver wv{wbase}, av{abase};
+  o->wsplit = wv.take<unsigned short>(size_t(3) * 256 * 256);
+  for (int l = 0; l < 4; ++l) o->stream[l] = wv.take<unsigned char>(size_t(8) * b3_stage_bytes());
+  o->wbytes = wv.off;
   for (int l = 0; l < 4; ++l) {
     const size_t M = size_t(batch) * lh[l] * lw[l], Mp = (M + 255) / 256 * 256;
-    o->a[l] = reinterpret_cast<float*>(take(Mp * 256 * sizeof(float)));
-    o->y[l] = reinterpret_cast<float*>(take(Mp * 256 * sizeof(float)));
+    o->a[l] = av.take<float>(Mp * 256);
+    o->y[l] = av.take<float>(Mp * 256);
   }
   const size_t chunks = (size_t(lh[0]) * lw[0] + 31) / 32;   // (32-token chunks: the merging kernel writes the statistics itself)
-  o->partial = reinterpret_cast<double*>(take(size_t(batch) * chunks * 64 * sizeof(double)));
-  o->stats = reinterpret_cast<float*>(take(size_t(batch) * 64 * sizeof(float)));
-  o->abytes = off;
+  o->partial = av.take<double>(size_t(batch) * chunks * 64);
+  o->stats = av.take<float>(size_t(batch) * 64);
+  o->abytes = av.off;
   o->bytes = o->wbytes + o->abytes;
   return DDP_OK;
 }
 }  // namespace
 
 int ddp_neck_msm_workspace(int batch, const int* level_h, const int* level_w, size_t* bytes) {
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   MsmLayout o;
   DDP_TRY(msm_layout(batch, level_h, level_w, nullptr, nullptr, &o));
   *bytes = o.bytes;
@@ -2223,13 +2216,7 @@ static int fpn_layout(const ddp_fpn_level* lv, int batch, char* wbase, char* aba
     set_error("neck_fpn: bad arguments");
     return DDP_E_BADCFG;
   }
-  char* base = wbase;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off += (nbytes + 255) / 256 * 256;
-    return p;
-  };
+  Carver wv{wbase}, av{abase};
   size_t max_w = 2304;
   for (int l = 0; l < 4; ++l) {
     const ddp_fpn_level& v = lv[l];
@@ -2239,35 +2226,30 @@ static int fpn_layout(const ddp_fpn_level* lv, int batch, char* wbase, char* aba
     }
     if (size_t(v.in_channels) > max_w) max_w = v.in_channels;
   }
-  o->wpack = reinterpret_cast<float*>(take(size_t(256) * max_w * 4));
-  o->wsplit = reinterpret_cast<unsigned short*>(take(size_t(3) * 256 * max_w * 2));
+  o->wpack = wv.take<float>(size_t(256) * max_w);
+  o->wsplit = wv.take<unsigned short>(size_t(3) * 256 * max_w);
   for (int l = 0; l < 4; ++l) {
-    o->lat_stream[l] = reinterpret_cast<unsigned char*>(take(size_t(lv[l].in_channels / 32) * b3_stage_bytes()));
-    o->out_stream[l] = reinterpret_cast<unsigned char*>(take(size_t(72) * b3_stage_bytes()));
+    o->lat_stream[l] = wv.take<unsigned char>(size_t(lv[l].in_channels / 32) * b3_stage_bytes());
+    o->out_stream[l] = wv.take<unsigned char>(size_t(72) * b3_stage_bytes());
   }
-  o->wbytes = off;
-  base = abase;
-  off = 0;
+  o->wbytes = wv.off;
   for (int l = 0; l < 4; ++l) {
     const ddp_fpn_level& v = lv[l];
     const size_t M = size_t(batch) * v.h * v.w, Mp = (M + 255) / 256 * 256;
-    o->a[l] = reinterpret_cast<float*>(take(Mp * v.in_channels * 4));
-    o->y[l] = reinterpret_cast<float*>(take(Mp * 256 * 4));
-    o->lat[l] = reinterpret_cast<float*>(take(Mp * 256 * 4));
-    o->stats[l] = reinterpret_cast<float*>(take(size_t(batch) * 64 * 4));
-    o->partial[l] = reinterpret_cast<double*>(take(size_t(batch) * ((size_t(v.h) * v.w + 31) / 32) * 64 * sizeof(double)));
+    o->a[l] = av.take<float>(Mp * v.in_channels);
+    o->y[l] = av.take<float>(Mp * 256);
+    o->lat[l] = av.take<float>(Mp * 256);
+    o->stats[l] = av.take<float>(size_t(batch) * 64);
+    o->partial[l] = av.take<double>(size_t(batch) * ((size_t(v.h) * v.w + 31) / 32) * 64);
   }
-  o->abytes = off;
+  o->abytes = av.off;
   o->bytes = o->wbytes + o->abytes;
   return DDP_OK;
 }
 }  // namespace
 
 int ddp_neck_fpn_workspace(const ddp_fpn_level* levels, int batch, size_t* bytes) {
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   FpnLayout o;
   DDP_TRY(fpn_layout(levels, batch, nullptr, nullptr, &o));
   *bytes = o.bytes;
@@ -2382,10 +2364,7 @@ int ddp_neck_fpn(const ddp_fpn_level* levels, int batch, const float* const* d_i
 // the four FPN outputs stay fp32 fragment-major and feed the merging directly - their NCHW form (one write by FPN, one read
 // and re-layout by the merging per level) is never produced.
 int ddp_neck_fpn_msm_workspace(const ddp_fpn_level* levels, int batch, size_t* bytes) {
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   FpnLayout f;
   DDP_TRY(fpn_layout(levels, batch, nullptr, nullptr, &f));
   int lh[4], lw[4];
@@ -2448,35 +2427,27 @@ static int fcn_layout(int maps, int h, int w, int K, char* base, FcnLayout* o) {
     set_error("fcn_head: bad geometry (maps %d map %dx%d classes %d)", maps, h, w, K);
     return DDP_E_BADCFG;
   }
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off += (nbytes + 255) / 256 * 256;
-    return p;
-  };
+  Carver cv{base};
   const size_t M = size_t(maps) * h * w, Mp = (M + 255) / 256 * 256;
   o->ldl = (K + 31) / 32 * 32;
-  o->x0 = reinterpret_cast<float*>(take(Mp * 256 * 4));        // row-major input (the sampler's concat-conv writes it)
-  o->xb0 = reinterpret_cast<float*>(take(Mp * 256 * 4));       // fp32 fragment-major activations, ping / pong
-  o->xb1 = reinterpret_cast<float*>(take(Mp * 256 * 4));
-  o->a_sb = reinterpret_cast<unsigned short*>(take(Mp * 256 * 6));   // (SB staging of the sampler's concat-conv input)
-  o->wpack = reinterpret_cast<float*>(take(size_t(256) * 2304 * 4));
-  o->wsplit = reinterpret_cast<unsigned short*>(take(size_t(3) * 256 * 2304 * 2));
-  o->stream = reinterpret_cast<unsigned char*>(take(size_t(72) * b3_stage_bytes()));
-  o->film = reinterpret_cast<float*>(take(512 * 4));
-  o->aff = reinterpret_cast<float*>(take(512 * 4));
-  o->cls_bias = reinterpret_cast<float*>(take(256 * 4));
-  o->logits = reinterpret_cast<float*>(take(Mp * o->ldl * 4));
-  o->bytes = off;
+  o->x0 = cv.take<float>(Mp * 256);                    // row-major input (the sampler's concat-conv writes it)
+  o->xb0 = cv.take<float>(Mp * 256);                    // fp32 fragment-major activations, ping / pong
+  o->xb1 = cv.take<float>(Mp * 256);
+  o->a_sb = cv.take<unsigned short>(Mp * 256 * 3);      // (SB staging of the sampler's concat-conv input)
+  o->wpack = cv.take<float>(size_t(256) * 2304);
+  o->wsplit = cv.take<unsigned short>(size_t(3) * 256 * 2304);
+  o->stream = cv.take<unsigned char>(size_t(72) * b3_stage_bytes());
+  o->film = cv.take<float>(512);
+  o->aff = cv.take<float>(512);
+  o->cls_bias = cv.take<float>(256);
+  o->logits = cv.take<float>(Mp * o->ldl);
+  o->bytes = cv.off;
   return DDP_OK;
 }
 }  // namespace
 
 int ddp_fcn_head_workspace(int maps, int h, int w, int num_classes, size_t* bytes) {
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   FcnLayout o;
   DDP_TRY(fcn_layout(maps, h, w, num_classes, nullptr, &o));
   *bytes = o.bytes;
@@ -2625,8 +2596,9 @@ int fcn_head_tokens(const ddp_fcn_conv* convs, int num_convs, int dilation, cons
   return launch_blk_to_row(nxt, o.logits, M, st, o.ldl, o.ldl);
 }
 
-// sampler loop around the FCN head: the head's own workspace first, then the loop's buffers
-struct FcnLoopLayout {
+// sampler loop around the FCN head: the head's own workspace first, then the loop's buffers, then the caller-visible tail
+// (the step-record and seeded-noise groups of carve_caller_regions)
+struct FcnLoopLayout : CallerRegions {
   FcnLayout head;
   float *tin, *u, *hid, *temb, *lut, *wx, *wm, *xtok, *xproj, *mask, *prob, *snoise;
   unsigned short *wx_split, *wm_split, *in_sb;
@@ -2634,49 +2606,36 @@ struct FcnLoopLayout {
   // images of the FiLM-scaled 3x3 weights and the shift vector; conv_seg's images and padded bias
   unsigned char *conv_streams, *cls_stream;
   float *conv_shifts, *cls_bias;
-  // DDP_FLAG_STEP_RECORD: (K, M) uint8 record and the (B, N) disagreement map - the last two buffers of the workspace
-  unsigned char* step_rec;
-  float* step_map;
-  float* seed_noise;   // DDP_FLAG_SEEDED_NOISE: (B, r, 256, h, w) start noise, in front of the step-record buffers
   size_t bytes;
 };
 int fcn_loop_layout(const ddp_cfg* c, int num_convs, char* base, FcnLoopLayout* o) {
   const int R = c->batch * c->randsteps, N = c->h * c->w, Kc = c->num_classes, Cx = c->feat_channels;
   DDP_TRY(fcn_layout(R, c->h, c->w, Kc, base, &o->head));
-  size_t off = o->head.bytes;
-  auto take = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off += (nbytes + 255) / 256 * 256;
-    return p;
-  };
-  auto takef = [&](size_t floats) { return reinterpret_cast<float*>(take(floats * sizeof(float))); };
+  Carver cv{base, o->head.bytes};
   const size_t M = size_t(R) * N, Mp = (M + 255) / 256 * 256, MB = size_t(c->batch) * N, MBp = (MB + 255) / 256 * 256;
-  o->tin = takef(DDP_MAX_STEPS);
-  o->u = takef(size_t(c->timesteps) * DDP_SINU_FEATS);
-  o->hid = takef(size_t(c->timesteps) * DDP_TIME_DIM);
-  o->temb = takef(size_t(c->timesteps) * DDP_TIME_DIM);
-  o->lut = takef(size_t(Kc + 1) * 256);
-  o->wx = takef(size_t(256) * Cx);
-  o->wm = takef(size_t(256) * 256);
-  o->wx_split = reinterpret_cast<unsigned short*>(take(size_t(3) * 256 * Cx * 2));
-  o->wm_split = reinterpret_cast<unsigned short*>(take(size_t(3) * 256 * 256 * 2));
-  o->xtok = takef(MB * Cx);
-  o->xproj = takef(MB * 256);
-  o->mask = takef(M * 256);
-  o->prob = takef(M * o->head.ldl);
-  o->snoise = takef(c->sampler == DDP_SAMPLER_DDPM ? M * 256 : 0);
+  o->tin = cv.take<float>(DDP_MAX_STEPS);
+  o->u = cv.take<float>(size_t(c->timesteps) * DDP_SINU_FEATS);
+  o->hid = cv.take<float>(size_t(c->timesteps) * DDP_TIME_DIM);
+  o->temb = cv.take<float>(size_t(c->timesteps) * DDP_TIME_DIM);
+  o->lut = cv.take<float>(size_t(Kc + 1) * 256);
+  o->wx = cv.take<float>(size_t(256) * Cx);
+  o->wm = cv.take<float>(size_t(256) * 256);
+  o->wx_split = cv.take<unsigned short>(size_t(3) * 256 * Cx);
+  o->wm_split = cv.take<unsigned short>(size_t(3) * 256 * 256);
+  o->xtok = cv.take<float>(MB * Cx);
+  o->xproj = cv.take<float>(MB * 256);
+  o->mask = cv.take<float>(M * 256);
+  o->prob = cv.take<float>(M * o->head.ldl);
+  o->snoise = cv.take<float>(c->sampler == DDP_SAMPLER_DDPM ? M * 256 : 0);
   const size_t sb_a = MBp * Cx, sb_b = Mp * 256;
-  o->in_sb = reinterpret_cast<unsigned short*>(take((sb_a > sb_b ? sb_a : sb_b) * 6));
+  o->in_sb = cv.take<unsigned short>((sb_a > sb_b ? sb_a : sb_b) * 3);
   const size_t per_conv = size_t(72) * b3_stage_bytes();
-  o->conv_streams = reinterpret_cast<unsigned char*>(take(size_t(c->timesteps) * num_convs * per_conv));
-  o->conv_shifts = takef(size_t(c->timesteps) * (num_convs > 0 ? num_convs : 1) * 256);
-  o->cls_stream = reinterpret_cast<unsigned char*>(take(size_t(8) * b3_stage_bytes()));
-  o->cls_bias = takef(256);
-  o->seed_noise = takef((c->flags & DDP_FLAG_SEEDED_NOISE) ? M * 256 : 0);
-  const bool rec = (c->flags & DDP_FLAG_STEP_RECORD) != 0;
-  o->step_rec = rec ? reinterpret_cast<unsigned char*>(take(step_record_bytes(c))) : nullptr;
-  o->step_map = rec ? takef(size_t(c->batch) * N) : nullptr;
-  o->bytes = off;
+  o->conv_streams = cv.take<unsigned char>(size_t(c->timesteps) * num_convs * per_conv);
+  o->conv_shifts = cv.take<float>(size_t(c->timesteps) * (num_convs > 0 ? num_convs : 1) * 256);
+  o->cls_stream = cv.take<unsigned char>(size_t(8) * b3_stage_bytes());
+  o->cls_bias = cv.take<float>(256);
+  carve_caller_regions(c, cv, o);
+  o->bytes = cv.off;
   return DDP_OK;
 }
 // a GroupNorm conv's images and bias do not depend on the step: its slot of step 0 serves every step (its other slots stay unused)
@@ -2752,10 +2711,7 @@ int ddp_fcn_head_forward(const ddp_fcn_conv* convs, int num_convs, int dilation,
 
 int ddp_sample_fcn_workspace(const ddp_cfg* cfg, int num_convs, int dilation, size_t* bytes) {
   DDP_TRY(validate_fcn_loop(cfg, num_convs, dilation));
-  if (!bytes) {
-    set_error("bytes is NULL");
-    return DDP_E_NULL;
-  }
+  DDP_TRY(check_bytes(bytes));
   FcnLoopLayout o;
   DDP_TRY(fcn_loop_layout(cfg, num_convs, nullptr, &o));
   *bytes = o.bytes;
@@ -2855,12 +2811,7 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
     SegUpdateArgs a = seg_update_args(o.head.logits, o.head.ldl, Kc, o.lut, o.mask, o.prob, cfg->accumulation ? (s == 0 ? 1 : 2) : 0,
                                       cfg->sampler, sp, M);
     if (cfg->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
-      if (key) {
-        prof_begin(TAG_GENERIC, st);
-        DDP_TRY(recorded(launch_noise_fill_tok(key, o.snoise, B, r, N, s, st), st));
-      } else {
-        DDP_TRY(launch_nchw_to_tok(d_step_noise + size_t(s) * M * 256, o.snoise, R, 256, N, st));
-      }
+      DDP_TRY(stage_step_noise(key, d_step_noise, o.snoise, B, r, N, s, st));
       a.step_noise = o.snoise;
     }
     a.x0_idx = o.step_rec ? o.step_rec + size_t(s) * M : nullptr;
@@ -2868,19 +2819,7 @@ int ddp_sample_fcn(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_fcn
   }
   if (cfg->accumulation) DDP_TRY(launch_finalize_nchw(o.prob, o.head.ldl, d_out, B, r, N, Kc, float(r * K), st));
   else DDP_TRY(launch_finalize_nchw(o.head.logits, o.head.ldl, d_out, B, r, N, Kc, float(r), st));
-  if (!o.step_rec) return DDP_OK;
-  StepDisagreementArgs da{};
-  da.rec = o.step_rec;
-  da.out = d_out;
-  da.map = o.step_map;
-  da.task = DDP_TASK_SEG;
-  da.B = B;
-  da.r = r;
-  da.K = K;
-  da.N = N;
-  da.num_classes = Kc;
-  prof_begin(TAG_GENERIC, st);
-  return recorded(launch_step_disagreement(da, st), st);
+  return step_disagreement(cfg, o, 0.f, d_out, st);
 }
 
 }  // extern "C"

@@ -146,7 +146,13 @@ def noise_key_words(seed, image_base=0, stream_base=0, call=0):
 
 class _SeededNoise:
     """What DDPEngine and FcnSamplerEngine share for ``seeded_noise=True``: the 8-word device key tensor, the argument checks of
-    ``sample()`` and the view of the start-noise buffer (``_workspace_bytes()`` is the engine's own workspace query)."""
+    ``sample()`` and the view of the start-noise buffer; and ``_region()``, the view of any buffer of ``caller_regions``
+    (``_workspace_bytes()`` is the engine's own workspace query)."""
+
+    def _region(self, name, dtype, shape):
+        off, nbytes = caller_regions(self.cfg, self._workspace_bytes())[name]
+        v = self.workspace.view(torch.uint8)[off:off + nbytes]
+        return (v if dtype == torch.uint8 else v.view(dtype)).view(shape)
 
     def _init_key(self):
         self.seeded = bool(self.cfg.flags & _lib.FLAG_SEEDED_NOISE)
@@ -192,14 +198,7 @@ class _SeededNoise:
         if not getattr(self, '_sampled', False):
             raise _lib.DdpError('no noise yet: call sample() first')
         c = self.cfg
-        cm = 1 if c.task == _lib.TASK_DEPTH else 256
-        n = c.batch * c.randsteps * cm * c.h * c.w
-        end = self._workspace_bytes()
-        if c.flags & _lib.FLAG_STEP_RECORD:
-            rec, smap = step_record_sizes(c)
-            end -= _round256(rec) + _round256(smap)
-        off = end - _round256(n * 4)
-        return self.workspace.view(torch.uint8)[off:off + n * 4].view(torch.float32).view(c.batch, c.randsteps, cm, c.h, c.w)
+        return self._region('seed_noise', torch.float32, (c.batch, c.randsteps, 1 if c.task == _lib.TASK_DEPTH else 256, c.h, c.w))
 
 
 class DDPEngine(_SeededNoise):
@@ -376,29 +375,25 @@ class DDPEngine(_SeededNoise):
         c = self.cfg
         if not c.flags & _lib.FLAG_X0_HINTS:
             raise _lib.DdpError('hints need an engine built with x0_hints=True')
-        seg = c.task == _lib.TASK_SEG
-        nbytes = c.batch * c.h * c.w * (1 if seg else 4)
-        end = self._workspace_bytes()
-        if c.flags & _lib.FLAG_STEP_RECORD:
-            rec, smap = step_record_sizes(c)
-            end -= _round256(rec) + _round256(smap)
-        if c.flags & _lib.FLAG_SEEDED_NOISE:
-            end -= _round256(c.batch * c.randsteps * (256 if seg else 1) * c.h * c.w * 4)
-        off = end - _round256(nbytes)
-        v = self.workspace.view(torch.uint8)[off:off + nbytes]
-        return (v if seg else v.view(torch.float32)).view(c.batch, c.h, c.w)
+        return self._region('hint_map', torch.uint8 if c.task == _lib.TASK_SEG else torch.float32, (c.batch, c.h, c.w))
+
+    def _write_region(self, dst, src, name, kind, dims, where):
+        """the checks and the stream-ordered copy of set_hints / set_prior / set_class_prior: ``src`` must be a tensor of dtype
+        ``kind`` (or any 'floating-point' one) with the shape of ``dst``, on the engine's device"""
+        ok = isinstance(src, torch.Tensor) and (src.dtype.is_floating_point if kind == 'floating-point' else src.dtype == kind)
+        if not ok:
+            raise _lib.DdpError(f'{name} must be a {kind} tensor, got {getattr(src, "dtype", type(src))}')
+        if tuple(src.shape) != tuple(dst.shape):
+            raise _lib.DdpError(f'{name} must have shape {tuple(dst.shape)} ({dims}), got {tuple(src.shape)}')
+        if src.device != self.device:
+            raise _lib.DdpError(f'engine lives on {self.device}: {where} on {src.device}')
+        with torch.cuda.device(self.device):
+            dst.copy_(src, non_blocking=True)
 
     def set_hints(self, hints):
         """copy ``hints`` (B, h, w) - uint8 for seg, float32 for depth, on the engine's device - into the hint map (stream-ordered)"""
         v = self.hints_view()
-        if not isinstance(hints, torch.Tensor) or hints.dtype != v.dtype:
-            raise _lib.DdpError(f'hints must be a {v.dtype} tensor, got {getattr(hints, "dtype", type(hints))}')
-        if tuple(hints.shape) != tuple(v.shape):
-            raise _lib.DdpError(f'hints must have shape {tuple(v.shape)} (batch, h, w), got {tuple(hints.shape)}')
-        if hints.device != self.device:
-            raise _lib.DdpError(f'engine lives on {self.device}: hints are on {hints.device}')
-        with torch.cuda.device(self.device):
-            v.copy_(hints, non_blocking=True)
+        self._write_region(v, hints, 'hints', v.dtype, 'batch, h, w', 'hints are')
 
     def clear_hints(self, _if_any=False):
         """every pixel free (seg: 255, depth: 0)"""
@@ -420,23 +415,15 @@ class DDPEngine(_SeededNoise):
         (bev; the C side's uint32); the kernel reads it when it runs (a captured graph picks up what it holds at replay).  Place:
         include/ddp_mi355x.h, "prior start"."""
         c = self.cfg
-        off, nbytes, _, _ = self._prior_places()
-        v = self.workspace.view(torch.uint8)[off:off + nbytes]
+        self._prior_places()
         dtype = {_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32}[c.task]
-        return (v if dtype == torch.uint8 else v.view(dtype)).view(c.batch, c.h, c.w)
+        return self._region('prior_map', dtype, (c.batch, c.h, c.w))
 
     def set_prior(self, prior):
         """copy ``prior`` (B, h, w) - uint8 for seg, float32 for depth, int32 for bev, on the engine's device - into the prior map
         (stream-ordered)"""
         v = self.prior_view()
-        if not isinstance(prior, torch.Tensor) or prior.dtype != v.dtype:
-            raise _lib.DdpError(f'prior must be a {v.dtype} tensor, got {getattr(prior, "dtype", type(prior))}')
-        if tuple(prior.shape) != tuple(v.shape):
-            raise _lib.DdpError(f'prior must have shape {tuple(v.shape)} (batch, h, w), got {tuple(prior.shape)}')
-        if prior.device != self.device:
-            raise _lib.DdpError(f'engine lives on {self.device}: the prior is on {prior.device}')
-        with torch.cuda.device(self.device):
-            v.copy_(prior, non_blocking=True)
+        self._write_region(v, prior, 'prior', v.dtype, 'batch, h, w', 'the prior is')
 
     def clear_prior(self, _if_any=False):
         """no prior knowledge anywhere: seg 255 (the ignore row), depth 0 (the middle of the range), bev 0 (no class present)"""
@@ -450,11 +437,11 @@ class DDPEngine(_SeededNoise):
         """(B, r, Cm, h, w) float32 VIEW of the start map the LAST sample() call (or graph replay) formed from the prior and its
         noise; valid until the next call.  (With ``seeded_noise`` this is the seeded-noise buffer, mixed in place.)"""
         c = self.cfg
-        _, _, off, nbytes = self._prior_places()
+        self._prior_places()
         if not getattr(self, '_sampled', False):
             raise _lib.DdpError('no start map yet: call sample() first')
-        cm = 1 if c.task == _lib.TASK_DEPTH else 256
-        return self.workspace.view(torch.uint8)[off:off + nbytes].view(torch.float32).view(c.batch, c.randsteps, cm, c.h, c.w)
+        return self._region('seed_noise' if c.flags & _lib.FLAG_SEEDED_NOISE else 'prior_start', torch.float32,
+                            (c.batch, c.randsteps, 1 if c.task == _lib.TASK_DEPTH else 256, c.h, c.w))
 
     # ---- DDP_FLAG_CLASS_PRIOR ------------------------------------------------------------------
     def class_prior_view(self):
@@ -464,21 +451,12 @@ class DDPEngine(_SeededNoise):
         c = self.cfg
         if not c.flags & _lib.FLAG_CLASS_PRIOR:
             raise _lib.DdpError('the class prior needs an engine built with class_prior=True')
-        off, nbytes, _, _ = class_prior_places(c, self._workspace_bytes())
-        return self.workspace.view(torch.uint8)[off:off + nbytes].view(torch.float32).view(c.batch, 256)
+        return self._region('cprior_table', torch.float32, (c.batch, 256))
 
     def set_class_prior(self, prior):
         """copy ``prior`` (B, num_classes) - a floating-point tensor on the engine's device - into the table (stream-ordered)"""
         v = self.class_prior_view()
-        c = self.cfg
-        if not isinstance(prior, torch.Tensor) or not prior.dtype.is_floating_point:
-            raise _lib.DdpError(f'class_prior must be a floating-point tensor, got {getattr(prior, "dtype", type(prior))}')
-        if tuple(prior.shape) != (c.batch, c.num_classes):
-            raise _lib.DdpError(f'class_prior must have shape {(c.batch, c.num_classes)} (batch, num_classes), got {tuple(prior.shape)}')
-        if prior.device != self.device:
-            raise _lib.DdpError(f'engine lives on {self.device}: the class prior is on {prior.device}')
-        with torch.cuda.device(self.device):
-            v[:, :c.num_classes].copy_(prior, non_blocking=True)
+        self._write_region(v[:, :self.cfg.num_classes], prior, 'class_prior', 'floating-point', 'batch, num_classes', 'the class prior is')
 
     def clear_class_prior(self, _if_any=False):
         """no prior: every entry 0 (the bits of the flag-clear call)"""
@@ -685,52 +663,45 @@ def _round256(n):
     return (n + 255) // 256 * 256
 
 
-def prior_start_places(cfg, workspace_bytes):
-    """(prior_offset, prior_bytes, start_offset, start_bytes) of include/ddp_mi355x.h ("prior start"), in bytes from the start of a
-    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): THE host-side derivation of where DDP_FLAG_PRIOR_START's buffers lie.
-    With DDP_FLAG_SEEDED_NOISE the start map is the seeded-noise buffer."""
+def caller_regions(cfg, workspace_bytes):
+    """{name: (offset, nbytes)}, in workspace order, of the buffers at the END of a sampler workspace that the caller reads or writes
+    directly or that lie between them: THE host-side table of the ordered list in include/ddp_mi355x.h (at ddp_query_workspace;
+    csrc/ddp_api.hip carve_caller_regions is the same table in C).  ``workspace_bytes`` = ddp_query_workspace(cfg), or
+    ddp_sample_fcn_workspace(cfg, ...) for the FCN loop, whose cfg can only carry the last two groups.  Each buffer is rounded up
+    to 256 bytes and exists only with its flag; the last one ends at ``workspace_bytes``."""
+    f = cfg.flags
     seg, depth = cfg.task == _lib.TASK_SEG, cfg.task == _lib.TASK_DEPTH
     n = cfg.batch * cfg.h * cfg.w
-    prior_bytes = n * (1 if seg else 4)
-    start_bytes = n * cfg.randsteps * (1 if depth else 256) * 4
-    end = workspace_bytes
-    if cfg.flags & _lib.FLAG_STEP_RECORD:
-        rec, smap = step_record_sizes(cfg)
-        end -= _round256(rec) + _round256(smap)
-    seeded_off = None
-    if cfg.flags & _lib.FLAG_SEEDED_NOISE:
-        end -= _round256(start_bytes)
-        seeded_off = end
-    if cfg.flags & _lib.FLAG_X0_HINTS:
-        end -= _round256(n * (1 if seg else 4)) + _round256(n * cfg.randsteps * (1 if seg else 4))
-    prior_off = end - _round256(prior_bytes)
-    start_off = seeded_off if seeded_off is not None else prior_off - _round256(start_bytes)
-    return prior_off, prior_bytes, start_off, start_bytes
+    px = 1 if seg else 4                                            # bytes per pixel of a hint / prior map
+    noise = n * cfg.randsteps * (1 if depth else 256) * 4           # a (B, r, Cm, h, w) float map: start noise, start map
+    rec, smap = step_record_sizes(cfg)
+    cp, ps, xh, sn, sr = (bool(f & b) for b in (_lib.FLAG_CLASS_PRIOR, _lib.FLAG_PRIOR_START, _lib.FLAG_X0_HINTS,
+                                                _lib.FLAG_SEEDED_NOISE, _lib.FLAG_STEP_RECORD))
+    table = [('cprior_rows', 2 * cfg.batch * 256 * 4, cp), ('cprior_table', cfg.batch * 256 * 4, cp),
+             ('prior_start', noise, ps and not sn), ('prior_map', n * px, ps),
+             ('hint_rows', n * cfg.randsteps * px, xh), ('hint_map', n * px, xh),
+             ('seed_noise', noise, sn),
+             ('step_rec', rec, sr), ('step_map', smap, sr)]
+    out, end = [], workspace_bytes
+    for name, nbytes, present in reversed(table):
+        if present:
+            end -= _round256(nbytes)
+            out.append((name, (end, nbytes)))
+    return dict(reversed(out))
+
+
+def prior_start_places(cfg, workspace_bytes):
+    """(prior_offset, prior_bytes, start_offset, start_bytes) of include/ddp_mi355x.h ("prior start"), in bytes from the start of a
+    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg).  With DDP_FLAG_SEEDED_NOISE the start map is the seeded-noise buffer."""
+    r = caller_regions(cfg, workspace_bytes)
+    return r['prior_map'] + r['seed_noise' if cfg.flags & _lib.FLAG_SEEDED_NOISE else 'prior_start']
 
 
 def class_prior_places(cfg, workspace_bytes):
     """(table_offset, table_bytes, bias_offset, bias_bytes) of include/ddp_mi355x.h ("class prior"), in bytes from the start of a
-    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): THE host-side derivation of where DDP_FLAG_CLASS_PRIOR's buffers lie -
-    the caller's table immediately in front of the prior-start, hint, seeded-noise and step-record buffers (whichever exist), the
-    library's per-image vectors immediately in front of it."""
-    table_bytes = cfg.batch * 256 * 4
-    bias_bytes = 2 * table_bytes
-    end = workspace_bytes
-    if cfg.flags & _lib.FLAG_PRIOR_START:
-        prior_off, _, start_off, _ = prior_start_places(cfg, workspace_bytes)
-        end = prior_off if cfg.flags & _lib.FLAG_SEEDED_NOISE else min(prior_off, start_off)
-    else:
-        seg = cfg.task == _lib.TASK_SEG
-        n = cfg.batch * cfg.h * cfg.w
-        if cfg.flags & _lib.FLAG_STEP_RECORD:
-            rec, smap = step_record_sizes(cfg)
-            end -= _round256(rec) + _round256(smap)
-        if cfg.flags & _lib.FLAG_SEEDED_NOISE:
-            end -= _round256(n * cfg.randsteps * (256 if seg else 1) * 4)
-        if cfg.flags & _lib.FLAG_X0_HINTS:
-            end -= _round256(n * (1 if seg else 4)) + _round256(n * cfg.randsteps * (1 if seg else 4))
-    table_off = end - _round256(table_bytes)
-    return table_off, table_bytes, table_off - _round256(bias_bytes), bias_bytes
+    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): the caller's table, the library's per-image vectors in front of it."""
+    r = caller_regions(cfg, workspace_bytes)
+    return r['cprior_table'] + r['cprior_rows']
 
 
 def class_mask_to_prior(mask):
@@ -904,8 +875,7 @@ class FcnSamplerEngine(_SeededNoise):
             raise _lib.DdpError('step_record() / step_disagreement() need an engine built with record_steps=True')
         if not self._sampled:
             raise _lib.DdpError('no step record yet: call sample() first')
-        rec, smap = step_record_sizes(self.cfg)      # the last two buffers of ddp_sample_fcn's workspace (include/ddp_mi355x.h)
-        return self._ws_bytes - _round256(smap) - _round256(rec)
+        return caller_regions(self.cfg, self._ws_bytes)['step_rec'][0]
 
     def step_record(self):
         """(K, B, r, h, w) uint8: the argmax class every step of the LAST sample() call fed back.  A fresh tensor."""

@@ -225,7 +225,21 @@ typedef struct ddp_step {
 const char* ddp_last_error(void);
 int ddp_abi_version(void);
 
-/* Size in bytes of the caller-provided workspace for `cfg` (constants + activations). */
+/* Size in bytes of the caller-provided workspace for `cfg` (constants + activations).
+ * THE TAIL OF THE WORKSPACE: the buffers a caller reads or writes directly are the LAST of the workspace, in one fixed order.  Each
+ * group exists only with its flag, each buffer is rounded up to 256 bytes (round256), and nothing follows the last one (the sizes
+ * are the formulas of the sections named on the right):
+ *   1. DDP_FLAG_CLASS_PRIOR    round256(bias_bytes), then round256(table_bytes)                                    "class prior"
+ *   2. DDP_FLAG_PRIOR_START    [DDP_FLAG_SEEDED_NOISE clear: round256(start_bytes)], then round256(prior_bytes)    "prior start"
+ *   3. DDP_FLAG_X0_HINTS       round256(row_bytes), then round256(hint_bytes)                                      "x0 hints"
+ *   4. DDP_FLAG_SEEDED_NOISE   round256(noise_bytes)                                                               "Seeded noise"
+ *   5. DDP_FLAG_STEP_RECORD    round256(record_bytes), then round256(map_bytes)                                    at ddp_x0_trace
+ * A buffer starts at ddp_query_workspace(cfg) minus its own rounded size and the rounded sizes of everything behind it in this
+ * list: the hint map of a cfg with flags 3, 4 and 5 at ddp_query_workspace(cfg) - round256(map_bytes) - round256(record_bytes)
+ * - round256(noise_bytes) - round256(hint_bytes).  Setting one of the five flags grows ddp_query_workspace by exactly its group;
+ * every offset in front of the group and ddp_query_const_workspace are those of the cfg without the flag.
+ * ddp_sample_fcn_workspace ends with groups 4 and 5 in the same way (ddp_sample_fcn refuses flags 1 to 3).
+ * ddp_amd.engine.caller_regions is this list on the host side. */
 int ddp_query_workspace(const ddp_cfg* cfg, size_t* bytes);
 
 /* Fill the constant region of the workspace: time embeddings and per-layer FiLM vectors for every
@@ -282,9 +296,8 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
  * Sizes, as formulas of the cfg:
  *   record_bytes = timesteps * batch * randsteps * head_h * head_w * (seg: 1, depth / bev: 4)
  *   map_bytes    = batch * head_h * head_w * 4
- * Both are carved at the END of the workspace, each rounded up to 256 bytes: ddp_query_workspace grows by
- * round256(record_bytes) + round256(map_bytes), every other offset and ddp_query_const_workspace are those of the cfg without
- * the flag.  The STEP-DISAGREEMENT MAP, (B, H, W) float, starts at *d_idx + round256(record_bytes) and is written once per
+ * Both are carved at the END of the workspace (group 5 of the list at ddp_query_workspace), each rounded up to 256 bytes.
+ * The STEP-DISAGREEMENT MAP, (B, H, W) float, starts at *d_idx + round256(record_bytes) and is written once per
  * ddp_sample by k_step_disagreement, after the output (same stream, hipGraph-capturable like the rest):
  *   seg   the fraction of the K * r recorded decisions of the pixel that differ from its final decision = argmax over the classes
  *         of the output ddp_sample returned (first maximum wins, as ddp_seg_postprocess)
@@ -317,11 +330,9 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * place of the caller's tensor; a ddpm step's noise is written token-major by k_noise_fill_tok straight into the buffer the update
  * kernel reads (no (K, B, r, Cm, h, w) tensor, no per-step transpose).  Size and place, as formulas of the cfg:
  *   noise_bytes = batch * randsteps * Cm * h * w * 4      (Cm = 1 for depth, else 256)
- * carved IMMEDIATELY IN FRONT of the step-record buffers - at the END of the workspace when DDP_FLAG_STEP_RECORD is clear -, rounded
- * up to 256 bytes: ddp_query_workspace grows by round256(noise_bytes), the buffer starts at
- *   ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)] - round256(noise_bytes),
- * every other offset and ddp_query_const_workspace are those of the cfg without the flag; ddp_sample_fcn_workspace follows the same
- * rule.  The buffer holds the (B, r, Cm, h, w) start noise of the LAST call until the next one.
+ * carved IMMEDIATELY IN FRONT of the step-record buffers - at the END of the workspace when DDP_FLAG_STEP_RECORD is clear - (group 4
+ * of the list at ddp_query_workspace; ddp_sample_fcn_workspace follows the same rule).  The buffer holds the (B, r, Cm, h, w) start
+ * noise of the LAST call until the next one.
  * Extra launches with the flag set: one k_noise_fill_nchw per call; per noise-adding ddpm step one k_noise_fill_tok in place of the
  * NCHW -> token-major transpose. */
 
@@ -337,12 +348,8 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * What ddp_sample returns stays the model's own prediction (scores / depth), and the step record (DDP_FLAG_STEP_RECORD,
  * DDP_FLAG_RECORD_X0) keeps the model's own decision of every step: a caller sees where the model disagrees with its hints.  Hints
  * act through the update, i.e. from the SECOND step on: timesteps = 1 is accepted and the hints have no effect there.
- * Sizes and places, as formulas of the cfg - two buffers, each rounded up to 256 bytes; ddp_query_workspace grows by exactly
- * round256(hint_bytes) + round256(row_bytes), every other offset and ddp_query_const_workspace are those of the cfg without the flag:
- *   hint_bytes = batch * h * w * (seg: 1, depth: 4)              the caller-written hint map, carved IMMEDIATELY IN FRONT of the
- *                seeded-noise buffer; it starts at
- *                ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)]
- *                                         - [SEEDED_NOISE: round256(noise_bytes)] - round256(hint_bytes)
+ * Sizes, as formulas of the cfg - two buffers, group 3 of the list at ddp_query_workspace, which gives their place:
+ *   hint_bytes = batch * h * w * (seg: 1, depth: 4)              the caller-written hint map
  *   row_bytes  = batch * randsteps * h * w * (seg: 1, depth: 4)  library-private, immediately in front of the hint map: the hints per
  *                row m = (b * r + rr) * N + n (the order of the x0 trace) with the "free" encodings normalised (seg 255, depth 0)
  * The library never initialises the hint map: the caller writes it (all free = every byte 255 / every float 0) before the first
@@ -372,14 +379,8 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  *   seg / bev   m0 = steps[0].alpha * x0[b][ch][n] + steps[0].sigma * eps[b][rr][ch][n]
  *   depth       m0 = steps[0].alpha * x0[b][n]     + eps[b][rr][0][n] / steps[0].sigma     (depth's ddp_step.sigma is 1 / sqrt(1 - gamma))
  * each as ONE fused multiply-add on the rounded second term.  Every route then reads m0 where it would read d_noise.
- * Sizes and places, as formulas of the cfg - each buffer rounded up to 256 bytes; ddp_query_workspace grows by exactly
- * round256(prior_bytes) + [SEEDED_NOISE clear: round256(start_bytes)], every other offset and ddp_query_const_workspace are those of
- * the cfg without the flag:
- *   prior_bytes = batch * h * w * (seg: 1, depth / bev: 4)        the caller-written prior map, carved IMMEDIATELY IN FRONT of the
- *                 x0-hint buffers (of the seeded-noise buffer without them); it starts at
- *                 ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)]
- *                                          - [SEEDED_NOISE: round256(noise_bytes)]
- *                                          - [X0_HINTS: round256(hint_bytes) + round256(row_bytes)] - round256(prior_bytes)
+ * Sizes, as formulas of the cfg - group 2 of the list at ddp_query_workspace, which gives their place:
+ *   prior_bytes = batch * h * w * (seg: 1, depth / bev: 4)        the caller-written prior map
  *   start_bytes = batch * randsteps * Cm * h * w * 4              the start map m0 (B, r, Cm, h, w), immediately in front of the prior
  *                 map; carved only when DDP_FLAG_SEEDED_NOISE is clear.  With both flags set the seeded-noise buffer is the start
  *                 buffer: it is filled with eps and then mixed in place, and after the call it holds m0, not eps
@@ -399,16 +400,8 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * clamped to [-1e30, 1e30] - so -inf (anything <= -1e30) means "class excluded": its score stays finite, its softmax term is
  * exactly 0 and the returned scores never hold an infinity (the bilinear epilogues would turn 0 * inf into NaN).  An image with
  * every class excluded is a uniform shift.
- * Sizes and places, as formulas of the cfg - two buffers, each rounded up to 256 bytes; ddp_query_workspace grows by exactly
- * round256(table_bytes) + round256(bias_bytes), every other offset and ddp_query_const_workspace are those of the cfg without the
- * flag:
- *   table_bytes = batch * 256 * 4       the caller-written table, carved IMMEDIATELY IN FRONT of the prior-start buffers (of the
- *                 x0-hint, seeded-noise, step-record buffers - whichever come first - or the end of the workspace); it starts at
- *                 ddp_query_workspace(cfg) - [STEP_RECORD: round256(map_bytes) + round256(record_bytes)]
- *                                          - [SEEDED_NOISE: round256(noise_bytes)]
- *                                          - [X0_HINTS: round256(hint_bytes) + round256(row_bytes)]
- *                                          - [PRIOR_START: round256(prior_bytes) + (SEEDED_NOISE clear: round256(start_bytes))]
- *                                          - round256(table_bytes)
+ * Sizes, as formulas of the cfg - two buffers, group 1 of the list at ddp_query_workspace, which gives their place:
+ *   table_bytes = batch * 256 * 4       the caller-written table
  *   bias_bytes  = 2 * batch * 256 * 4   library-private, immediately in front of the table: per image the vector
  *                 fl32(conv_seg.bias + clamp(prior[b])), zero padded to 256 (the accumulator start of conv_seg in the layer
  *                 kernel's seg tails, which a lane reads for the image of its token, m / (r N) - a 32-token tile may straddle two

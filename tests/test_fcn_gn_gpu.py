@@ -139,9 +139,8 @@ class _Loop:
 
     def record(self):
         """(K, B, r, h, w) uint8: the step record at the end of the workspace (include/ddp_mi355x.h, DDP_FLAG_STEP_RECORD)"""
-        from ddp_amd.engine import _round256, step_record_sizes, step_record_view
-        rec, smap = step_record_sizes(self.cfg)
-        return step_record_view(self.g.ws, self.nbytes - _round256(smap) - _round256(rec), self.cfg).clone().cpu()
+        from ddp_amd.engine import caller_regions, step_record_view
+        return step_record_view(self.g.ws, caller_regions(self.cfg, self.nbytes)['step_rec'][0], self.cfg).clone().cpu()
 
 
 def _loop_checks(c, sd, dev, x, noise, sn, ref, decisions):
