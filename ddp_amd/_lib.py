@@ -23,6 +23,7 @@ FLAG_DDPM_CHAIN = 4096
 FLAG_X0_HINTS = 16384      # (8192 stays undefined)
 FLAG_PRIOR_START = 65536   # (so does 32768)
 FLAG_CLASS_PRIOR = 131072
+FLAG_SCORE_PRIOR = 1048576   # (262144 and 524288 stay undefined)
 DEPTH_NORM_LINEAR, DEPTH_NORM_SOFTMAX, DEPTH_NORM_SIGMOID = 0, 1, 2
 MAX_DEPTH_BINS = 256
 BEV_MAX_PRESCALE_AREA = 16

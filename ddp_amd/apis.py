@@ -50,6 +50,8 @@ def _run_batch(model, data, device, batch_indices=None, **kwargs):
         data['prior'] = _to_device(data['prior'], device)
     if data.get('class_prior') is not None:    # class prior (DDP.forward(class_prior=)): (b, num_classes), no frame
         data['class_prior'] = _to_device(data['class_prior'], device)
+    if data.get('score_prior') is not None:    # score prior (DDP.forward(score_prior=)): (b, num_classes, H, W), likewise
+        data['score_prior'] = _to_device(data['score_prior'], device)
     # seeded noise (model.noise_seed set): image i of the batch draws the noise of dataset index batch_indices[0] + i, whatever
     # samples_per_gpu is and whichever rank the batch landed on (a batch_sampler of a sequential or strided sampler hands out
     # increasing indices; the first one names the batch)

@@ -8,7 +8,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libddp_mi355x.so')
 SOURCES = ['ddp_api.hip', 'ddp_gemm.hip', 'ddp_gemm_bf16.hip', 'ddp_kernels.hip', 'ddp_layer_tail.hip', 'ddp_step_record.hip',
-           'ddp_noise.hip', 'ddp_ddpm_chain.hip', 'ddp_hints.hip', 'ddp_prior_start.hip', 'ddp_fcn_gn.hip', 'ddp_class_prior.hip']
+           'ddp_noise.hip', 'ddp_ddpm_chain.hip', 'ddp_hints.hip', 'ddp_prior_start.hip', 'ddp_fcn_gn.hip', 'ddp_class_prior.hip',
+           'ddp_score_prior.hip']
 HEADERS = ['exports.map', 'ddp_internal.h', 'gemm_f32.h', 'gemm_bf16x3.h', 'layer_bf16x3.h', os.path.join('..', '..', 'include', 'ddp_mi355x.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-Wall', '-Wno-unused-function']
 

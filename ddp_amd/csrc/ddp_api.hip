@@ -85,6 +85,9 @@ struct Carver {
 // The caller-visible tail of a sampler workspace (ddp_sample and ddp_sample_fcn): the buffers the caller reads or writes directly,
 // each present only with its flag (include/ddp_mi355x.h, at ddp_query_workspace)
 struct CallerRegions {
+  // DDP_FLAG_SCORE_PRIOR: the caller-written NCHW map (B, num_classes, h, w) and the token-major rows k_score_prior_rows writes:
+  // (B * N, KP), KP = 64 * ceil(num_classes / 64), normalised, zero padded (the seg tails' and k_seg_update's addend)
+  float *sprior_rows = nullptr, *sprior_map = nullptr;
   // DDP_FLAG_CLASS_PRIOR: the caller-written table (B, 256) and the per-image vectors k_class_prior writes: (B, 256) bias + prior rows
   // (the seg tails' accumulator start), then (B, 256) prior rows (k_seg_update's addend)
   float *cprior_rows = nullptr, *cprior_table = nullptr;
@@ -212,8 +215,12 @@ int validate(const ddp_cfg* c) {
   if (c->flags & ~(DDP_FLAG_UNFUSED_LAYER | DDP_FLAG_UNFUSED_PROLOGUE | DDP_FLAG_RECORD_X0 | DDP_FLAG_GATHER_GUESS_ZERO |
                    DDP_FLAG_FORCE_X0 | DDP_FLAG_UNFUSED_TAIL | DDP_FLAG_SB_HEAD | DDP_FLAG_DEPTH_SCALE_UP | DDP_FLAG_DEPTH_NO_EPS |
                    DDP_FLAG_STEP_RECORD | DDP_FLAG_SEEDED_NOISE | DDP_FLAG_DDPM_CHAIN | DDP_FLAG_X0_HINTS |
-                   DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR)) {
+                   DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR | DDP_FLAG_SCORE_PRIOR)) {
     set_error("unknown flags 0x%x", c->flags);
+    return DDP_E_BADCFG;
+  }
+  if ((c->flags & DDP_FLAG_SCORE_PRIOR) && c->task != DDP_TASK_SEG) {
+    set_error("DDP_FLAG_SCORE_PRIOR exists for the segmentation sampler only (task %d: no depth or bev prior is built)", c->task);
     return DDP_E_BADCFG;
   }
   if ((c->flags & DDP_FLAG_CLASS_PRIOR) && c->task != DDP_TASK_SEG) {
@@ -317,17 +324,22 @@ inline size_t step_record_bytes(const ddp_cfg* c) {
 // The tail of a sampler workspace, in its one fixed order (the ordered list of include/ddp_mi355x.h at ddp_query_workspace; the same
 // table on the host side: ddp_amd.engine.caller_regions).  Every group exists only with its flag, so every offset in front of a group
 // is the one of the cfg without that flag:
+//   score prior    the private token-major rows, then the caller's NCHW map
 //   class prior    the private per-image vectors, then the caller's table
 //   prior start    the start map (only without DDP_FLAG_SEEDED_NOISE: with it the seeded-noise buffer is the start map), then the
 //                  caller's prior map
 //   x0 hints       the private row buffer, then the caller's map
 //   seeded noise   the start noise of the call
 //   step record    the record, then the disagreement map: the LAST two buffers
-// ddp_sample_fcn refuses the first three flags (validate_fcn_loop): its tail is the last two groups.
+// ddp_sample_fcn refuses the first four flags (validate_fcn_loop): its tail is the last two groups.
 void carve_caller_regions(const ddp_cfg* c, Carver& cv, CallerRegions* o) {
   const size_t B = c->batch, BN = B * c->h * c->w, M0 = BN * c->randsteps;
   const size_t Cm = c->task == DDP_TASK_DEPTH ? 1 : 256;      // channels of the noisy map
   const size_t px = c->task == DDP_TASK_SEG ? 1 : 4;          // bytes per pixel of a hint / prior map: uint8 classes, else fp32 / uint32
+  if (c->flags & DDP_FLAG_SCORE_PRIOR) {
+    o->sprior_rows = cv.take<float>(BN * size_t((c->num_classes + 63) / 64 * 64));
+    o->sprior_map = cv.take<float>(BN * size_t(c->num_classes));
+  }
   if (c->flags & DDP_FLAG_CLASS_PRIOR) {
     o->cprior_rows = cv.take<float>(2 * B * 256);
     o->cprior_table = cv.take<float>(B * 256);
@@ -1288,6 +1300,8 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
       tl.x0_idx = x0.idx;
       tl.cp_bias = o.cprior_rows;                        // (nullptr without DDP_FLAG_CLASS_PRIOR)
       tl.cp_rn = o.r * o.N;
+      tl.sp_rows = o.sprior_rows;                        // (nullptr without DDP_FLAG_SCORE_PRIOR)
+      tl.sp_n = o.N;
       tl.M = M;
       tl.num_classes = o.Kc;
       tl.ldl = o.ldl;
@@ -1327,6 +1341,9 @@ int sample_seg(const ddp_cfg* c, const ddp_weights* w, const ddp_step* steps, co
     a.x0_idx = x0.idx;
     a.cp_delta = o.cprior_rows ? o.cprior_rows + size_t(o.B) * 256 : nullptr;
     a.cp_rn = o.r * o.N;
+    a.sp_rows = o.sprior_rows;
+    a.sp_n = o.N;
+    a.sp_kp = (o.Kc + 63) / 64 * 64;
     if (c->sampler == DDP_SAMPLER_DDPM && sp.ddpm_add_noise) {
       DDP_TRY(stage_step_noise(key, d_step_noise, o.snoise, o.B, o.r, o.N, s, st));
       a.step_noise = o.snoise;
@@ -1681,6 +1698,11 @@ int ddp_sample(const ddp_cfg* cfg, const ddp_weights* weights, const ddp_step* s
     DDP_TRY(recorded(launch_class_prior(o.cprior_table, weights->head_b, o.cprior_rows, o.cprior_rows + size_t(o.B) * 256, o.B, o.Kc, st),
                      st));
   }
+  // DDP_FLAG_SCORE_PRIOR: the caller's NCHW map as read NOW -> the token-major prior rows of the seg decision kernels
+  if (o.sprior_rows) {
+    prof_begin(TAG_GENERIC, st);
+    DDP_TRY(recorded(launch_score_prior_rows(o.sprior_map, o.sprior_rows, o.B, o.Kc, o.N, st), st));
+  }
   const uint32_t* key = nullptr;
   if (seeded) {
     key = reinterpret_cast<const uint32_t*>(d_noise);
@@ -1743,12 +1765,12 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
 
 int ddp_head_forward(const ddp_cfg* cfg, const ddp_weights* weights, const float* d_feat, const float* d_temb,
                      float* d_out, void* d_workspace, void* stream) {
-  // one decoder pass has no x0 feedback and no start map: DDP_FLAG_X0_HINTS, DDP_FLAG_PRIOR_START and DDP_FLAG_CLASS_PRIOR are ignored
-  // (the buffers they carve lie behind everything used here)
+  // one decoder pass has no x0 feedback and no start map: DDP_FLAG_X0_HINTS, DDP_FLAG_PRIOR_START, DDP_FLAG_CLASS_PRIOR and
+  // DDP_FLAG_SCORE_PRIOR are ignored (the buffers they carve lie behind everything used here)
   ddp_cfg no_hints;
-  if (cfg && (cfg->flags & (DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR))) {
+  if (cfg && (cfg->flags & (DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR | DDP_FLAG_SCORE_PRIOR))) {
     no_hints = *cfg;
-    no_hints.flags &= ~(DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR);
+    no_hints.flags &= ~(DDP_FLAG_X0_HINTS | DDP_FLAG_PRIOR_START | DDP_FLAG_CLASS_PRIOR | DDP_FLAG_SCORE_PRIOR);
     cfg = &no_hints;
   }
   DDP_TRY(validate(cfg));
@@ -2679,6 +2701,10 @@ int validate_fcn_loop(const ddp_cfg* cfg, int num_convs, int dilation) {
   }
   if (cfg->flags & DDP_FLAG_CLASS_PRIOR) {
     set_error("sample_fcn: DDP_FLAG_CLASS_PRIOR is built for ddp_sample only (the FCN loop takes no class prior)");
+    return DDP_E_BADCFG;
+  }
+  if (cfg->flags & DDP_FLAG_SCORE_PRIOR) {
+    set_error("sample_fcn: DDP_FLAG_SCORE_PRIOR is built for ddp_sample only (the FCN loop takes no score prior)");
     return DDP_E_BADCFG;
   }
   if (num_convs < 0 || num_convs > 8 || dilation < 1) {

@@ -21,9 +21,7 @@ __global__ void __launch_bounds__(256) k_class_prior(const float* __restrict__ t
   const size_t i = size_t(blockIdx.x) * 256 + k;
   float p = 0.f, b = 0.f;
   if (k < num_classes) {
-    p = table[i];
-    if (!(p == p)) p = 0.f;                          // NaN reads as "no prior"
-    p = fminf(fmaxf(p, -1e30f), 1e30f);
+    p = prior_normalise(table[i]);
     b = head_b[k] + p;
   }
   bias_rows[i] = b;

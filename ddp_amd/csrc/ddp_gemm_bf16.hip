@@ -205,11 +205,11 @@ int launch_tail_tf(const b3::LayerArgs& la, int grid, hipStream_t st) {
   prof_end(TAG_HEAD, st);
   return check_launch(MODE == 4 ? "b3::k_layer (seg tail + next step head)" : "b3::k_layer (seg tail)");
 }
-// la.x0_force (DDP_FLAG_FORCE_X0, a test instrument; DDP_FLAG_X0_HINTS) or la.cp_bias (DDP_FLAG_CLASS_PRIOR) selects the conditioned
-// instantiation; the product path runs <.., false>
+// la.x0_force (DDP_FLAG_FORCE_X0, a test instrument; DDP_FLAG_X0_HINTS), la.cp_bias (DDP_FLAG_CLASS_PRIOR) or la.sp_rows
+// (DDP_FLAG_SCORE_PRIOR) selects the conditioned instantiation; the product path runs <.., false>
 template <int MODE, int NCH>
 int launch_tail_t(const b3::LayerArgs& la, int grid, hipStream_t st) {
-  return (la.x0_force || la.cp_bias) ? launch_tail_tf<MODE, NCH, true>(la, grid, st) : launch_tail_tf<MODE, NCH, false>(la, grid, st);
+  return (la.x0_force || la.cp_bias || la.sp_rows) ? launch_tail_tf<MODE, NCH, true>(la, grid, st) : launch_tail_tf<MODE, NCH, false>(la, grid, st);
 }
 }  // namespace
 
@@ -229,6 +229,8 @@ int launch_b3_tail(const TailLaunch& a, hipStream_t st) {
   la.x0_keep = a.x0_keep;
   la.cp_bias = a.cp_bias;
   la.cp_rn = a.cp_rn;
+  la.sp_rows = a.sp_rows;
+  la.sp_n = a.sp_n;
   la.num_classes = a.num_classes;
   la.ldl = a.ldl;
   la.prob_mode = a.prob_mode;

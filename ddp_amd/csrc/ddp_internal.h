@@ -135,6 +135,8 @@ struct TailLaunch {
   int x0_keep;                    // DDP_FLAG_X0_HINTS: x0_force is the hint row buffer - a value >= num_classes keeps the argmax
   const float* cp_bias;           // DDP_FLAG_CLASS_PRIOR: (B, 256) per-image conv_seg bias rows (bias + prior), the row of token m is
   int cp_rn;                      //   m / cp_rn (cp_rn = r * N); nullptr: the one bias of bias_ext / seg_bias
+  const float* sp_rows;           // DDP_FLAG_SCORE_PRIOR: (B * N, KP) per-pixel prior rows (KP = 64 * ceil(num_classes / 64)), the row of
+  int sp_n;                       //   token m is (m / cp_rn) * sp_n + m % sp_n (sp_n = N), added to the accumulator start; nullptr: none
   int M, num_classes, ldl, prob_mode;
   float alpha, sigma, alpha_next, sigma_next;
   // fuse_next: this launch is also the head of the NEXT step (k_layer MODE 4): mask_sb = nullptr, the update runs on
@@ -282,6 +284,10 @@ struct SegUpdateArgs {
   // they are read and the sums are written back to `logits` (the last step's are the output without accumulation); nullptr: none
   const float* cp_delta;
   int cp_rn;
+  // DDP_FLAG_SCORE_PRIOR: (B * N, sp_kp) per-pixel prior rows, normalised; row (m / cp_rn) * sp_n + m % sp_n (sp_n = N) is added to the
+  // scores of token m behind cp_delta's and the sums are written back in the same way; nullptr: none
+  const float* sp_rows;
+  int sp_n, sp_kp;
 };
 int launch_seg_update(const SegUpdateArgs& a, hipStream_t st);
 // x0 = (sigmoid(E[argmax_k scores]) * 2 - 1) * bit_scale, NCHW (B,K,N) -> (B,256,N)
@@ -461,6 +467,16 @@ int launch_hint_rows(const void* map, void* rows, int task, int B, int r, int N,
 // bias_rows (B, 256) = head_b + prior (zero beyond num_classes), delta_rows (B, 256) = prior (zero beyond num_classes)
 int launch_class_prior(const float* table, const float* head_b, float* bias_rows, float* delta_rows, int B, int num_classes,
                        hipStream_t st);
+
+// ---- ddp_score_prior.hip (DDP_FLAG_SCORE_PRIOR) -----------------------------------------------------
+// the caller's NCHW map (B, num_classes, N) normalised like the class prior (prior_normalise) and transposed token-major:
+// rows (B * N, KP), KP = 64 * ceil(num_classes / 64), row b * N + n, zero in columns >= num_classes
+int launch_score_prior_rows(const float* map, float* rows, int B, int num_classes, int N, hipStream_t st);
+// NaN -> 0, clamp to [-1e30, 1e30]: the one normalisation of both priors (-inf excludes a class with a finite score)
+__device__ __forceinline__ float prior_normalise(float p) {
+  if (!(p == p)) p = 0.f;                            // NaN reads as "no prior"
+  return fminf(fmaxf(p, -1e30f), 1e30f);
+}
 
 // ---- ddp_prior_start.hip (DDP_FLAG_PRIOR_START) -----------------------------------------------------
 // out (B, r, Cm, N) = alpha x0(prior) + sigma eps (seg / bev; Cm = 256) or alpha x0(prior) + eps / sigma (depth; Cm = 1), eps

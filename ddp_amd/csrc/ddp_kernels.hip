@@ -1641,8 +1641,11 @@ __global__ void __launch_bounds__(256) k_seg_update(SegUpdateArgs a) {
   for (int q = 0; q < 4; ++q) {
     const int k = lane + 64 * q;
     v[q] = (k < K) ? lg[k] : -INFINITY;
-    if (a.cp_delta && k < K) {      // DDP_FLAG_CLASS_PRIOR: the image's prior row in front of every reader of the score, the output included
-      v[q] += a.cp_delta[size_t(m / a.cp_rn) * 256 + k];
+    if ((a.cp_delta || a.sp_rows) && k < K) {
+      // DDP_FLAG_CLASS_PRIOR: the image's prior row in front of every reader of the score, the output included; DDP_FLAG_SCORE_PRIOR:
+      // the pixel's row behind it (both priors add, in the order of the layer kernel's tails)
+      if (a.cp_delta) v[q] += a.cp_delta[size_t(m / a.cp_rn) * 256 + k];
+      if (a.sp_rows) v[q] += a.sp_rows[(size_t(m / a.cp_rn) * a.sp_n + m % a.sp_n) * a.sp_kp + k];
       const_cast<float*>(lg)[k] = v[q];
     }
     if (k < K && (v[q] > best)) {   // strict >: keeps the first (smallest k) maximum within the lane

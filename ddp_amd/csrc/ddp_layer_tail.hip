@@ -37,7 +37,7 @@ int launch_lt_other(const b3::LayerArgs& la, int grid, hipStream_t st) {
 // teacher forcing (DDP_FLAG_FORCE_X0) is a test instrument: its instantiations exist without the non-temporal variant
 template <int NCH>
 int launch_lt_n(const b3::LayerArgs& la, int grid, hipStream_t st) {
-  if (la.x0_force || la.cp_bias) return launch_lt<NCH, false, true>(la, grid, st);
+  if (la.x0_force || la.cp_bias || la.sp_rows) return launch_lt<NCH, false, true>(la, grid, st);
   if (la.M >= b3::LYR_NT_MIN_TOKENS) return launch_lt<NCH, true, false>(la, grid, st);
   return launch_lt<NCH, false, false>(la, grid, st);
 }
@@ -49,7 +49,7 @@ int launch_b3_layer_tail(const LayerLaunch& l, const TailLaunch& t, const unsign
                          const float* seg_bias, hipStream_t st) {
   if (l.M <= 0) return DDP_OK;
   if (!b3_layer_tail_supported(t.num_classes) || t.mask_sb || l.M != t.M || l.Q != t.Q || t.kind < 0 || t.kind > 2 ||
-      (t.kind != 0 && (t.fuse_next || t.num_classes > 32 || t.x0_force || t.cp_bias || (t.x0_idx && t.num_classes > 8)))) {
+      (t.kind != 0 && (t.fuse_next || t.num_classes > 32 || t.x0_force || t.cp_bias || t.sp_rows || (t.x0_idx && t.num_classes > 8)))) {
     set_error("layer + tail kernel: unsupported call (kind %d, classes %d, legacy noisy map %d)", t.kind, t.num_classes, t.mask_sb ? 1 : 0);
     return DDP_E_BADCFG;
   }
@@ -83,6 +83,8 @@ int launch_b3_layer_tail(const LayerLaunch& l, const TailLaunch& t, const unsign
   la.x0_keep = t.x0_keep;
   la.cp_bias = t.cp_bias;
   la.cp_rn = t.cp_rn;
+  la.sp_rows = t.sp_rows;
+  la.sp_n = t.sp_n;
   la.num_classes = t.num_classes;
   la.ldl = t.ldl;
   la.prob_mode = t.prob_mode;

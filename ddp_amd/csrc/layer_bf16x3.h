@@ -177,6 +177,11 @@ struct LayerArgs {
   // its image, m / cp_rn (cp_rn = r * N), instead of the one row in LDS - a 32-token group may straddle two images.  nullptr: none
   const float* cp_bias;
   int cp_rn;
+  // DDP_FLAG_SCORE_PRIOR (behind the class-prior fields).  sp_rows: (B * N, 64 * NCH) per-pixel prior rows, normalised, zero padded;
+  // the FORCE instantiations of the seg tails add the row of the token's pixel, (m / cp_rn) * sp_n + m % sp_n (sp_n = N; cp_rn is set
+  // with or without cp_bias), to the accumulator start - all r replicas of a pixel read the same row.  nullptr: none
+  const float* sp_rows;
+  int sp_n;
 };
 
 // vmcnt(12): everything but the 12 newest vector-memory ops (= the DMA pieces of the stage just issued) is done
@@ -1576,6 +1581,22 @@ k_layer(LayerArgs la) {
           }
         }
         if (!own_row) bias_init(lg[c], MODE == 6 ? LYR_T_SEG / 64 + c : c);
+        if constexpr (FORCE) {
+          // DDP_FLAG_SCORE_PRIOR: fl32(start + p), p the row of this lane's pixel - the same eight 16-byte loads, the same clamp of
+          // a padding token to M - 1 (the last pixel's row, in range)
+          if (la.sp_rows) {
+            const int mi = m_base + j < M ? m_base + j : M - 1;
+            const float* row = la.sp_rows + (size_t(mi / la.cp_rn) * la.sp_n + mi % la.sp_n) * (NCH * 64) + c * 64 + 4 * h;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(row + t * 32 + 8 * g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) lg[c][t][4 * g + e] += p[e];
+              }
+          }
+        }
         tall_pair(lg[c][0], lg[c][1], I1);
       }
       const int m = m_base + j;

@@ -212,8 +212,13 @@ class DDPEngine(_SeededNoise):
                  gather_guess_zero=False, force_x0=False, fused_tail=None, nchw_head=None, depth_scale_up=False,
                  depth_use_eps=True, depth_bins=None, depth_norm='linear', head_min_depth=None, head_max_depth=None,
                  bev_prescale=1.0, bev_seg_kernel=1, record_steps=False, seeded_noise=False, ddpm_chain=None, x0_hints=False,
-                 prior_start=False, t_start=1.0, class_prior=False):
-        """``class_prior`` (DDP_FLAG_CLASS_PRIOR; seg): a per-image additive prior on the conv_seg scores, in front of everything that
+                 prior_start=False, t_start=1.0, class_prior=False, score_prior=False):
+        """``score_prior`` (DDP_FLAG_SCORE_PRIOR; seg): a per-pixel additive prior on the conv_seg scores, in front of everything that
+        reads them at every step - ``set_score_prior()`` / ``score_prior_view()`` / ``clear_score_prior()``,
+        ``SampleGraph.replay(score_prior=)``.  (B, num_classes, h, w) float32, NCHW; ``-inf`` excludes a class at a pixel, NaN reads
+        as 0; adds to ``class_prior``.  The engine writes zeros (no prior) whenever it allocates or regrows the workspace and on every
+        ``set_geometry``.
+        ``class_prior`` (DDP_FLAG_CLASS_PRIOR; seg): a per-image additive prior on the conv_seg scores, in front of everything that
         reads them at every step - ``set_class_prior()`` / ``class_prior_view()`` / ``clear_class_prior()``,
         ``SampleGraph.replay(class_prior=)``.  (B, num_classes) float32; ``-inf`` excludes a class (``class_mask_to_prior``), NaN
         reads as 0.  The engine writes zeros (no prior) whenever it allocates or regrows the workspace and on every ``set_geometry``.
@@ -338,6 +343,10 @@ class DDPEngine(_SeededNoise):
             if task != 'seg':
                 raise ValueError(f'class_prior is built for the segmentation sampler (DDP_FLAG_CLASS_PRIOR): task {task!r} takes none')
             cfg.flags |= _lib.FLAG_CLASS_PRIOR
+        if score_prior:
+            if task != 'seg':
+                raise ValueError(f'score_prior is built for the segmentation sampler (DDP_FLAG_SCORE_PRIOR): task {task!r} takes none')
+            cfg.flags |= _lib.FLAG_SCORE_PRIOR
         self.t_start = float(t_start)
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
@@ -362,6 +371,7 @@ class DDPEngine(_SeededNoise):
         self.clear_hints(_if_any=True)
         self.clear_prior(_if_any=True)
         self.clear_class_prior(_if_any=True)
+        self.clear_score_prior(_if_any=True)
 
     def _workspace_bytes(self):
         nbytes = C.c_size_t(0)
@@ -466,6 +476,28 @@ class DDPEngine(_SeededNoise):
         with torch.cuda.device(self.device):
             v.zero_()
 
+    # ---- DDP_FLAG_SCORE_PRIOR ------------------------------------------------------------------
+    def score_prior_view(self):
+        """(B, num_classes, h, w) float32 VIEW of the caller-written score prior map inside the workspace.  The library reads it when
+        ddp_sample runs (a captured graph picks up what it holds at replay).  Place: include/ddp_mi355x.h, "score prior"."""
+        c = self.cfg
+        if not c.flags & _lib.FLAG_SCORE_PRIOR:
+            raise _lib.DdpError('the score prior needs an engine built with score_prior=True')
+        return self._region('sprior_map', torch.float32, (c.batch, c.num_classes, c.h, c.w))
+
+    def set_score_prior(self, prior):
+        """copy ``prior`` (B, num_classes, h, w) - a floating-point tensor on the engine's device - into the map (stream-ordered)"""
+        v = self.score_prior_view()
+        self._write_region(v, prior, 'score_prior', 'floating-point', 'batch, num_classes, h, w', 'the score prior is')
+
+    def clear_score_prior(self, _if_any=False):
+        """no prior: every entry 0 (the bits of the flag-clear call)"""
+        if _if_any and not self.cfg.flags & _lib.FLAG_SCORE_PRIOR:
+            return
+        v = self.score_prior_view()
+        with torch.cuda.device(self.device):
+            v.zero_()
+
     # ------------------------------------------------------------------------------------------
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -510,6 +542,7 @@ class DDPEngine(_SeededNoise):
         self.clear_hints(_if_any=True)   # (and the hint map: another geometry or another buffer - unset hints are no hints)
         self.clear_prior(_if_any=True)   # (and the prior map)
         self.clear_class_prior(_if_any=True)   # (and the class prior table)
+        self.clear_score_prior(_if_any=True)   # (and the score prior map)
         return self
 
     def out_shape(self):
@@ -675,9 +708,11 @@ def caller_regions(cfg, workspace_bytes):
     px = 1 if seg else 4                                            # bytes per pixel of a hint / prior map
     noise = n * cfg.randsteps * (1 if depth else 256) * 4           # a (B, r, Cm, h, w) float map: start noise, start map
     rec, smap = step_record_sizes(cfg)
-    cp, ps, xh, sn, sr = (bool(f & b) for b in (_lib.FLAG_CLASS_PRIOR, _lib.FLAG_PRIOR_START, _lib.FLAG_X0_HINTS,
-                                                _lib.FLAG_SEEDED_NOISE, _lib.FLAG_STEP_RECORD))
-    table = [('cprior_rows', 2 * cfg.batch * 256 * 4, cp), ('cprior_table', cfg.batch * 256 * 4, cp),
+    sp, cp, ps, xh, sn, sr = (bool(f & b) for b in (_lib.FLAG_SCORE_PRIOR, _lib.FLAG_CLASS_PRIOR, _lib.FLAG_PRIOR_START,
+                                                    _lib.FLAG_X0_HINTS, _lib.FLAG_SEEDED_NOISE, _lib.FLAG_STEP_RECORD))
+    kp = (cfg.num_classes + 63) // 64 * 64                          # the score prior's row length: whole 64-class chunks
+    table = [('sprior_rows', n * kp * 4, sp), ('sprior_map', n * cfg.num_classes * 4, sp),
+             ('cprior_rows', 2 * cfg.batch * 256 * 4, cp), ('cprior_table', cfg.batch * 256 * 4, cp),
              ('prior_start', noise, ps and not sn), ('prior_map', n * px, ps),
              ('hint_rows', n * cfg.randsteps * px, xh), ('hint_map', n * px, xh),
              ('seed_noise', noise, sn),
@@ -702,6 +737,13 @@ def class_prior_places(cfg, workspace_bytes):
     workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): the caller's table, the library's per-image vectors in front of it."""
     r = caller_regions(cfg, workspace_bytes)
     return r['cprior_table'] + r['cprior_rows']
+
+
+def score_prior_places(cfg, workspace_bytes):
+    """(map_offset, map_bytes, rows_offset, rows_bytes) of include/ddp_mi355x.h ("score prior"), in bytes from the start of a
+    workspace of ``workspace_bytes`` = ddp_query_workspace(cfg): the caller's NCHW map, the library's token-major rows in front of it."""
+    r = caller_regions(cfg, workspace_bytes)
+    return r['sprior_map'] + r['sprior_rows']
 
 
 def class_mask_to_prior(mask):
@@ -740,8 +782,10 @@ class SampleGraph:
         self.workspace_ptr = engine.workspace.data_ptr()
 
     def replay(self, x=None, noise=None, step_noise=None, seed=None, image_base=None, call=None, hints=None, prior=None,
-               class_prior=None):
-        """``class_prior`` (class_prior engines): written to the engine's table in front of the launch (``DDPEngine.set_class_prior``);
+               class_prior=None, score_prior=None):
+        """``score_prior`` (score_prior engines): written to the engine's map in front of the launch (``DDPEngine.set_score_prior``);
+        None: the graph runs on what the map holds.
+        ``class_prior`` (class_prior engines): written to the engine's table in front of the launch (``DDPEngine.set_class_prior``);
         None: the graph runs on what the table holds.
         ``prior`` (prior_start engines): written to the engine's prior map in front of the launch (``DDPEngine.set_prior``); None:
         the graph runs on what the map holds.
@@ -776,6 +820,8 @@ class SampleGraph:
             eng.set_prior(prior)
         if class_prior is not None:
             eng.set_class_prior(class_prior)
+        if score_prior is not None:
+            eng.set_score_prior(score_prior)
         self.graph.replay()
         return self.out
 
@@ -787,7 +833,9 @@ class FcnSamplerEngine(_SeededNoise):
     def __init__(self, state_dict, head, *, h, w, batch=1, randsteps=1, timesteps=3, num_classes=150, bit_scale=0.01,
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
                  device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False, x0_hints=False,
-                 prior_start=False, class_prior=False):
+                 prior_start=False, class_prior=False, score_prior=False):
+        if score_prior:
+            raise ValueError('score_prior is built for ddp_sample only (DDP_FLAG_SCORE_PRIOR): the FCN-head loop takes no score prior')
         if class_prior:
             raise ValueError('class_prior is built for ddp_sample only (DDP_FLAG_CLASS_PRIOR): the FCN-head loop takes no class prior')
         if prior_start:

@@ -126,6 +126,25 @@ class _SamplerMixin:
         (possibly replaced) members exactly as before"""
         return {} if class_prior is None else dict(class_prior=class_prior)
 
+    def _score_prior_map(self, score_prior, b, h, w, device):
+        """``score_prior`` (b, num_classes, H, W) float -> the float32 NCHW map of the engine (DDP_FLAG_SCORE_PRIOR) on ``device``: a map
+        that is not at the map resolution (h, w) is resized there as the scores are resized on the way out,
+        ``F.interpolate(mode='bilinear', align_corners=self.align_corners)``, on the device.  (Bilinear weights mix neighbours: an
+        excluded class, ``-inf``, stays excluded only on pixels all of whose neighbours exclude it - give such a map at (h, w).)"""
+        if not torch.is_tensor(score_prior) or score_prior.dim() != 4 or tuple(score_prior.shape[:2]) != (b, self.num_classes) \
+                or not score_prior.dtype.is_floating_point:
+            raise ValueError(f'score_prior must be a float (batch, num_classes, H, W) = ({b}, {self.num_classes}, H, W) tensor, got '
+                             f'{tuple(score_prior.shape) if torch.is_tensor(score_prior) else type(score_prior)}')
+        t = score_prior.to(device=device, dtype=torch.float32)
+        if tuple(t.shape[2:]) != (h, w):
+            t = F.interpolate(t, size=(h, w), mode='bilinear', align_corners=self.align_corners)
+        return t.contiguous()
+
+    @staticmethod
+    def _sp_kw(score_prior):
+        """the keyword that carries a score prior down the call chain - none without one (as ``_cp_kw``)"""
+        return {} if score_prior is None else dict(score_prior=score_prior)
+
     @staticmethod
     def _check_t_start(prior, t_start):
         if prior is not None and t_start is None:
@@ -209,7 +228,8 @@ class DDP(nn.Module, _SamplerMixin):
         return times
 
     def _engine_for(self, b, h, w, device, sampler, timesteps=None, randsteps=None, accumulation=None, kind='sample',
-                    record_steps=False, seeded=False, hints=False, prior=False, t_start=None, class_prior=False):
+                    record_steps=False, seeded=False, hints=False, prior=False, t_start=None, class_prior=False,
+                    score_prior=False):
         from ..decode_heads.fcn_head_with_time import FCNHeadWithTime
         K = self.timesteps if timesteps is None else timesteps
         r = self.randsteps if randsteps is None else randsteps
@@ -221,8 +241,11 @@ class DDP(nn.Module, _SamplerMixin):
         ts = 1.0 if t_start is None else float(t_start)
         chain = bool(self.ddpm_chain) and sampler == 'ddpm'
         key = (kind, str(device), sampler, K, r, acc, self.bit_scale, self.time_difference, self.sample_range[0],
-               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints), bool(prior), ts, bool(class_prior))
+               self.noise_schedule, bool(record_steps), bool(seeded), chain, bool(hints), bool(prior), ts, bool(class_prior),
+               bool(score_prior))
         if isinstance(self.decode_head, FCNHeadWithTime):
+            if score_prior:
+                raise ValueError('score_prior is built for the deformable head\'s sampler: the FCNHeadWithTime loop takes none')
             if class_prior:
                 raise ValueError('class_prior is built for the deformable head\'s sampler: the FCNHeadWithTime loop takes none')
             if prior or ts != 1.0:
@@ -243,7 +266,7 @@ class DDP(nn.Module, _SamplerMixin):
             nl = count_layers(self.hot_path_state_dict())
             return DDPEngine(None, 'seg', h=h, w=w, feat_channels=256, weights=self._packed_weights(device, 'seg', nl),
                              ddpm_chain=chain, x0_hints=bool(hints), prior_start=bool(prior), t_start=ts,
-                             class_prior=bool(class_prior), **common)
+                             class_prior=bool(class_prior), score_prior=bool(score_prior), **common)
         return self._get_engine(key, factory, geometry=(b, h, w))
 
     def hot_path_state_dict(self):
@@ -258,8 +281,13 @@ class DDP(nn.Module, _SamplerMixin):
 
     @torch.no_grad()
     def ddim_sample(self, x, img_metas=None, noise=None, return_steps=False, image_base=0, call=0, hints=None, prior=None,
-                    t_start=None, class_prior=None):
-        """``class_prior`` (b, num_classes) float (call-time only; DDP_FLAG_CLASS_PRIOR): row i is added to the conv_seg scores of
+                    t_start=None, class_prior=None, score_prior=None):
+        """``score_prior`` (b, num_classes, H, W) float (call-time only; DDP_FLAG_SCORE_PRIOR): entry [i][k][y][x] is added to the
+        conv_seg score of class k at that pixel of image i at every step, in front of the argmax that is fed back, the accumulated
+        softmax and the scores returned - what the sampler computes when the decode head returns ``scores + score_prior[i]``.  A map
+        that is not at (h, w) is resized there (bilinear, ``align_corners`` of the model).  ``-inf`` excludes a class at a pixel; NaN
+        reads as 0; adds to ``class_prior``.
+        ``class_prior`` (b, num_classes) float (call-time only; DDP_FLAG_CLASS_PRIOR): row i is added to the conv_seg scores of
         image i at every step, in front of the argmax that is fed back, the accumulated softmax and the scores returned - what a
         model with ``conv_seg.bias + class_prior[i]`` would compute for image i.  ``-inf`` excludes a class
         (``ddp_amd.engine.class_mask_to_prior``); NaN reads as 0.
@@ -286,6 +314,9 @@ class DDP(nn.Module, _SamplerMixin):
         cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
         if cp is not None:
             hk.update(class_prior=True)
+        sp = None if score_prior is None else self._score_prior_map(score_prior, b, h, w, x.device)
+        if sp is not None:
+            hk.update(score_prior=True)
         if noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True, **hk)
             if hmap is not None:
@@ -294,6 +325,8 @@ class DDP(nn.Module, _SamplerMixin):
                 eng.set_prior(pmap)
             if cp is not None:
                 eng.set_class_prior(cp)
+            if sp is not None:
+                eng.set_score_prior(sp)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
@@ -305,13 +338,15 @@ class DDP(nn.Module, _SamplerMixin):
             eng.set_prior(pmap)
         if cp is not None:
             eng.set_class_prior(cp)
+        if sp is not None:
+            eng.set_score_prior(sp)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     @torch.no_grad()
     def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0, hints=None,
-                    prior=None, t_start=None, class_prior=None):
-        """``hints``, ``prior``, ``t_start``, ``class_prior``: as ``ddim_sample``"""
+                    prior=None, t_start=None, class_prior=None, score_prior=None):
+        """``hints``, ``prior``, ``t_start``, ``class_prior``, ``score_prior``: as ``ddim_sample``"""
         self._check_feature(x)
         b, c, h, w = x.shape
         self._check_t_start(prior, t_start)
@@ -323,6 +358,9 @@ class DDP(nn.Module, _SamplerMixin):
         cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
         if cp is not None:
             hk.update(class_prior=True)
+        sp = None if score_prior is None else self._score_prior_map(score_prior, b, h, w, x.device)
+        if sp is not None:
+            hk.update(score_prior=True)
         if noise is None and step_noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True, **hk)
             if hmap is not None:
@@ -331,6 +369,8 @@ class DDP(nn.Module, _SamplerMixin):
                 eng.set_prior(pmap)
             if cp is not None:
                 eng.set_class_prior(cp)
+            if sp is not None:
+                eng.set_score_prior(sp)
             out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
             return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
         if noise is None:
@@ -344,26 +384,29 @@ class DDP(nn.Module, _SamplerMixin):
             eng.set_prior(pmap)
         if cp is not None:
             eng.set_class_prior(cp)
+        if sp is not None:
+            eng.set_score_prior(sp)
         out = eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
         return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)
 
-    def encode_decode(self, img, img_metas=None, image_base=0, call=0, class_prior=None):
-        """ddp.py:114-129."""
+    def encode_decode(self, img, img_metas=None, image_base=0, call=0, class_prior=None, score_prior=None):
+        """ddp.py:114-129.  ``score_prior``: see ``ddim_sample``."""
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+            out = self.ddim_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior), **self._sp_kw(score_prior))
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+            out = self.ddpm_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior), **self._sp_kw(score_prior))
         else:
             raise NotImplementedError
         return F.interpolate(out, size=img.shape[2:], mode='bilinear', align_corners=self.align_corners)
 
-    def whole_inference(self, img, img_meta=None, rescale=False, image_base=0, call=0, class_prior=None):
-        """encoder_decoder.py:229-248: crop to img_shape and resize to ori_shape when rescale."""
-        seg_logit = self.encode_decode(img, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+    def whole_inference(self, img, img_meta=None, rescale=False, image_base=0, call=0, class_prior=None, score_prior=None):
+        """encoder_decoder.py:229-248: crop to img_shape and resize to ori_shape when rescale.  ``score_prior``: see ``ddim_sample``."""
+        seg_logit = self.encode_decode(img, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior),
+                                       **self._sp_kw(score_prior))
         if rescale and img_meta:
             rs = img_meta[0]['img_shape'][:2]
             seg_logit = seg_logit[:, :, :rs[0], :rs[1]]
@@ -420,9 +463,13 @@ class DDP(nn.Module, _SamplerMixin):
             out = tuple(img_meta[0]['ori_shape'][:2])
         return seg_slide_postprocess(scores, ys, xs, (ch, cw), img.shape[2:], keep, out, self.align_corners, flip, want)
 
-    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None, prior=None, t_start=None, class_prior=None):
+    def slide_inference(self, img, img_meta, rescale, image_base=0, call=0, hints=None, prior=None, t_start=None, class_prior=None,
+                        score_prior=None):
         """``class_prior`` (b, num_classes): every window of image i samples with row i (see ``ddim_sample``).
+        ``score_prior`` is not built for slide inference (ValueError).
         encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
+        if score_prior is not None:
+            raise ValueError('score_prior is not built for slide inference (one score prior map per sampler call, not per window)')
         if prior is not None or t_start is not None:
             raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
         if hints is not None:
@@ -453,9 +500,10 @@ class DDP(nn.Module, _SamplerMixin):
 
     AUG_CALL_STRIDE = 1 << 16            # seeded noise: augmentation a owns the call values [a * stride, (a + 1) * stride)
 
-    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None):
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None,
+                 score_prior=None):
         """``class_prior`` (b, num_classes): an image-level prior has no frame - every augmentation of image i samples with row i.
-        ``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
+        ``hints``, ``prior``, ``t_start`` and ``score_prior`` are not built for test-time augmentation (ValueError).
         With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
         index), so no two augmentations of an image share noise.
         encoder_decoder.py:306-331: mean of the per-augmentation probabilities (multi-scale / flip), then argmax.
@@ -464,6 +512,8 @@ class DDP(nn.Module, _SamplerMixin):
         softmax -> flip-undo for all of them, the mean and the argmax per output pixel: the (1,K,H,W) tensors ``inference``
         materialises per augmentation and the running sum at ori_shape never exist."""
         from ..engine import seg_aug_postprocess
+        if score_prior is not None:
+            raise ValueError('score_prior is not built for aug_test (every augmentation has its own frame)')
         if hints is not None:
             raise ValueError('hints are not built for aug_test (every augmentation has its own frame)')
         if prior is not None or t_start is not None:
@@ -506,8 +556,11 @@ class DDP(nn.Module, _SamplerMixin):
                 flip = meta.get('flip_direction', 'horizontal')
         return crop, out_size, flip
 
-    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None):
-        """``class_prior`` (b, num_classes) float: see ``ddim_sample``; in slide mode every window of image i gets row i.
+    def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None,
+                    score_prior=None):
+        """``score_prior`` (b, num_classes, H, W) float, in the frame of ``img`` or at the map resolution: see ``ddim_sample``; slide
+        mode raises ValueError.
+        ``class_prior`` (b, num_classes) float: see ``ddim_sample``; in slide mode every window of image i gets row i.
         ``prior`` (b,Hp,Wp) uint8 in the frame of ``img`` and ``t_start``: see ``ddim_sample``; slide mode raises ValueError.
         ``hints`` (b,Hh,Wh) uint8 in the frame of ``img``: see ``ddim_sample``; slide mode raises ValueError.
         encoder_decoder.py:250-304 (mode='whole'), post-loop epilogue fused into one kernel:
@@ -519,7 +572,10 @@ class DDP(nn.Module, _SamplerMixin):
         if prior is not None or t_start is not None:
             hk.update(prior=prior, t_start=t_start)
         hk.update(self._cp_kw(class_prior))
+        hk.update(self._sp_kw(score_prior))
         if self._mode() == 'slide':
+            if score_prior is not None:
+                raise ValueError('score_prior is not built for slide inference (one score prior map per sampler call, not per window)')
             if prior is not None or t_start is not None:
                 raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
             if hints is not None:
@@ -554,8 +610,9 @@ class DDP(nn.Module, _SamplerMixin):
         return res
 
     def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, hints=None, prior=None, t_start=None,
-                class_prior=None, **kwargs):
-        """``class_prior``: see ``simple_test`` / ``aug_test``.
+                class_prior=None, score_prior=None, **kwargs):
+        """``score_prior``: see ``simple_test`` (``aug_test`` raises ValueError when given one).
+        ``class_prior``: see ``simple_test`` / ``aug_test``.
         ``hints``, ``prior``, ``t_start``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
         base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
         augmentation lists the test pipeline produces."""
@@ -568,14 +625,14 @@ class DDP(nn.Module, _SamplerMixin):
                 return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
                                      **({} if hints is None else {'hints': hints}),
                                      **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
-                                     **self._cp_kw(class_prior))
+                                     **self._cp_kw(class_prior), **self._sp_kw(score_prior))
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
         return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
                                 **({} if hints is None else {'hints': hints}),
                                 **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
-                                **self._cp_kw(class_prior))
+                                **self._cp_kw(class_prior), **self._sp_kw(score_prior))
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
@@ -590,8 +647,9 @@ class SelfAlignedDDP(DDP):
     (:150-164) - is exposed as ``self_aligned_predict``."""
 
     @torch.no_grad()
-    def self_aligned_predict(self, x, noise=None, return_logits=False, image_base=0, call=0, class_prior=None):
-        """``class_prior`` (b, num_classes): added to the pass's scores in front of the argmax (see ``ddim_sample``).
+    def self_aligned_predict(self, x, noise=None, return_logits=False, image_base=0, call=0, class_prior=None, score_prior=None):
+        """``score_prior`` (b, num_classes, H, W): added to the pass's scores in front of the argmax (see ``ddim_sample``).
+        ``class_prior`` (b, num_classes): added to the pass's scores in front of the argmax (see ``ddim_sample``).
         self_aligned_ddp.py:150-164: ONE decoder pass at t = 1 on pure noise, then the x0 projection:
             feat = transform(cat[x, noise]); logits = decode_head(feat, time_mlp(log_snr(1)))
             preds = (sigmoid(embedding_table(argmax(logits))) * 2 - 1) * bit_scale
@@ -605,12 +663,17 @@ class SelfAlignedDDP(DDP):
         b, c, h, w = x.shape
         cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
         ck = {} if cp is None else dict(class_prior=True)
+        sp = None if score_prior is None else self._score_prior_map(score_prior, b, h, w, x.device)
+        if sp is not None:
+            ck.update(score_prior=True)
         # the head dispatch of _engine_for (the reference's pre-pass goes through the generic _decode_head_forward_test)
         if noise is None and self.noise_seed is not None:
             eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned',
                                    seeded=True, **ck)
             if cp is not None:
                 eng.set_class_prior(cp)
+            if sp is not None:
+                eng.set_score_prior(sp)
             logits = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
         else:
             if noise is None:
@@ -618,6 +681,8 @@ class SelfAlignedDDP(DDP):
             eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned', **ck)
             if cp is not None:
                 eng.set_class_prior(cp)
+            if sp is not None:
+                eng.set_score_prior(sp)
             logits = eng.sample(x.contiguous().float(), noise.reshape(b, 1, c, h, w).contiguous().float())
         preds = torch.empty((b, 256, h, w), dtype=torch.float32, device=x.device)
         emb = self.embedding_table.weight.detach().float().contiguous()

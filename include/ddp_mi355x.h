@@ -124,8 +124,16 @@ enum { DDP_FLAG_UNFUSED_LAYER = 1, DDP_FLAG_UNFUSED_PROLOGUE = 2, DDP_FLAG_RECOR
                                         in front of everything that reads the scores - see "class prior" below.  Combines with every
                                         other flag of ddp_sample.  Refused (DDP_E_BADCFG) for depth and bev and by ddp_sample_fcn,
                                         ddp_prepare_fcn and ddp_sample_fcn_workspace; ddp_head_forward ignores it.  (Bits 8192 and
-                                        32768 stay undefined, every bit above this one is refused.)  Clear: launches, workspace sizes
+                                        32768 stay undefined; the bits above this one: DDP_FLAG_SCORE_PRIOR.)  Clear: launches, workspace sizes
                                         and outputs are unchanged */,
+       DDP_FLAG_SCORE_PRIOR = 1048576 /* model surface, seg through ddp_sample, both samplers, both engines, every route: a per-pixel
+                                         additive prior on the conv_seg scores, read from a caller-written NCHW map (B, num_classes,
+                                         h, w) and applied in front of everything that reads the scores - see "score prior" below.
+                                         Combines with every other flag of ddp_sample, DDP_FLAG_CLASS_PRIOR (both priors add) and 256
+                                         classes included.  Refused (DDP_E_BADCFG) for depth and bev and by ddp_sample_fcn,
+                                         ddp_prepare_fcn and ddp_sample_fcn_workspace; ddp_head_forward ignores it.  (Bits 8192, 32768,
+                                         262144 and 524288 stay undefined and every bit above this one is refused.)  Clear: launches,
+                                         workspace sizes and outputs are unchanged */,
        DDP_FLAG_SB_HEAD = 128 /* the first step's head as the four launches it was fused from (NCHW -> split fragments of x and of
                                   the start noise, the x-projection GEMM, k_layer MODE 2) instead of ONE kernel that reads the
                                   caller's NCHW tensors directly (k_layer MODE 7); A/B runs and parity tests of the separate kernels */,
@@ -229,6 +237,7 @@ int ddp_abi_version(void);
  * THE TAIL OF THE WORKSPACE: the buffers a caller reads or writes directly are the LAST of the workspace, in one fixed order.  Each
  * group exists only with its flag, each buffer is rounded up to 256 bytes (round256), and nothing follows the last one (the sizes
  * are the formulas of the sections named on the right):
+ *   0. DDP_FLAG_SCORE_PRIOR: round256(rows_bytes), then round256(map_bytes)                                       "score prior"
  *   1. DDP_FLAG_CLASS_PRIOR    round256(bias_bytes), then round256(table_bytes)                                    "class prior"
  *   2. DDP_FLAG_PRIOR_START    [DDP_FLAG_SEEDED_NOISE clear: round256(start_bytes)], then round256(prior_bytes)    "prior start"
  *   3. DDP_FLAG_X0_HINTS       round256(row_bytes), then round256(hint_bytes)                                      "x0 hints"
@@ -236,9 +245,9 @@ int ddp_abi_version(void);
  *   5. DDP_FLAG_STEP_RECORD    round256(record_bytes), then round256(map_bytes)                                    at ddp_x0_trace
  * A buffer starts at ddp_query_workspace(cfg) minus its own rounded size and the rounded sizes of everything behind it in this
  * list: the hint map of a cfg with flags 3, 4 and 5 at ddp_query_workspace(cfg) - round256(map_bytes) - round256(record_bytes)
- * - round256(noise_bytes) - round256(hint_bytes).  Setting one of the five flags grows ddp_query_workspace by exactly its group;
+ * - round256(noise_bytes) - round256(hint_bytes).  Setting one of the six flags grows ddp_query_workspace by exactly its group;
  * every offset in front of the group and ddp_query_const_workspace are those of the cfg without the flag.
- * ddp_sample_fcn_workspace ends with groups 4 and 5 in the same way (ddp_sample_fcn refuses flags 1 to 3).
+ * ddp_sample_fcn_workspace ends with groups 4 and 5 in the same way (ddp_sample_fcn refuses flags 0 to 3).
  * ddp_amd.engine.caller_regions is this list on the host side. */
 int ddp_query_workspace(const ddp_cfg* cfg, size_t* bytes);
 
@@ -413,6 +422,37 @@ int ddp_x0_trace(const ddp_cfg* cfg, void* d_workspace, const unsigned char** d_
  * Extra launches with the flag set: one k_class_prior per call.  The layer kernel's seg tails run their conditioned instantiations
  * (the ones DDP_FLAG_FORCE_X0 and DDP_FLAG_X0_HINTS run, which have no non-temporal variant); the flag-clear instantiations are
  * untouched. */
+
+/* score prior (DDP_FLAG_SCORE_PRIOR, seg; csrc/ddp_score_prior.hip).  Soft knowledge about the answer that varies over the image:
+ * the logits of a cheaper model, last frame's scores warped to this frame, a scribble with a strength, a region where some classes
+ * cannot occur.  The SCORE PRIOR MAP is (B, num_classes, h, w) float32 at the map resolution, NCHW - the layout of d_out; entry
+ * [b][k][n] is added to the conv_seg score of class k at pixel n of image b, for all r replicas and all K steps, in front of
+ * everything that reads the score: the argmax fed back as x0 (segmentors/ddp.py:235-239), the accumulated softmax, the returned
+ * last-step scores, the step record and the DDP_FLAG_RECORD_X0 trace.  The call computes what the reference's sampler computes when
+ * its decode head returns scores + prior[b].  One launch per call (k_score_prior_rows, behind k_class_prior) normalises the map as
+ * read THEN by the class prior's rule - NaN reads as 0, every value is clamped to [-1e30, 1e30] - so -inf excludes a class at that
+ * pixel: its score stays finite, its softmax term is exactly 0 and no infinity reaches the bilinear epilogues.
+ * Combination rules: with DDP_FLAG_CLASS_PRIOR both priors add (the image's row first, then the pixel's); with DDP_FLAG_FORCE_X0 /
+ * DDP_FLAG_X0_HINTS the forced or hinted decision is fed back and the returned scores carry the prior; an all-zero map gives the bits
+ * of the flag-clear call; a map that is constant over the pixels of each image gives the bits of DDP_FLAG_CLASS_PRIOR with that row,
+ * on every route.
+ * Sizes and places, as formulas of the cfg - two buffers, each rounded up to 256 bytes, group 0 of the list at ddp_query_workspace;
+ * ddp_query_workspace grows by exactly round256(rows_bytes) + round256(map_bytes), every other offset and
+ * ddp_query_const_workspace are those of the cfg without the flag:
+ *   map_bytes  = batch * num_classes * h * w * 4   the caller-written map, carved IMMEDIATELY IN FRONT of the class-prior buffers (of
+ *                the prior-start, x0-hint, seeded-noise, step-record buffers - whichever come first - or the end of the workspace)
+ *   rows_bytes = batch * h * w * KP * 4, KP = 64 * ceil(num_classes / 64)   library-private, immediately in front of the map: the
+ *                normalised prior token-major, row b * N + n (N = h * w), zero in columns >= num_classes.  A lane of the layer
+ *                kernel's seg tails adds the row of its token's pixel, (m / (r N)) * N + m % N, to the accumulator start of
+ *                conv_seg (lg = fl32(start + p), the start being the class-prior row or conv_seg.bias); k_seg_update adds the same
+ *                row to the head GEMM's scores and writes the sums back on the routes that run conv_seg as a tile GEMM (the fp32
+ *                engine, DDP_FLAG_UNFUSED_LAYER, ddpm without DDP_FLAG_DDPM_CHAIN)
+ * The library never initialises the map: the caller writes it (all zeros = no prior) before the first ddp_sample;
+ * ddp_amd.engine.DDPEngine does so whenever it allocates the workspace or changes the geometry.  The kernel reads the caller's map
+ * from device memory when it runs, so a captured graph picks up a new map on replay.
+ * Extra launches with the flag set: one k_score_prior_rows per call.  The layer kernel's seg tails run their conditioned
+ * instantiations (the ones DDP_FLAG_FORCE_X0, DDP_FLAG_X0_HINTS and DDP_FLAG_CLASS_PRIOR run, which have no non-temporal variant) and
+ * read KP * 4 bytes more per token and step; the flag-clear instantiations are untouched. */
 
 /* ---- finer-grained entry points (unit tests, and the decode_head plugin surface) ------------- */
 

@@ -7,6 +7,7 @@ next while every tagged kernel took the same time - which calls are slow, and wh
   python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= free=DDP_X0_HINTS=free sparse=DDP_X0_HINTS=sparse
   python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= prior=DDP_PRIOR_START=1.0 --tags
   python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= cprior=DDP_CLASS_PRIOR=1 --calls 20 --blocks 2 --tags
+  python scripts/call_times.py --workload ade_swin_t_k3_8x512x1024 clear= sprior=DDP_SCORE_PRIOR=1 --calls 20 --blocks 2 --tags
 
 Per variant and block: the sorted per-call HIP-event times, their median / min / max, the mean power and clock over the block."""
 import argparse
@@ -59,8 +60,15 @@ def main():
         # DDP_CLASS_PRIOR=1: DDP_FLAG_CLASS_PRIOR set (seg), a seeded soft table (+-3 on a third of the classes, another row per image) -
         # likewise a switch of this script
         ck = os.environ.get('DDP_CLASS_PRIOR', '0') not in ('', '0')
+        # DDP_SCORE_PRIOR=1: DDP_FLAG_SCORE_PRIOR set (seg), a seeded soft map (+-3 on a third of the (pixel, class) entries) - likewise
+        sk = os.environ.get('DDP_SCORE_PRIOR', '0') not in ('', '0')
         engines[name] = DDPEngine(sd, task, **(dict(x0_hints=True) if hk else {}), **(dict(prior_start=True, t_start=float(pk)) if pk else {}),
-                                  **(dict(class_prior=True) if ck else {}), **kw)
+                                  **(dict(class_prior=True) if ck else {}), **(dict(score_prior=True) if sk else {}), **kw)
+        if sk:
+            g = torch.Generator(device=dev).manual_seed(10)
+            shape = (wl['batch'], wl['num_classes'], wl['h'], wl['w'])
+            u = torch.rand(shape, generator=g, device=dev)
+            engines[name].set_score_prior(torch.where(u < 1.0 / 6.0, 3.0, 0.0) - torch.where(u > 5.0 / 6.0, 3.0, 0.0))
         if ck:
             g = torch.Generator().manual_seed(9)
             shape = (wl['batch'], wl['num_classes'])
