@@ -73,29 +73,88 @@ def _post(dataset, result, batch_indices, pre_eval, format_only, format_args):
     return result
 
 
-def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None):
+def seg_gt_loader(dataset, index):
+    """the default ``gt_loader`` of ``device_eval``: what ``CustomDataset.pre_eval`` (mmseg/datasets/custom.py:298-312) hands to
+    ``intersect_and_union`` for image ``index``."""
+    return dict(label=dataset.get_gt_seg_map_by_idx(index), num_classes=len(dataset.CLASSES), ignore_index=dataset.ignore_index,
+                reduce_zero_label=dataset.reduce_zero_label)
+
+
+def _post_device(dataset, result, batch_indices, gt_loader):
+    """``device_eval``: ``result`` holds the device maps of ``model(on_device=True)``; the per-image entries of ``dataset.pre_eval``
+    come from ``ddp_amd.evaluation`` - one small device-to-host copy per batch.  uint8 maps are class maps (seg), float32 maps
+    are depth maps; depth needs a caller-given ``gt_loader`` -> dict(gt=, crop=, min_depth=, max_depth=)."""
+    from . import evaluation as ev
+    if not result:
+        return []
+    if any(not torch.is_tensor(r) for r in result):
+        raise TypeError('device_eval=True: the model did not return device tensors (does its test entry take on_device=True?)')
+    if result[0].dtype == torch.uint8:
+        gts = [(gt_loader or seg_gt_loader)(dataset, i) for i in batch_indices]
+        out = [None] * len(result)
+        groups = {}
+        for j, g in enumerate(gts):          # one call per distinct (num_classes, ignore_index, reduce_zero_label): one, in practice
+            groups.setdefault((int(g['num_classes']), int(g['ignore_index']), bool(g['reduce_zero_label'])), []).append(j)
+        for (k, ign, rzl), js in groups.items():
+            for j, t in zip(js, ev.seg_pre_eval([result[j] for j in js], [gts[j]['label'] for j in js], k, ign, rzl)):
+                out[j] = t
+        return out
+    if gt_loader is None:
+        raise ValueError('device_eval=True on depth maps needs gt_loader(dataset, index) -> dict(gt=, crop=, min_depth=, max_depth=): '
+                         'the reference has no ground-truth accessor for depth datasets')
+    gts = [gt_loader(dataset, i) for i in batch_indices]
+    out = [None] * len(result)
+    groups = {}
+    for j, g in enumerate(gts):
+        groups.setdefault((float(g['min_depth']), float(g['max_depth'])), []).append(j)
+    for (lo, hi), js in groups.items():
+        for j, t in zip(js, ev.depth_pre_eval([result[j] for j in js], [gts[j]['gt'] for j in js], lo, hi,
+                                              crops=[gts[j].get('crop') for j in js])):
+            out[j] = t
+    return out
+
+
+def _check_device_eval(device_eval, pre_eval):
+    if device_eval and not pre_eval:
+        raise ValueError('device_eval=True requires pre_eval=True (it replaces dataset.pre_eval; the other paths need the maps on the host)')
+
+
+def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device_eval=False, gt_loader=None):
     """test.py:34-137 without the drawing / deprecated ``efficient_test`` branches.  Returns the list of per-image
-    results (or pre-eval tuples / formatted file names) in dataset order."""
+    results (or pre-eval tuples / formatted file names) in dataset order.
+    ``device_eval=True`` (with ``pre_eval=True``): the model is called with ``on_device=True`` and the per-image pre-eval entries
+    are reduced on the device (``ddp_amd.evaluation``); ``gt_loader(dataset, index)`` supplies the ground truth (default for
+    seg datasets: ``seg_gt_loader``).  The entries equal ``dataset.pre_eval``'s, so ``dataset.evaluate`` is untouched."""
     assert not (pre_eval and format_only), '``pre_eval`` and ``format_only`` are mutually exclusive'
+    _check_device_eval(device_eval, pre_eval)
     model.eval()
     device = _model_device(model)
     dataset = data_loader.dataset
     results = []
     for batch_indices, data in zip(data_loader.batch_sampler, data_loader):
+        if device_eval:
+            results.extend(_post_device(dataset, _run_batch(model, data, device, batch_indices, on_device=True), batch_indices, gt_loader))
+            continue
         result = _run_batch(model, data, device, batch_indices)
         results.extend(_post(dataset, result, batch_indices, pre_eval, format_only, format_args))
     return results
 
 
 def multi_gpu_test(model, data_loader, tmpdir=None, gpu_collect=False, pre_eval=False, format_only=False,
-                   format_args=None):
-    """test.py:140-229: every rank walks its DistributedSampler shard, then the per-rank lists are merged."""
+                   format_args=None, device_eval=False, gt_loader=None):
+    """test.py:140-229: every rank walks its DistributedSampler shard, then the per-rank lists are merged.
+    ``device_eval`` / ``gt_loader``: see ``single_gpu_test``."""
     assert not (pre_eval and format_only), '``pre_eval`` and ``format_only`` are mutually exclusive'
+    _check_device_eval(device_eval, pre_eval)
     model.eval()
     device = _model_device(model)
     dataset = data_loader.dataset
     results = []
     for batch_indices, data in zip(data_loader.batch_sampler, data_loader):
+        if device_eval:
+            results.extend(_post_device(dataset, _run_batch(model, data, device, batch_indices, rescale=True, on_device=True),
+                                        batch_indices, gt_loader))
+            continue
         result = _run_batch(model, data, device, batch_indices, rescale=True)
         results.extend(_post(dataset, result, batch_indices, pre_eval, format_only, format_args))
     return collect_results(results, len(dataset), tmpdir=tmpdir, gpu_collect=gpu_collect)

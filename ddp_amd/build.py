@@ -109,18 +109,84 @@ def build_probe(force=False, verbose=True):
     return _start_probe(force, verbose)()
 
 
+# device-side pre_eval statistics (include/ddp_eval_mi355x.h, ddp_amd/evaluation.py): a library and a stamp of their own, outside
+# source_hash() - no part of the sampler ABI, libddp_mi355x.so does not contain it
+EVAL_CSRC = os.path.join(CSRC, 'eval')
+EVAL_SOURCES = ['ddp_eval.hip']
+EVAL_HEADERS = ['eval_exports.map', os.path.join('..', '..', '..', 'include', 'ddp_eval_mi355x.h')]
+EVAL_LIB_PATH = os.path.join(LIB_DIR, 'libddp_eval.so')
+EVAL_STAMP_PATH = os.path.join(LIB_DIR, '.eval_sha')
+
+
+def eval_hash():
+    """sha256 (16 hex digits) over the evaluation sources, their version script and their C-ABI header"""
+    import hashlib
+    h = hashlib.sha256()
+    for s in sorted(EVAL_SOURCES + EVAL_HEADERS):
+        with open(os.path.join(EVAL_CSRC, s), 'rb') as f:
+            h.update(s.encode() + b'\0' + f.read())
+    return h.hexdigest()[:16]
+
+
+def eval_built_hash():
+    try:
+        with open(EVAL_STAMP_PATH) as f:
+            return f.read().strip()
+    except OSError:
+        return ''
+
+
+def eval_needs_build():
+    return not os.path.exists(EVAL_LIB_PATH) or eval_built_hash() != eval_hash()
+
+
+def eval_cmd(out_path):
+    """the one hipcc line of the evaluation library (no object file in between): the product FLAGS + its version script"""
+    return ([_hipcc()] + FLAGS + ['-x', 'hip', '-shared'] + [os.path.join(EVAL_CSRC, s) for s in EVAL_SOURCES]
+            + ['-Wl,--version-script=' + os.path.join(EVAL_CSRC, 'eval_exports.map'), '-o', out_path])
+
+
+def _start_eval(force, verbose):
+    """start the evaluation library's hipcc (or nothing, when it is current); -> finish(), as _start_probe"""
+    if not force and not eval_needs_build():
+        return lambda: EVAL_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    sha = eval_hash()                    # hashed BEFORE compiling, as in build()
+    if os.path.exists(EVAL_STAMP_PATH):
+        os.remove(EVAL_STAMP_PATH)
+    cmd = eval_cmd(EVAL_LIB_PATH)
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    proc = subprocess.Popen(cmd)
+
+    def finish():
+        if proc.wait() != 0:
+            raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+        with open(EVAL_STAMP_PATH, 'w') as f:
+            f.write(sha + '\n')
+        return EVAL_LIB_PATH
+    return finish
+
+
+def build_eval(force=False, verbose=True):
+    return _start_eval(force, verbose)()
+
+
 def build(force=False, verbose=True):
-    # the probe compiles beside the product's objects; its compile-time checks of the schedule tables make build() fail
-    finish_probe = _start_probe(force, verbose)
+    # the probe and the evaluation library compile beside the product's objects; the probe's compile-time checks of the schedule
+    # tables make build() fail
+    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose)]
     try:
         path = _build_product(force, verbose)
     except BaseException:
-        try:
-            finish_probe()
-        except RuntimeError:
-            pass
+        for finish in finish_side:
+            try:
+                finish()
+            except RuntimeError:
+                pass
         raise
-    finish_probe()
+    for finish in finish_side:
+        finish()
     return path
 
 

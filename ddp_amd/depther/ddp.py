@@ -224,15 +224,19 @@ class DDP(nn.Module, _SamplerMixin):
                           **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
         return self._post([d], [self._flip_of(img_meta)], img.shape[2:] if rescale else d.shape[2:])
 
-    def simple_test(self, img, img_meta, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
-        """encoder_decoder.py:198-209: list (batch) of (1,H,W) float32 arrays.  ``img`` may hold b >= 1 images (independent
+    def simple_test(self, img, img_meta, rescale=True, image_base=0, hints=None, prior=None, t_start=None, on_device=False):
+        """``on_device=True``: return the list of float32 (1,H,W) DEVICE tensors the epilogue wrote instead of host arrays
+        (``ddp_amd.apis.single_gpu_test(device_eval=True)``, ``ddp_amd.evaluation.depth_pre_eval``).
+        encoder_decoder.py:198-209: list (batch) of (1,H,W) float32 arrays.  ``img`` may hold b >= 1 images (independent
         noise per image; the reference's sampler is b = 1 only, depther/ddp.py:232).  ``hints`` (b,Hh,Wh) float32, ``prior`` (b,Hp,Wp)
         float32 with ``t_start``: see ``sample``."""
-        return list(self.inference(img, img_meta, rescale, **self._seed_kw(image_base),
-                                   **({} if hints is None else {'hints': hints}), **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start})).cpu().numpy())
+        out = self.inference(img, img_meta, rescale, **self._seed_kw(image_base),
+                             **({} if hints is None else {'hints': hints}), **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
+        return list(out) if on_device else list(out.cpu().numpy())
 
-    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None):
-        """``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
+    def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None, on_device=False):
+        """``on_device``: see ``simple_test``.
+        ``hints``, ``prior`` and ``t_start`` are not built for test-time augmentation (ValueError).
         encoder_decoder.py:210-229: mean over the augmentations (KITTI / NYU test pipelines: plain + horizontal flip,
         depth/configs/_base_/datasets/kitti.py:30-33).  Every augmentation runs the full sampling loop with its own noise; only the
         LOW-RESOLUTION maps are kept and ONE kernel does clamp -> resize -> flip-undo -> running sum -> / n per output pixel."""
@@ -253,7 +257,8 @@ class DDP(nn.Module, _SamplerMixin):
                 assert all(m['ori_shape'] == ori_shape for m in meta)
             maps.append(self._low_res(img, meta, **self._seed_kw(image_base, a)))      # (seeded noise: the augmentation index is the `call`)
             flips.append(self._flip_of(meta))
-        return list(self._post(maps, flips, imgs[0].shape[2:]).cpu().numpy())
+        out = self._post(maps, flips, imgs[0].shape[2:])
+        return list(out) if on_device else list(out.cpu().numpy())
 
     def forward_test(self, imgs, img_metas, **kwargs):
         """base.py:62-92: the outer lists are the test-time augmentations."""

@@ -500,9 +500,18 @@ class DDP(nn.Module, _SamplerMixin):
 
     AUG_CALL_STRIDE = 1 << 16            # seeded noise: augmentation a owns the call values [a * stride, (a + 1) * stride)
 
+    @staticmethod
+    def _deliver(seg, on_device):
+        """the return value of the test entry points: int64 host arrays as in the reference, or - ``on_device`` - the uint8 device
+        maps the epilogue wrote (no copy, no cast; ``ddp_amd.evaluation.seg_pre_eval`` reduces them where they are)"""
+        if on_device:
+            return list(seg if seg.dtype == torch.uint8 else seg.to(torch.uint8))
+        return list(seg.cpu().numpy().astype('int64'))
+
     def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None,
-                 score_prior=None):
-        """``class_prior`` (b, num_classes): an image-level prior has no frame - every augmentation of image i samples with row i.
+                 score_prior=None, on_device=False):
+        """``on_device``: see ``simple_test``.
+        ``class_prior`` (b, num_classes): an image-level prior has no frame - every augmentation of image i samples with row i.
         ``hints``, ``prior``, ``t_start`` and ``score_prior`` are not built for test-time augmentation (ValueError).
         With ``self.noise_seed`` set, augmentation a samples with ``call`` = a (slide mode: a * AUG_CALL_STRIDE + the window-chunk
         index), so no two augmentations of an image share noise.
@@ -528,7 +537,7 @@ class DDP(nn.Module, _SamplerMixin):
             for a, (img, meta) in enumerate(zip(imgs[1:], img_metas[1:]), 1):
                 prob += self.inference(img, meta, rescale, **self._seed_kw(image_base, a * self.AUG_CALL_STRIDE), **self._cp_kw(class_prior))
             prob /= len(imgs)
-            return list(prob.argmax(dim=1).cpu().numpy().astype('int64'))
+            return self._deliver(prob.argmax(dim=1), on_device)
         ori_shape = tuple(img_metas[0][0]['ori_shape'][:2])
         scores, metas = [], []
         for a, (img, meta) in enumerate(zip(imgs, img_metas)):
@@ -543,7 +552,7 @@ class DDP(nn.Module, _SamplerMixin):
             metas.append(dict(img_size=tuple(img.shape[2:]), crop_size=tuple(meta[0]['img_shape'][:2]),
                               flip=meta[0].get('flip_direction', 'horizontal') if meta[0].get('flip', False) else None))
         seg = seg_aug_postprocess(scores, metas, ori_shape, self.align_corners)
-        return list(seg.cpu().numpy().astype('int64'))
+        return self._deliver(seg, on_device)
 
     @staticmethod
     def _epilogue_args(meta, rescale):
@@ -557,8 +566,10 @@ class DDP(nn.Module, _SamplerMixin):
         return crop, out_size, flip
 
     def simple_test(self, img, img_meta=None, rescale=True, image_base=0, hints=None, prior=None, t_start=None, class_prior=None,
-                    score_prior=None):
-        """``score_prior`` (b, num_classes, H, W) float, in the frame of ``img`` or at the map resolution: see ``ddim_sample``; slide
+                    score_prior=None, on_device=False):
+        """``on_device=True``: return the list of uint8 (H, W) DEVICE tensors the epilogue wrote instead of int64 host arrays - no
+        ``.cpu()``, no cast (``ddp_amd.apis.single_gpu_test(device_eval=True)``, ``ddp_amd.evaluation.seg_pre_eval``).
+        ``score_prior`` (b, num_classes, H, W) float, in the frame of ``img`` or at the map resolution: see ``ddim_sample``; slide
         mode raises ValueError.
         ``class_prior`` (b, num_classes) float: see ``ddim_sample``; in slide mode every window of image i gets row i.
         ``prior`` (b,Hp,Wp) uint8 in the frame of ``img`` and ``t_start``: see ``ddim_sample``; slide mode raises ValueError.
@@ -587,7 +598,7 @@ class DDP(nn.Module, _SamplerMixin):
             # softmax is monotone, so the two agree except where fp32 rounding of exp / the division makes two probabilities EQUAL
             # that came from different scores - the reference then returns the lower class index, this path the class with the
             # larger score.  test_slide_epilogue_golden bounds it: identical wherever the reference's top-2 margin exceeds 1e-5.)
-            return list(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base), **self._cp_kw(class_prior)).cpu().numpy().astype('int64'))
+            return self._deliver(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base), **self._cp_kw(class_prior)), on_device)
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
             out = self.ddim_sample(x, img_meta, **self._seed_kw(image_base), **hk)
@@ -602,16 +613,17 @@ class DDP(nn.Module, _SamplerMixin):
                 for i in range(b)]
         if all(a == args[0] for a in args):
             seg = seg_postprocess(out, img.shape[2:], args[0][0], args[0][1], self.align_corners, args[0][2])
-            return list(seg.cpu().numpy().astype('int64'))
+            return self._deliver(seg, on_device)
         res = []
         for i, (crop, out_size, flip) in enumerate(args):
             seg = seg_postprocess(out[i:i + 1].contiguous(), img.shape[2:], crop, out_size, self.align_corners, flip)
-            res.append(seg[0].cpu().numpy().astype('int64'))
+            res.extend(self._deliver(seg, on_device))
         return res
 
     def forward(self, img, img_metas=None, return_loss=False, rescale=True, image_base=0, hints=None, prior=None, t_start=None,
-                class_prior=None, score_prior=None, **kwargs):
-        """``score_prior``: see ``simple_test`` (``aug_test`` raises ValueError when given one).
+                class_prior=None, score_prior=None, on_device=False, **kwargs):
+        """``on_device``: see ``simple_test``.
+        ``score_prior``: see ``simple_test`` (``aug_test`` raises ValueError when given one).
         ``class_prior``: see ``simple_test`` / ``aug_test``.
         ``hints``, ``prior``, ``t_start``: see ``simple_test`` (``aug_test`` raises ValueError when given any).
         base.py:62-110 ``forward`` / ``forward_test``: ``img`` / ``img_metas`` may be the one-element
@@ -625,14 +637,14 @@ class DDP(nn.Module, _SamplerMixin):
                 return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
                                      **({} if hints is None else {'hints': hints}),
                                      **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
-                                     **self._cp_kw(class_prior), **self._sp_kw(score_prior))
+                                     **self._cp_kw(class_prior), **self._sp_kw(score_prior), **({'on_device': True} if on_device else {}))
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
         return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
                                 **({} if hints is None else {'hints': hints}),
                                 **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
-                                **self._cp_kw(class_prior), **self._sp_kw(score_prior))
+                                **self._cp_kw(class_prior), **self._sp_kw(score_prior), **({'on_device': True} if on_device else {}))
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
