@@ -80,10 +80,12 @@ def seg_gt_loader(dataset, index):
                 reduce_zero_label=dataset.reduce_zero_label)
 
 
-def _post_device(dataset, result, batch_indices, gt_loader):
+def _post_device(dataset, result, batch_indices, gt_loader, confusion=None):
     """``device_eval``: ``result`` holds the device maps of ``model(on_device=True)``; the per-image entries of ``dataset.pre_eval``
     come from ``ddp_amd.evaluation`` - one small device-to-host copy per batch.  uint8 maps are class maps (seg), float32 maps
-    are depth maps; depth needs a caller-given ``gt_loader`` -> dict(gt=, crop=, min_depth=, max_depth=)."""
+    are depth maps; depth needs a caller-given ``gt_loader`` -> dict(gt=, crop=, min_depth=, max_depth=).
+    ``confusion``: a ``ddp_amd.confusion.ConfusionMatrix`` that also takes the batch's class maps and the labels loaded here
+    (uploaded once, for both reductions); it copies nothing back."""
     from . import evaluation as ev
     if not result:
         return []
@@ -96,9 +98,19 @@ def _post_device(dataset, result, batch_indices, gt_loader):
         for j, g in enumerate(gts):          # one call per distinct (num_classes, ignore_index, reduce_zero_label): one, in practice
             groups.setdefault((int(g['num_classes']), int(g['ignore_index']), bool(g['reduce_zero_label'])), []).append(j)
         for (k, ign, rzl), js in groups.items():
-            for j, t in zip(js, ev.seg_pre_eval([result[j] for j in js], [gts[j]['label'] for j in js], k, ign, rzl)):
+            labels = [gts[j]['label'] for j in js]
+            if confusion is not None:
+                if (k, ign, rzl) != (confusion.num_classes, confusion.ignore_index, confusion.reduce_zero_label):
+                    raise ValueError(f'confusion: the matrix was made for (num_classes, ignore_index, reduce_zero_label) = '
+                                     f'{(confusion.num_classes, confusion.ignore_index, confusion.reduce_zero_label)}, the ground truth of '
+                                     f'image {batch_indices[js[0]]} has {(k, ign, rzl)}')
+                labels = [ev._as_u8(l, f'label {batch_indices[j]}').to(result[j].device, non_blocking=True) for j, l in zip(js, labels)]
+                confusion.update([result[j] for j in js], labels)
+            for j, t in zip(js, ev.seg_pre_eval([result[j] for j in js], labels, k, ign, rzl)):
                 out[j] = t
         return out
+    if confusion is not None:
+        raise ValueError('confusion= takes class maps (uint8): the reference has no confusion matrix for depth maps')
     if gt_loader is None:
         raise ValueError('device_eval=True on depth maps needs gt_loader(dataset, index) -> dict(gt=, crop=, min_depth=, max_depth=): '
                          'the reference has no ground-truth accessor for depth datasets')
@@ -114,26 +126,33 @@ def _post_device(dataset, result, batch_indices, gt_loader):
     return out
 
 
-def _check_device_eval(device_eval, pre_eval):
+def _check_device_eval(device_eval, pre_eval, confusion=None):
     if device_eval and not pre_eval:
         raise ValueError('device_eval=True requires pre_eval=True (it replaces dataset.pre_eval; the other paths need the maps on the host)')
+    if confusion is not None and not device_eval:
+        raise ValueError('confusion= requires device_eval=True (the matrix is accumulated from the device maps of on_device=True)')
 
 
-def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device_eval=False, gt_loader=None):
+def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device_eval=False, gt_loader=None,
+                    confusion=None):
     """test.py:34-137 without the drawing / deprecated ``efficient_test`` branches.  Returns the list of per-image
     results (or pre-eval tuples / formatted file names) in dataset order.
     ``device_eval=True`` (with ``pre_eval=True``): the model is called with ``on_device=True`` and the per-image pre-eval entries
     are reduced on the device (``ddp_amd.evaluation``); ``gt_loader(dataset, index)`` supplies the ground truth (default for
-    seg datasets: ``seg_gt_loader``).  The entries equal ``dataset.pre_eval``'s, so ``dataset.evaluate`` is untouched."""
+    seg datasets: ``seg_gt_loader``).  The entries equal ``dataset.pre_eval``'s, so ``dataset.evaluate`` is untouched.
+    ``confusion`` (with ``device_eval=True``): a ``ddp_amd.confusion.ConfusionMatrix``; every batch's device maps and the labels
+    ``gt_loader`` returned also go through ``confusion.update`` - no second load, nothing copied back; read ``confusion.result()``
+    afterwards (``tools/confusion_matrix.py``'s matrix without the pickled predictions).  The return value is unchanged."""
     assert not (pre_eval and format_only), '``pre_eval`` and ``format_only`` are mutually exclusive'
-    _check_device_eval(device_eval, pre_eval)
+    _check_device_eval(device_eval, pre_eval, confusion)
     model.eval()
     device = _model_device(model)
     dataset = data_loader.dataset
     results = []
     for batch_indices, data in zip(data_loader.batch_sampler, data_loader):
         if device_eval:
-            results.extend(_post_device(dataset, _run_batch(model, data, device, batch_indices, on_device=True), batch_indices, gt_loader))
+            results.extend(_post_device(dataset, _run_batch(model, data, device, batch_indices, on_device=True), batch_indices, gt_loader,
+                                        confusion))
             continue
         result = _run_batch(model, data, device, batch_indices)
         results.extend(_post(dataset, result, batch_indices, pre_eval, format_only, format_args))
@@ -143,7 +162,8 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 def multi_gpu_test(model, data_loader, tmpdir=None, gpu_collect=False, pre_eval=False, format_only=False,
                    format_args=None, device_eval=False, gt_loader=None):
     """test.py:140-229: every rank walks its DistributedSampler shard, then the per-rank lists are merged.
-    ``device_eval`` / ``gt_loader``: see ``single_gpu_test``."""
+    ``device_eval`` / ``gt_loader``: see ``single_gpu_test``.  There is no ``confusion=`` here: a ``DistributedSampler`` repeats
+    samples to pad its shards, ``collect_results`` cuts their entries off again, and an accumulator cannot un-count them."""
     assert not (pre_eval and format_only), '``pre_eval`` and ``format_only`` are mutually exclusive'
     _check_device_eval(device_eval, pre_eval)
     model.eval()

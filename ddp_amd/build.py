@@ -172,10 +172,73 @@ def build_eval(force=False, verbose=True):
     return _start_eval(force, verbose)()
 
 
+# device-side confusion matrix (include/ddp_cm_mi355x.h, ddp_amd/confusion.py): again a library and a stamp of their own, outside
+# source_hash() and eval_hash() - neither of the other two libraries contains it
+CM_CSRC = os.path.join(CSRC, 'cm')
+CM_SOURCES = ['ddp_cm.hip']
+CM_HEADERS = ['cm_exports.map', os.path.join('..', '..', '..', 'include', 'ddp_cm_mi355x.h')]
+CM_LIB_PATH = os.path.join(LIB_DIR, 'libddp_cm.so')
+CM_STAMP_PATH = os.path.join(LIB_DIR, '.cm_sha')
+
+
+def cm_hash():
+    """sha256 (16 hex digits) over the confusion-matrix source, its version script and its C-ABI header"""
+    import hashlib
+    h = hashlib.sha256()
+    for s in sorted(CM_SOURCES + CM_HEADERS):
+        with open(os.path.join(CM_CSRC, s), 'rb') as f:
+            h.update(s.encode() + b'\0' + f.read())
+    return h.hexdigest()[:16]
+
+
+def cm_built_hash():
+    try:
+        with open(CM_STAMP_PATH) as f:
+            return f.read().strip()
+    except OSError:
+        return ''
+
+
+def cm_needs_build():
+    return not os.path.exists(CM_LIB_PATH) or cm_built_hash() != cm_hash()
+
+
+def cm_cmd(out_path):
+    """the one hipcc line of the confusion-matrix library (no object file in between): the product FLAGS + its version script"""
+    return ([_hipcc()] + FLAGS + ['-x', 'hip', '-shared'] + [os.path.join(CM_CSRC, s) for s in CM_SOURCES]
+            + ['-Wl,--version-script=' + os.path.join(CM_CSRC, 'cm_exports.map'), '-o', out_path])
+
+
+def _start_cm(force, verbose):
+    """start the confusion-matrix library's hipcc (or nothing, when it is current); -> finish(), as _start_probe"""
+    if not force and not cm_needs_build():
+        return lambda: CM_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    sha = cm_hash()                      # hashed BEFORE compiling, as in build()
+    if os.path.exists(CM_STAMP_PATH):
+        os.remove(CM_STAMP_PATH)
+    cmd = cm_cmd(CM_LIB_PATH)
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    proc = subprocess.Popen(cmd)
+
+    def finish():
+        if proc.wait() != 0:
+            raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+        with open(CM_STAMP_PATH, 'w') as f:
+            f.write(sha + '\n')
+        return CM_LIB_PATH
+    return finish
+
+
+def build_cm(force=False, verbose=True):
+    return _start_cm(force, verbose)()
+
+
 def build(force=False, verbose=True):
-    # the probe and the evaluation library compile beside the product's objects; the probe's compile-time checks of the schedule
-    # tables make build() fail
-    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose)]
+    # the probe, the evaluation library and the confusion-matrix library compile beside the product's objects; the probe's
+    # compile-time checks of the schedule tables make build() fail
+    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose), _start_cm(force, verbose)]
     try:
         path = _build_product(force, verbose)
     except BaseException:
