@@ -235,10 +235,73 @@ def build_cm(force=False, verbose=True):
     return _start_cm(force, verbose)()
 
 
+# device-side LSS lift and pool (include/ddp_lss_mi355x.h, ddp_amd/lss.py): a fourth library with a stamp of its own, outside the
+# other three hashes - none of the other libraries contains it
+LSS_CSRC = os.path.join(CSRC, 'lss')
+LSS_SOURCES = ['ddp_lss.hip']
+LSS_HEADERS = ['lss_exports.map', os.path.join('..', '..', '..', 'include', 'ddp_lss_mi355x.h')]
+LSS_LIB_PATH = os.path.join(LIB_DIR, 'libddp_lss.so')
+LSS_STAMP_PATH = os.path.join(LIB_DIR, '.lss_sha')
+
+
+def lss_hash():
+    """sha256 (16 hex digits) over the LSS source, its version script and its C-ABI header"""
+    import hashlib
+    h = hashlib.sha256()
+    for s in sorted(LSS_SOURCES + LSS_HEADERS):
+        with open(os.path.join(LSS_CSRC, s), 'rb') as f:
+            h.update(s.encode() + b'\0' + f.read())
+    return h.hexdigest()[:16]
+
+
+def lss_built_hash():
+    try:
+        with open(LSS_STAMP_PATH) as f:
+            return f.read().strip()
+    except OSError:
+        return ''
+
+
+def lss_needs_build():
+    return not os.path.exists(LSS_LIB_PATH) or lss_built_hash() != lss_hash()
+
+
+def lss_cmd(out_path):
+    """the one hipcc line of the LSS library (no object file in between): the product FLAGS + its version script"""
+    return ([_hipcc()] + FLAGS + ['-x', 'hip', '-shared'] + [os.path.join(LSS_CSRC, s) for s in LSS_SOURCES]
+            + ['-Wl,--version-script=' + os.path.join(LSS_CSRC, 'lss_exports.map'), '-o', out_path])
+
+
+def _start_lss(force, verbose):
+    """start the LSS library's hipcc (or nothing, when it is current); -> finish(), as _start_probe"""
+    if not force and not lss_needs_build():
+        return lambda: LSS_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    sha = lss_hash()                     # hashed BEFORE compiling, as in build()
+    if os.path.exists(LSS_STAMP_PATH):
+        os.remove(LSS_STAMP_PATH)
+    cmd = lss_cmd(LSS_LIB_PATH)
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    proc = subprocess.Popen(cmd)
+
+    def finish():
+        if proc.wait() != 0:
+            raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+        with open(LSS_STAMP_PATH, 'w') as f:
+            f.write(sha + '\n')
+        return LSS_LIB_PATH
+    return finish
+
+
+def build_lss(force=False, verbose=True):
+    return _start_lss(force, verbose)()
+
+
 def build(force=False, verbose=True):
-    # the probe, the evaluation library and the confusion-matrix library compile beside the product's objects; the probe's
+    # the probe, the evaluation, confusion-matrix and LSS libraries compile beside the product's objects; the probe's
     # compile-time checks of the schedule tables make build() fail
-    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose), _start_cm(force, verbose)]
+    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose), _start_cm(force, verbose), _start_lss(force, verbose)]
     try:
         path = _build_product(force, verbose)
     except BaseException:

@@ -46,6 +46,7 @@ class Registry:
 
 MODELS = Registry('models')
 BACKBONES = NECKS = HEADS = LOSSES = SEGMENTORS = DEPTHER = FUSIONMODELS = MODELS
+VTRANSFORMS = MODELS
 
 
 def _foreign_builder(kind):
@@ -200,3 +201,18 @@ def register_into_mmdet3d():
     MF.register_module(name='DDP', force=True, module=BevDDP)
     MH.register_module(name='DeformableHeadWithTime', force=True, module=BEVDeformableHeadWithTime)
     return ['mmdet3d.FUSIONMODELS', 'mmdet3d.HEADS']
+
+
+def register_vtransform_into_mmdet3d():
+    """Register the device ``LSSTransform`` under the REFERENCE's name in an importable ``mmdet3d``
+    (bev/mmdet3d/models/vtransforms/lss.py:13 ``@VTRANSFORMS.register_module() class LSSTransform``), force=True, so that the
+    ``vtransform: {type: LSSTransform, ...}`` key of the camera-only bev config resolves to the lift and pool of libddp_lss.so.  A
+    call of its own, so that ``register_into_mmdet3d`` keeps touching what it touched.  Returns the list of registries touched
+    (empty when mmdet3d, or its VTRANSFORMS registry, is not importable)."""
+    try:
+        from mmdet3d.models.builder import VTRANSFORMS as MV
+    except ImportError:
+        return []
+    from .bev.lss import LSSTransform
+    MV.register_module(name='LSSTransform', force=True, module=LSSTransform)
+    return ['mmdet3d.VTRANSFORMS']
