@@ -298,10 +298,74 @@ def build_lss(force=False, verbose=True):
     return _start_lss(force, verbose)()
 
 
+# device-side front of DepthLSSTransform (include/ddp_dlss_mi355x.h, ddp_amd/dlss.py): lidar projection, depth scatter and the
+# dtransform stem; a fifth library with a stamp of its own, outside the other four hashes - none of the other libraries contains it
+DLSS_CSRC = os.path.join(CSRC, 'dlss')
+DLSS_SOURCES = ['ddp_dlss.hip']
+DLSS_HEADERS = ['dlss_exports.map', os.path.join('..', '..', '..', 'include', 'ddp_dlss_mi355x.h')]
+DLSS_LIB_PATH = os.path.join(LIB_DIR, 'libddp_dlss.so')
+DLSS_STAMP_PATH = os.path.join(LIB_DIR, '.dlss_sha')
+
+
+def dlss_hash():
+    """sha256 (16 hex digits) over the depth-LSS source, its version script and its C-ABI header"""
+    import hashlib
+    h = hashlib.sha256()
+    for s in sorted(DLSS_SOURCES + DLSS_HEADERS):
+        with open(os.path.join(DLSS_CSRC, s), 'rb') as f:
+            h.update(s.encode() + b'\0' + f.read())
+    return h.hexdigest()[:16]
+
+
+def dlss_built_hash():
+    try:
+        with open(DLSS_STAMP_PATH) as f:
+            return f.read().strip()
+    except OSError:
+        return ''
+
+
+def dlss_needs_build():
+    return not os.path.exists(DLSS_LIB_PATH) or dlss_built_hash() != dlss_hash()
+
+
+def dlss_cmd(out_path):
+    """the one hipcc line of the depth-LSS library (no object file in between): the product FLAGS + its version script"""
+    return ([_hipcc()] + FLAGS + ['-x', 'hip', '-shared'] + [os.path.join(DLSS_CSRC, s) for s in DLSS_SOURCES]
+            + ['-Wl,--version-script=' + os.path.join(DLSS_CSRC, 'dlss_exports.map'), '-o', out_path])
+
+
+def _start_dlss(force, verbose):
+    """start the depth-LSS library's hipcc (or nothing, when it is current); -> finish(), as _start_probe"""
+    if not force and not dlss_needs_build():
+        return lambda: DLSS_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    sha = dlss_hash()                    # hashed BEFORE compiling, as in build()
+    if os.path.exists(DLSS_STAMP_PATH):
+        os.remove(DLSS_STAMP_PATH)
+    cmd = dlss_cmd(DLSS_LIB_PATH)
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    proc = subprocess.Popen(cmd)
+
+    def finish():
+        if proc.wait() != 0:
+            raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+        with open(DLSS_STAMP_PATH, 'w') as f:
+            f.write(sha + '\n')
+        return DLSS_LIB_PATH
+    return finish
+
+
+def build_dlss(force=False, verbose=True):
+    return _start_dlss(force, verbose)()
+
+
 def build(force=False, verbose=True):
-    # the probe, the evaluation, confusion-matrix and LSS libraries compile beside the product's objects; the probe's
+    # the probe, the evaluation, confusion-matrix, LSS and depth-LSS libraries compile beside the product's objects; the probe's
     # compile-time checks of the schedule tables make build() fail
-    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose), _start_cm(force, verbose), _start_lss(force, verbose)]
+    finish_side = [_start_probe(force, verbose), _start_eval(force, verbose), _start_cm(force, verbose), _start_lss(force, verbose),
+                   _start_dlss(force, verbose)]
     try:
         path = _build_product(force, verbose)
     except BaseException:

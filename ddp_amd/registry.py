@@ -216,3 +216,18 @@ def register_vtransform_into_mmdet3d():
     from .bev.lss import LSSTransform
     MV.register_module(name='LSSTransform', force=True, module=LSSTransform)
     return ['mmdet3d.VTRANSFORMS']
+
+
+def register_depth_vtransform_into_mmdet3d():
+    """Register the device ``DepthLSSTransform`` under the REFERENCE's name in an importable ``mmdet3d``
+    (bev/mmdet3d/models/vtransforms/depth_lss.py:14 ``@VTRANSFORMS.register_module() class DepthLSSTransform``), force=True, so that
+    the ``vtransform: {type: DepthLSSTransform, ...}`` key of a camera + lidar bev config resolves to libddp_dlss.so and
+    libddp_lss.so.  A call of its own: ``register_vtransform_into_mmdet3d`` keeps touching only ``LSSTransform``.  Returns the list of
+    registries touched (empty when mmdet3d, or its VTRANSFORMS registry, is not importable)."""
+    try:
+        from mmdet3d.models.builder import VTRANSFORMS as MV
+    except ImportError:
+        return []
+    from .bev.depth_lss import DepthLSSTransform
+    MV.register_module(name='DepthLSSTransform', force=True, module=DepthLSSTransform)
+    return ['mmdet3d.VTRANSFORMS']
