@@ -1,12 +1,11 @@
 """ctypes binding of libddp_lss.so (include/ddp_lss_mi355x.h): the LSSTransform lift and pool on the device.
 
-Like ``_lib``, ``_eval_lib`` and ``_cm_lib``: NO fallback.  A missing or stale library raises; build it with
-``python -m ddp_amd.build``.
+NO fallback: ``_sidelib`` raises on a missing or stale library; build it with ``python -m ddp_amd.build``.
 """
 import ctypes as C
-import os
 
 from . import build as _build
+from ._sidelib import Binding, SideLibError
 
 ABI_VERSION = 1
 MAX_CHANNELS = 256
@@ -24,54 +23,21 @@ class Cfg(C.Structure):
                 ('nx', C.c_int32 * 3)]
 
 
-EXPORTS = ['ddp_lss_last_error', 'ddp_lss_abi_version', 'ddp_lss_workspace', 'ddp_lss_plan', 'ddp_lss_plan_from_ranks',
-           'ddp_lss_ranks', 'ddp_lss_pool']
-
-_libs = {}
-
-
-class DdpLssError(RuntimeError):
-    def __init__(self, msg, code=None):
-        super().__init__(msg)
-        self.code = code
-
-
-def load(path=None):
-    """Load (once per path) and return libddp_lss.so; raises when it is missing or was built from other sources."""
-    path = os.path.abspath(path or _build.LSS_LIB_PATH)
-    if path in _libs:
-        return _libs[path]
-    if not os.path.exists(path):
-        raise DdpLssError(f'{path} not found: build it with `python -m ddp_amd.build` (hipcc --offload-arch=gfx950); '
-                          'ddp_amd.lss has no non-HIP fallback')
-    if path == os.path.abspath(_build.LSS_LIB_PATH) and _build.lss_built_hash() != _build.lss_hash():
-        raise DdpLssError(f'{path} is stale: built from sources {_build.lss_built_hash() or "<no stamp>"}, the tree holds '
-                          f'{_build.lss_hash()}; rebuild with `python -m ddp_amd.build`')
-    lib = C.CDLL(path)
-    cfg = C.POINTER(Cfg)
-    lib.ddp_lss_last_error.restype = C.c_char_p
-    lib.ddp_lss_last_error.argtypes = []
-    lib.ddp_lss_abi_version.restype = C.c_int
-    lib.ddp_lss_abi_version.argtypes = []
-    lib.ddp_lss_workspace.restype = C.c_int
-    lib.ddp_lss_workspace.argtypes = [cfg, C.POINTER(C.c_size_t)]
-    lib.ddp_lss_plan.restype = C.c_int
-    lib.ddp_lss_plan.argtypes = [cfg, _fp, _fp, _fp, _fp]
-    lib.ddp_lss_plan_from_ranks.restype = C.c_int
-    lib.ddp_lss_plan_from_ranks.argtypes = [cfg, _fp, _fp, _fp]
-    lib.ddp_lss_ranks.restype = C.c_int
-    lib.ddp_lss_ranks.argtypes = [cfg, _fp, C.POINTER(_fp)]
-    lib.ddp_lss_pool.restype = C.c_int
-    lib.ddp_lss_pool.argtypes = [cfg, _fp, _fp, _fp, _fp]
-    if lib.ddp_lss_abi_version() != ABI_VERSION:
-        raise DdpLssError(f'ABI mismatch: library {lib.ddp_lss_abi_version()} vs binding {ABI_VERSION}')
-    _libs[path] = lib
-    return lib
+_cfg = C.POINTER(Cfg)
+ARGTYPES = {
+    'ddp_lss_workspace': [_cfg, C.POINTER(C.c_size_t)],
+    'ddp_lss_plan': [_cfg, _fp, _fp, _fp, _fp],
+    'ddp_lss_plan_from_ranks': [_cfg, _fp, _fp, _fp],
+    'ddp_lss_ranks': [_cfg, _fp, C.POINTER(_fp)],
+    'ddp_lss_pool': [_cfg, _fp, _fp, _fp, _fp],
+}
+EXPORTS = ['ddp_lss_last_error', 'ddp_lss_abi_version', *ARGTYPES]
 
 
-def check(rc, lib=None):
-    if rc != 0:
-        msg = (lib or load()).ddp_lss_last_error().decode()
-        if rc == E_BADCFG:
-            raise ValueError(f'libddp_lss refused the configuration: {msg}')
-        raise DdpLssError(f'libddp_lss error {rc}: {msg}', rc)
+class DdpLssError(SideLibError):
+    pass
+
+
+# a refused configuration is the caller's ValueError, anything else a DdpLssError
+_binding = Binding(_build.SIDE['lss'], ABI_VERSION, ARGTYPES, 'ddp_amd.lss', DdpLssError, badcfg=E_BADCFG)
+load, check = _binding.load, _binding.check

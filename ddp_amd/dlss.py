@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from . import _dlss_lib as M
+from .evaluation import _stream
 
 
 def pack_lidar(lidar2image, img_aug_matrix, lidar_aug_matrix):
@@ -28,10 +29,6 @@ def pack_lidar(lidar2image, img_aug_matrix, lidar_aug_matrix):
 def stem_size(image_size):
     """the output size of the two stem stages: 1 x 1, then 5 x 5 stride 4 padding 2"""
     return (int(image_size[0]) - 1) // 4 + 1, (int(image_size[1]) - 1) // 4 + 1
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _dev(t, what, dtype=torch.float32, shape=None):

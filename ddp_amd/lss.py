@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lss_lib as M
+from .evaluation import _stream
 
 
 def grid_of(xbound, ybound, zbound):
@@ -38,10 +39,6 @@ def pack_cameras(camera2lidar_rots, camera2lidar_trans, intrins, post_rots, post
                      camera2lidar_trans.reshape(B, N, 3)], dim=2).float().contiguous()
     extra = torch.cat([extra_rots.reshape(B, 9), extra_trans.reshape(B, 3)], dim=1).float().contiguous()
     return cam, extra
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _dev_f32(t, what, shape=None):

@@ -64,7 +64,7 @@ def main():
     dev = torch.device('cuda:0')
     ps = bench.PowerSampler()
     ps.start()
-    lines = [dict(record='header', cm_hash=build.cm_hash(), eval_hash=build.eval_hash(), source_hash=build.source_hash(),
+    lines = [dict(record='header', cm_hash=build.SIDE['cm'].hash(), eval_hash=build.SIDE['eval'].hash(), source_hash=build.source_hash(),
                   torch=torch.__version__, device=torch.cuda.get_device_name(0), iters=args.iters, host_iters=args.host_iters,
                   host_threads=torch.get_num_threads(), gate=GATE, power_source=ps.source)]
     failed = []

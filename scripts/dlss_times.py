@@ -181,7 +181,7 @@ def main():
             my_on_ref = dtransform(image.flatten(0, 1).clone())
         torch.cuda.synchronize()
         assert all(torch.equal(p, q) for p, q in zip(points, before))
-        rec = dict(record='dlss', dlss_hash=build.dlss_hash(), torch=torch.__version__, device=torch.cuda.get_device_name(0), batch=B, cams=6,
+        rec = dict(record='dlss', dlss_hash=build.SIDE['dlss'].hash(), torch=torch.__version__, device=torch.cuda.get_device_name(0), batch=B, cams=6,
                    image=list(IMAGE), points=[int(p.shape[0]) for p in points], pmax=pmax, on_image_pairs=on, lit_pixels=lit,
                    lit_share=round(lit / image.numel(), 5), pixels_lit_differently_from_torch=int(((image != 0) != (ref_image != 0)).sum()),
                    pixels_with_another_depth_than_torch=int((image != ref_image).sum()), contested_pairs=on - lit,

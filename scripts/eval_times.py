@@ -142,7 +142,7 @@ def main():
     dev = torch.device('cuda:0')
     ps = bench.PowerSampler()
     ps.start()
-    lines = [dict(record='header', eval_hash=build.eval_hash(), source_hash=build.source_hash(), torch=torch.__version__,
+    lines = [dict(record='header', eval_hash=build.SIDE['eval'].hash(), source_hash=build.source_hash(), torch=torch.__version__,
                   device=torch.cuda.get_device_name(0), iters=args.iters, host_iters=args.host_iters, host_threads=torch.get_num_threads(),
                   power_source=ps.source)]
 

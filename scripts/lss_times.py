@@ -136,7 +136,7 @@ def main():
         torch.cuda.synchronize()
         err = float((got - ref).abs().max() / ref.abs().max())
         P, K, X, C, D = ranks.numel(), B * 65536, B * 6 * 32 * 88, pool.C, pool.D
-        rec = dict(record='lss', lss_hash=build.lss_hash(), torch=torch.__version__, device=torch.cuda.get_device_name(0), batch=B, cams=6,
+        rec = dict(record='lss', lss_hash=build.SIDE['lss'].hash(), torch=torch.__version__, device=torch.cuda.get_device_name(0), batch=B, cams=6,
                    depth_bins=D, feature=[32, 88], channels=C, cells=[256, 256, 1], points=P, kept=kept, kept_torch_route=kept_ref,
                    nonempty_cells=int((lists > 0).sum()), mean_list=round(kept / max(int((lists > 0).sum()), 1), 2), longest_list=int(lists.max()),
                    max_rel_vs_torch_route=err, iters=args.iters)

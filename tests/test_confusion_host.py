@@ -4,13 +4,10 @@ and the tally identity hold; the matrix contains the pre_eval counters; the libr
 exports, the other two untouched); every refusal happens before any launch; the host layer and the keyword surface.  No GPU
 compute is invoked."""
 import ctypes as C
-import importlib.util
 import inspect
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,7 +17,7 @@ import confusion_cases as CC
 import device_eval_cases as V
 from ddp_amd import _cm_lib as M
 from ddp_amd import _eval_lib as E
-from ddp_amd import _lib, apis, build
+from ddp_amd import apis, build
 from ddp_amd import confusion as cf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,70 +101,29 @@ def test_matrix_contains_the_pre_eval_counters():
     assert e[1].sum() - m.sum() == t[2] > 0 and np.array_equal(np.diag(m), e[0, :19])
 
 
-# ---- a library of its own ------------------------------------------------------------------------------------------------------------
-def _dyn_syms(path):
-    out = subprocess.run(['nm', '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if ' T ' in l)
-
-
-def test_library_builds_and_exports_exactly_the_header():
-    path = build.build_cm(verbose=False)
-    assert os.path.exists(path) and not build.cm_needs_build() and build.cm_built_hash() == build.cm_hash()
+# ---- the library's own (what every side library shares: tests/test_build_host.py) ------------------------------------------------------
+def test_binding_matches_the_header():
+    build.SIDE['cm'].start(verbose=False)()
     header = open(os.path.join(ROOT, 'include', 'ddp_cm_mi355x.h')).read()
-    declared = sorted(set(re.findall(r'\b(ddp_cm_\w+)\s*\(', re.sub(r'/\*.*?\*/', '', header, flags=re.S))))
     # four functions and the item struct: the five names the header declares
-    assert _dyn_syms(path) == declared == sorted(M.EXPORTS) and len(declared) == 4
-    assert re.findall(r'typedef struct (\w+)', header) == ['ddp_cm_item'] and len(declared) + 1 == 5
-    script = open(os.path.join(build.CM_CSRC, 'cm_exports.map')).read()
-    assert sorted(re.findall(r'\b(ddp_cm_\w+);', script)) == declared and 'local:\n    *;' in script
-    lib = M.load()
-    assert lib.ddp_cm_abi_version() == 1 == M.ABI_VERSION and '#define DDP_CM_ABI_VERSION 1' in header
+    assert re.findall(r'typedef struct (\w+)', header) == ['ddp_cm_item'] and len(M.EXPORTS) + 1 == 5
     assert '#define DDP_CM_MAX_ITEMS 64' in header and M.MAX_ITEMS == 64 and '#define DDP_CM_TALLY 4' in header and M.TALLY == 4
     assert C.sizeof(M.Item) == 24 == C.sizeof(E.SegItem)
     assert (M.E_BADCFG, M.E_ALIGN, M.E_LAUNCH, M.E_NULL) == (E.E_BADCFG, E.E_ALIGN, E.E_LAUNCH, E.E_NULL)
-    # the other two libraries: untouched
-    build.build(verbose=False)
-    syms = [s for s in _dyn_syms(_lib.lib_path()) if 'ddp_' in s]
-    assert syms == sorted(_lib.EXPORTS) and len(syms) == 36 and not any(s.startswith('ddp_cm') for s in syms)
-    esyms = _dyn_syms(build.EVAL_LIB_PATH)
-    assert esyms == sorted(E.EXPORTS) and len(esyms) == 6 and not any(s.startswith('ddp_cm') for s in esyms)
-    assert _lib.ABI_VERSION == 7 and E.ABI_VERSION == 1
-
-
-def test_hash_and_stamp_are_its_own(tmp_path):
-    assert build.CM_SOURCES == ['ddp_cm.hip']
-    assert build.CM_STAMP_PATH.endswith(os.path.join('lib', '.cm_sha')) and build.CM_LIB_PATH.endswith(os.path.join('lib', 'libddp_cm.so'))
-    assert len({build.CM_STAMP_PATH, build.EVAL_STAMP_PATH, build.STAMP_PATH, build.PROBE_STAMP_PATH}) == 4
-    assert build.cm_cmd('x.so')[1:1 + len(build.FLAGS)] == build.FLAGS and build.cm_cmd('x.so')[-1] == 'x.so'
-    assert any(a.startswith('-Wl,--version-script=') and a.endswith('cm_exports.map') for a in build.cm_cmd('x.so'))
-    assert sum(a.endswith('.hip') for a in build.cm_cmd('x.so')) == 1 and '-c' not in build.cm_cmd('x.so')
-    sets = [{os.path.normpath(os.path.join(base, s)) for s in names}
-            for base, names in ((build.CSRC, build.SOURCES + build.HEADERS), (build.EVAL_CSRC, build.EVAL_SOURCES + build.EVAL_HEADERS),
-                                (build.CM_CSRC, build.CM_SOURCES + build.CM_HEADERS))]
-    assert not sets[0] & sets[2] and not sets[1] & sets[2] and os.path.normpath(os.path.join(ROOT, 'include', 'ddp_cm_mi355x.h')) in sets[2]
-    assert len({build.cm_hash(), build.eval_hash(), build.source_hash()}) == 3
-    # an edit of ddp_cm.hip in a copy of the tree changes cm_hash() and nothing else
-    for d in ('ddp_amd', 'include'):
-        shutil.copytree(os.path.join(ROOT, d), tmp_path / d, ignore=shutil.ignore_patterns('lib', 'lib_*', '__pycache__'))
-    spec = importlib.util.spec_from_file_location('_build_of_the_copy', str(tmp_path / 'ddp_amd' / 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)                           # build.py finds its sources beside itself
-    assert b.CM_CSRC.startswith(str(tmp_path))
-    before = [b.source_hash(), b.eval_hash(), b.cm_hash()]
-    assert before == [build.source_hash(), build.eval_hash(), build.cm_hash()]
-    with open(tmp_path / 'ddp_amd' / 'csrc' / 'cm' / 'ddp_cm.hip', 'a') as f:
-        f.write('// edited\n')
-    after = [b.source_hash(), b.eval_hash(), b.cm_hash()]
-    assert after[:2] == before[:2] and after[2] != before[2] and b.cm_needs_build()
 
 
 def test_stale_or_missing_library_raises(tmp_path, monkeypatch):
     with pytest.raises(M.DdpCmError, match='not found'):
         M.load(str(tmp_path / 'libddp_cm.so'))
-    monkeypatch.setattr(build, 'cm_built_hash', lambda: 'feedfeedfeedfeed')
-    monkeypatch.setattr(M, '_libs', {})
-    with pytest.raises(M.DdpCmError, match='stale'):
+    monkeypatch.setattr(M._binding, 'libs', {})
+    with monkeypatch.context() as m:
+        m.setattr(build.SIDE['cm'], 'built_hash', lambda: 'feedfeedfeedfeed')
+        with pytest.raises(M.DdpCmError, match='is stale'):
+            M.load()
+    monkeypatch.setattr(M._binding, 'abi_version', M.ABI_VERSION + 1)
+    with pytest.raises(M.DdpCmError, match='ABI mismatch: library 1 vs binding 2') as e:
         M.load()
+    assert e.value.code is None and isinstance(e.value, RuntimeError) and not M._binding.libs
 
 
 FAKE = 0x1000     # a non-NULL "device pointer": every call below is refused before anything is enqueued

@@ -3,13 +3,10 @@ from the reference's own functions equal the numpy restatements of tests/device_
 evaluation library is a library of its own (its hash, its exports, the product library untouched); every refusal happens before
 any launch; the crop rectangles, the finalisation rules and the keyword surface.  No GPU compute is invoked."""
 import ctypes as C
-import hashlib
 import inspect
 import json
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,7 +14,7 @@ import torch
 
 import device_eval_cases as V
 from ddp_amd import _eval_lib as E
-from ddp_amd import _lib, apis, build
+from ddp_amd import apis, build
 from ddp_amd import evaluation as ev
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -208,55 +205,26 @@ def test_bev_case_conditions():
                 assert (p == thr).any()
 
 
-# ---- a library of its own ------------------------------------------------------------------------------------------------------------
-def _sha(names, base):
-    h = hashlib.sha256()
-    for s in sorted(names):
-        with open(os.path.join(base, s), 'rb') as f:
-            h.update(s.encode() + b'\0' + f.read())
-    return h.hexdigest()[:16]
-
-
-def test_hashes_are_separate():
-    assert build.source_hash() == _sha(build.SOURCES + build.HEADERS, build.CSRC)
-    assert build.eval_hash() == _sha(build.EVAL_SOURCES + build.EVAL_HEADERS, build.EVAL_CSRC) != build.source_hash()
-    assert build.EVAL_SOURCES == ['ddp_eval.hip']
-    product = {os.path.normpath(os.path.join(build.CSRC, s)) for s in build.SOURCES + build.HEADERS}
-    mine = {os.path.normpath(os.path.join(build.EVAL_CSRC, s)) for s in build.EVAL_SOURCES + build.EVAL_HEADERS}
-    assert not product & mine and os.path.normpath(os.path.join(ROOT, 'include', 'ddp_eval_mi355x.h')) in mine
-    assert build.EVAL_STAMP_PATH.endswith(os.path.join('lib', '.eval_sha')) and build.EVAL_LIB_PATH.endswith(os.path.join('lib', 'libddp_eval.so'))
-    assert build.eval_cmd('x.so')[1:1 + len(build.FLAGS)] == build.FLAGS
-    assert any(a.startswith('-Wl,--version-script=') and a.endswith('eval_exports.map') for a in build.eval_cmd('x.so'))
-
-
-def _dyn_syms(path):
-    out = subprocess.run(['nm', '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if ' T ' in l)
-
-
-def test_library_builds_and_exports_exactly_the_header():
-    path = build.build_eval(verbose=False)
-    assert os.path.exists(path) and not build.eval_needs_build() and build.eval_built_hash() == build.eval_hash()
+# ---- the library's own (what every side library shares: tests/test_build_host.py) ------------------------------------------------------
+def test_binding_matches_the_header():
+    build.SIDE['eval'].start(verbose=False)()
     header = open(os.path.join(ROOT, 'include', 'ddp_eval_mi355x.h')).read()
-    declared = sorted(set(re.findall(r'\b(ddp_eval_\w+)\s*\(', re.sub(r'/\*.*?\*/', '', header, flags=re.S))))
-    assert _dyn_syms(path) == declared == sorted(E.EXPORTS) and len(declared) == 6
-    lib = E.load()
-    assert lib.ddp_eval_abi_version() == 1 == E.ABI_VERSION and '#define DDP_EVAL_ABI_VERSION 1' in header
     assert '#define DDP_EVAL_MAX_ITEMS 64' in header and E.MAX_ITEMS == 64
     assert (C.sizeof(E.SegItem), C.sizeof(E.DepthItem), C.sizeof(E.BevItem)) == (24, 40, 16)
-    # the product library: untouched
-    syms = [s for s in _dyn_syms(_lib.lib_path()) if 'ddp_' in s]
-    assert syms == sorted(_lib.EXPORTS) and len(syms) == 36 and not any(s.startswith('ddp_eval') for s in syms)
-    assert _lib.ABI_VERSION == 7
 
 
 def test_stale_or_missing_library_raises(tmp_path, monkeypatch):
     with pytest.raises(E.DdpEvalError, match='not found'):
         E.load(str(tmp_path / 'libddp_eval.so'))
-    monkeypatch.setattr(build, 'eval_built_hash', lambda: 'feedfeedfeedfeed')
-    monkeypatch.setattr(E, '_libs', {})
-    with pytest.raises(E.DdpEvalError, match='stale'):
+    monkeypatch.setattr(E._binding, 'libs', {})
+    with monkeypatch.context() as m:
+        m.setattr(build.SIDE['eval'], 'built_hash', lambda: 'feedfeedfeedfeed')
+        with pytest.raises(E.DdpEvalError, match='is stale'):
+            E.load()
+    monkeypatch.setattr(E._binding, 'abi_version', E.ABI_VERSION + 1)
+    with pytest.raises(E.DdpEvalError, match='ABI mismatch: library 1 vs binding 2') as e:
         E.load()
+    assert e.value.code is None and isinstance(e.value, RuntimeError) and not E._binding.libs
 
 
 FAKE = 0x1000     # a non-NULL "device pointer": every call below is refused before anything is enqueued

@@ -4,7 +4,6 @@ its name promises; the reference's fp32 pixel coordinates lie within DELTA / 4 o
 reference's own stem output lies inside the stem bound; the library is a library of its own (exports, hash, stamp, ABI); every refusal
 happens before any launch; the workspace formula; no kernel touches scratch; the device-free plugin surface.  No GPU compute is invoked."""
 import ctypes as C
-import importlib.util
 import inspect
 import os
 import re
@@ -17,7 +16,7 @@ import torch
 
 import dlss_cases as DC
 import lss_cases as LC
-from ddp_amd import _cm_lib, _eval_lib, _lib, _lss_lib, build, registry
+from ddp_amd import _cm_lib, build, registry
 from ddp_amd import _dlss_lib as M
 from ddp_amd import dlss as L
 from ddp_amd.bev.depth_lss import DepthLSSTransform
@@ -185,71 +184,27 @@ def test_reference_stem_output_lies_inside_the_bound(name):
     assert mutant.shape == want.shape and (np.abs(fix['stem'] - mutant) > bound).any()
 
 
-# ---- a library of its own ------------------------------------------------------------------------------------------------------------
-def _dyn_syms(path):
-    out = subprocess.run(['nm', '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if ' T ' in l)
-
-
-def test_library_builds_and_exports_exactly_the_header():
-    path = build.build_dlss(verbose=False)
-    assert os.path.exists(path) and not build.dlss_needs_build() and build.dlss_built_hash() == build.dlss_hash()
+# ---- the library's own (what every side library shares: tests/test_build_host.py) ------------------------------------------------------
+def test_binding_matches_the_header():
+    build.SIDE['dlss'].start(verbose=False)()
     header = open(os.path.join(ROOT, 'include', 'ddp_dlss_mi355x.h')).read()
-    declared = sorted(set(re.findall(r'\b(ddp_dlss_\w+)\s*\(', re.sub(r'/\*.*?\*/', '', header, flags=re.S))))
-    assert _dyn_syms(path) == declared == sorted(M.EXPORTS) and len(declared) == 8
-    script = open(os.path.join(build.DLSS_CSRC, 'dlss_exports.map')).read()
-    assert sorted(re.findall(r'\b(ddp_dlss_\w+);', script)) == declared and 'local:\n    *;' in script
-    lib = M.load()
-    assert lib.ddp_dlss_abi_version() == 1 == M.ABI_VERSION and '#define DDP_DLSS_ABI_VERSION 1' in header
     assert f'#define DDP_DLSS_STEM_FOLDED {M.STEM_FOLDED}' in header and M.STEM_FOLDED == 8 + 8 + 25 * 8 * 32 + 32
     assert (M.E_BADCFG, M.E_ALIGN, M.E_LAUNCH, M.E_NULL) == (_cm_lib.E_BADCFG, _cm_lib.E_ALIGN, _cm_lib.E_LAUNCH, _cm_lib.E_NULL)
     assert C.sizeof(M.Cfg) == 5 * 4 and C.sizeof(M.StemParams) == 12 * 8 + 2 * 8
-    # the other four libraries: untouched
-    build.build(verbose=False)
-    for p, exports, n in ((_lib.lib_path(), _lib.EXPORTS, 36), (build.EVAL_LIB_PATH, _eval_lib.EXPORTS, 6), (build.CM_LIB_PATH, _cm_lib.EXPORTS, 4),
-                          (build.LSS_LIB_PATH, _lss_lib.EXPORTS, 7)):
-        syms = [s for s in _dyn_syms(p) if 'ddp_' in s]
-        assert syms == sorted(exports) and len(syms) == n and not any(s.startswith('ddp_dlss') for s in syms)
-    assert _lib.ABI_VERSION == 7 and _eval_lib.ABI_VERSION == 1 and _cm_lib.ABI_VERSION == 1 and _lss_lib.ABI_VERSION == 1
-
-
-def test_hash_and_stamp_are_its_own(tmp_path):
-    assert build.DLSS_SOURCES == ['ddp_dlss.hip']
-    assert build.DLSS_STAMP_PATH.endswith(os.path.join('lib', '.dlss_sha')) and build.DLSS_LIB_PATH.endswith(os.path.join('lib', 'libddp_dlss.so'))
-    assert len({build.DLSS_STAMP_PATH, build.LSS_STAMP_PATH, build.CM_STAMP_PATH, build.EVAL_STAMP_PATH, build.STAMP_PATH, build.PROBE_STAMP_PATH}) == 6
-    cmd = build.dlss_cmd('x.so')
-    assert cmd[1:1 + len(build.FLAGS)] == build.FLAGS and cmd[-1] == 'x.so' and '-c' not in cmd and sum(a.endswith('.hip') for a in cmd) == 1
-    assert any(a.startswith('-Wl,--version-script=') and a.endswith('dlss_exports.map') for a in cmd)
-    sets = [{os.path.normpath(os.path.join(base, s)) for s in names}
-            for base, names in ((build.CSRC, build.SOURCES + build.HEADERS), (build.EVAL_CSRC, build.EVAL_SOURCES + build.EVAL_HEADERS),
-                                (build.CM_CSRC, build.CM_SOURCES + build.CM_HEADERS), (build.LSS_CSRC, build.LSS_SOURCES + build.LSS_HEADERS),
-                                (build.DLSS_CSRC, build.DLSS_SOURCES + build.DLSS_HEADERS))]
-    assert not any(sets[i] & sets[4] for i in range(4)) and os.path.normpath(os.path.join(ROOT, 'include', 'ddp_dlss_mi355x.h')) in sets[4]
-    assert len({build.dlss_hash(), build.lss_hash(), build.cm_hash(), build.eval_hash(), build.source_hash()}) == 5
-    # an edit of ddp_dlss.hip or of its header in a copy of the tree changes dlss_hash() and none of the other four
-    for d in ('ddp_amd', 'include'):
-        shutil.copytree(os.path.join(ROOT, d), tmp_path / d, ignore=shutil.ignore_patterns('lib', 'lib_*', '__pycache__'))
-    spec = importlib.util.spec_from_file_location('_build_of_the_copy_dlss', str(tmp_path / 'ddp_amd' / 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    hashes = lambda: [b.source_hash(), b.eval_hash(), b.cm_hash(), b.lss_hash(), b.dlss_hash()]
-    before = hashes()
-    assert before == [build.source_hash(), build.eval_hash(), build.cm_hash(), build.lss_hash(), build.dlss_hash()]
-    for rel in (('ddp_amd', 'csrc', 'dlss', 'ddp_dlss.hip'), ('include', 'ddp_dlss_mi355x.h'), ('ddp_amd', 'csrc', 'dlss', 'dlss_exports.map')):
-        with open(tmp_path.joinpath(*rel), 'a') as f:
-            f.write('\n')
-        after = hashes()
-        assert after[:4] == before[:4] and after[4] != before[4] and b.dlss_needs_build()
-        before = after
 
 
 def test_stale_or_missing_library_raises(tmp_path, monkeypatch):
     with pytest.raises(M.DdpDlssError, match='not found'):
         M.load(str(tmp_path / 'libddp_dlss.so'))
-    monkeypatch.setattr(build, 'dlss_built_hash', lambda: 'feedfeedfeedfeed')
-    monkeypatch.setattr(M, '_libs', {})
-    with pytest.raises(M.DdpDlssError, match='stale'):
+    monkeypatch.setattr(M._binding, 'libs', {})
+    with monkeypatch.context() as m:
+        m.setattr(build.SIDE['dlss'], 'built_hash', lambda: 'feedfeedfeedfeed')
+        with pytest.raises(M.DdpDlssError, match='is stale'):
+            M.load()
+    monkeypatch.setattr(M._binding, 'abi_version', M.ABI_VERSION + 1)
+    with pytest.raises(M.DdpDlssError, match='ABI mismatch: library 1 vs binding 2') as e:
         M.load()
+    assert e.value.code is None and isinstance(e.value, RuntimeError) and not M._binding.libs
 
 
 FAKE = 0x10000    # a non-NULL, 256-byte aligned "device pointer": every call below is refused before anything is enqueued
@@ -367,7 +322,7 @@ HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not available')
 def test_no_kernel_touches_scratch(tmp_path):
     out = tmp_path / 'dlss.s'
-    src = os.path.join(build.DLSS_CSRC, 'ddp_dlss.hip')
+    src = os.path.join(build.SIDE['dlss'].csrc, 'ddp_dlss.hip')
     subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-x', 'hip', src,
                     '--cuda-device-only', '-S', '-o', str(out)], check=True, capture_output=True, timeout=600)
     figures = {}

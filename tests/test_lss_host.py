@@ -4,7 +4,6 @@ promises, counted in float64; a restatement with ``floor`` instead of truncation
 stays below 1 %; the library is a library of its own (exports, hash, stamp, ABI); every refusal happens before any launch; the
 workspace formula; no kernel touches scratch; the device-free plugin surface.  No GPU compute is invoked."""
 import ctypes as C
-import importlib.util
 import os
 import re
 import shutil
@@ -15,7 +14,7 @@ import pytest
 import torch
 
 import lss_cases as LC
-from ddp_amd import _cm_lib, _eval_lib, _lib, build, registry
+from ddp_amd import _cm_lib, build, registry
 from ddp_amd import _lss_lib as M
 from ddp_amd import lss as L
 from ddp_amd.bev.lss import LSSTransform
@@ -137,69 +136,28 @@ def test_near_boundary_share(name):
     assert LC.admissible(c, q, LC.ranks_of(c, LC.cells_f32(c))[0]).all()
 
 
-# ---- a library of its own ------------------------------------------------------------------------------------------------------------
-def _dyn_syms(path):
-    out = subprocess.run(['nm', '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if ' T ' in l)
-
-
-def test_library_builds_and_exports_exactly_the_header():
-    path = build.build_lss(verbose=False)
-    assert os.path.exists(path) and not build.lss_needs_build() and build.lss_built_hash() == build.lss_hash()
+# ---- the library's own (what every side library shares: tests/test_build_host.py) ------------------------------------------------------
+def test_binding_matches_the_header():
+    build.SIDE['lss'].start(verbose=False)()
     header = open(os.path.join(ROOT, 'include', 'ddp_lss_mi355x.h')).read()
-    declared = sorted(set(re.findall(r'\b(ddp_lss_\w+)\s*\(', re.sub(r'/\*.*?\*/', '', header, flags=re.S))))
-    assert _dyn_syms(path) == declared == sorted(M.EXPORTS) and len(declared) == 7
-    script = open(os.path.join(build.LSS_CSRC, 'lss_exports.map')).read()
-    assert sorted(re.findall(r'\b(ddp_lss_\w+);', script)) == declared and 'local:\n    *;' in script
-    lib = M.load()
-    assert lib.ddp_lss_abi_version() == 1 == M.ABI_VERSION and '#define DDP_LSS_ABI_VERSION 1' in header
     assert '#define DDP_LSS_MAX_CHANNELS 256' in header and '#define DDP_LSS_MAX_DEPTH_BINS 512' in header
+    assert (M.MAX_CHANNELS, M.MAX_DEPTH_BINS) == (256, 512)
     assert (M.E_BADCFG, M.E_ALIGN, M.E_LAUNCH, M.E_NULL) == (_cm_lib.E_BADCFG, _cm_lib.E_ALIGN, _cm_lib.E_LAUNCH, _cm_lib.E_NULL)
     assert C.sizeof(M.Cfg) == 8 * 4 + 12 * 8 + 3 * 4 + 4                  # 8 ints, 12 doubles, nx[3], tail padding
-    # the other three libraries: untouched
-    build.build(verbose=False)
-    for p, exports, n in ((_lib.lib_path(), _lib.EXPORTS, 36), (build.EVAL_LIB_PATH, _eval_lib.EXPORTS, 6), (build.CM_LIB_PATH, _cm_lib.EXPORTS, 4)):
-        syms = [s for s in _dyn_syms(p) if 'ddp_' in s]
-        assert syms == sorted(exports) and len(syms) == n and not any(s.startswith('ddp_lss') for s in syms)
-    assert _lib.ABI_VERSION == 7 and _eval_lib.ABI_VERSION == 1 and _cm_lib.ABI_VERSION == 1
-
-
-def test_hash_and_stamp_are_its_own(tmp_path):
-    assert build.LSS_SOURCES == ['ddp_lss.hip']
-    assert build.LSS_STAMP_PATH.endswith(os.path.join('lib', '.lss_sha')) and build.LSS_LIB_PATH.endswith(os.path.join('lib', 'libddp_lss.so'))
-    assert len({build.LSS_STAMP_PATH, build.CM_STAMP_PATH, build.EVAL_STAMP_PATH, build.STAMP_PATH, build.PROBE_STAMP_PATH}) == 5
-    cmd = build.lss_cmd('x.so')
-    assert cmd[1:1 + len(build.FLAGS)] == build.FLAGS and cmd[-1] == 'x.so' and '-c' not in cmd and sum(a.endswith('.hip') for a in cmd) == 1
-    assert any(a.startswith('-Wl,--version-script=') and a.endswith('lss_exports.map') for a in cmd)
-    sets = [{os.path.normpath(os.path.join(base, s)) for s in names}
-            for base, names in ((build.CSRC, build.SOURCES + build.HEADERS), (build.EVAL_CSRC, build.EVAL_SOURCES + build.EVAL_HEADERS),
-                                (build.CM_CSRC, build.CM_SOURCES + build.CM_HEADERS), (build.LSS_CSRC, build.LSS_SOURCES + build.LSS_HEADERS))]
-    assert not any(sets[i] & sets[3] for i in range(3)) and os.path.normpath(os.path.join(ROOT, 'include', 'ddp_lss_mi355x.h')) in sets[3]
-    assert len({build.lss_hash(), build.cm_hash(), build.eval_hash(), build.source_hash()}) == 4
-    # an edit of ddp_lss.hip or of its header in a copy of the tree changes lss_hash() and none of the other three
-    for d in ('ddp_amd', 'include'):
-        shutil.copytree(os.path.join(ROOT, d), tmp_path / d, ignore=shutil.ignore_patterns('lib', 'lib_*', '__pycache__'))
-    spec = importlib.util.spec_from_file_location('_build_of_the_copy_lss', str(tmp_path / 'ddp_amd' / 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    hashes = lambda: [b.source_hash(), b.eval_hash(), b.cm_hash(), b.lss_hash()]
-    before = hashes()
-    assert before == [build.source_hash(), build.eval_hash(), build.cm_hash(), build.lss_hash()]
-    for rel in (('ddp_amd', 'csrc', 'lss', 'ddp_lss.hip'), ('include', 'ddp_lss_mi355x.h')):
-        with open(tmp_path.joinpath(*rel), 'a') as f:
-            f.write('// edited\n')
-        after = hashes()
-        assert after[:3] == before[:3] and after[3] != before[3] and b.lss_needs_build()
-        before = after
 
 
 def test_stale_or_missing_library_raises(tmp_path, monkeypatch):
     with pytest.raises(M.DdpLssError, match='not found'):
         M.load(str(tmp_path / 'libddp_lss.so'))
-    monkeypatch.setattr(build, 'lss_built_hash', lambda: 'feedfeedfeedfeed')
-    monkeypatch.setattr(M, '_libs', {})
-    with pytest.raises(M.DdpLssError, match='stale'):
+    monkeypatch.setattr(M._binding, 'libs', {})
+    with monkeypatch.context() as m:
+        m.setattr(build.SIDE['lss'], 'built_hash', lambda: 'feedfeedfeedfeed')
+        with pytest.raises(M.DdpLssError, match='is stale'):
+            M.load()
+    monkeypatch.setattr(M._binding, 'abi_version', M.ABI_VERSION + 1)
+    with pytest.raises(M.DdpLssError, match='ABI mismatch: library 1 vs binding 2') as e:
         M.load()
+    assert e.value.code is None and isinstance(e.value, RuntimeError) and not M._binding.libs
 
 
 FAKE = 0x10000    # a non-NULL, 256-byte aligned "device pointer": every call below is refused before anything is enqueued
@@ -299,7 +257,7 @@ HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not available')
 def test_no_kernel_touches_scratch(tmp_path):
     out = tmp_path / 'lss.s'
-    src = os.path.join(build.LSS_CSRC, 'ddp_lss.hip')
+    src = os.path.join(build.SIDE['lss'].csrc, 'ddp_lss.hip')
     subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-x', 'hip', src,
                     '--cuda-device-only', '-S', '-o', str(out)], check=True, capture_output=True, timeout=600)
     figures = {}
