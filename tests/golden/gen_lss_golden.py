@@ -11,7 +11,8 @@ reference's.
 
 Writes, per case, tests/golden/lss/lss_<case>.npz (the inputs, the state dict, the fp32 geometry, the kept mask with the ranks the
 reference's indices give, the output with ``downsample=1``) and lss_<case>_ds2.npz (the state dict and the output of the
-``downsample=2`` module, which shares ``depthnet``; not for ``odd``, whose nz = 2 the reference's downsample stack cannot take).
+``downsample=2`` module, which shares ``depthnet``; not for a case with nz > 1 - ``odd``, ``c129``, ``c256`` -, whose nz * C
+channels the reference's downsample stack cannot take).  The synthetic cases of ``lss_cases.SYNTH`` have no geometry and no fixture.
 Arrays only.  Parameters are rounded to multiples of 2^-8 so that the files compress; the ``long`` case has the points of ``cfg``
 and does not repeat its geometry.
 """

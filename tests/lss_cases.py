@@ -2,6 +2,7 @@
 against.  Device-free: numpy and CPU torch only.
 
   ``CASES`` / ``case(name)``   geometry + a nuScenes-like rig (six yaws, focal ~1266, post_rot 0.48 I, post_trans (-32, -176, 0)) + inputs
+  ``SYNTH`` / ``synth(name)``  chosen rank tables for ``plan_from_ranks`` (exact list lengths, 1025 scan tiles) + inputs; no geometry
   ``geometry_f32``             the fp32 chain of the reference's ``get_geometry`` as torch CPU ops -> (B, N, D, fH, fW, 3)
   ``cells_f64``                the same chain in float64 -> the cell coordinate q per axis, before truncation
   ``ranks_of``                 q -> int32 ranks with truncation toward zero (``mode='trunc'``, what ``.long()`` does) or ``floor``
@@ -33,8 +34,17 @@ CASES = {
                  longest=1),
     'empty': dict(B=1, yaws=[0.0, 180.0], pitch=[0.0, 0.0], feature=(2, 3), image=(256, 704), C=4, in_channels=3,
                   dbound=(1.0, 21.0, 4.0), xbound=(500.0, 532.0, 2.0), ybound=(500.0, 532.0, 2.0), zbound=(-10.0, 10.0, 20.0), longest=0),
+    # past the first tile of each tiling of ddp_lss.hip: K = 4230 cells (five scan tiles of 1024, K % 4 = 2), 135 pixels (three
+    # pre-pass tiles of 64, the last of 7)
+    'tiles': dict(B=2, yaws=[0.0, 120.0, 240.0], pitch=[5.0, -15.0, 0.0], feature=(9, 15), image=(256, 704), C=5, in_channels=4,
+                  dbound=(1.0, 61.0, 6.0), xbound=(-22.5, 22.5, 1.0), ybound=(-23.5, 23.5, 1.0), zbound=(-10.0, 10.0, 20.0), longest=100),
+    # three and four channel groups of 64 in the pool; nz = 2, so that the fixtures stay small (no downsample = 2 variant)
+    'c129': dict(B=1, yaws=[45.0, 225.0], pitch=[10.0, -20.0], feature=(5, 13), image=(256, 704), C=129, in_channels=3,
+                 dbound=(1.0, 31.0, 5.0), xbound=(-8.0, 8.0, 4.0), ybound=(-9.0, 9.0, 2.0), zbound=(-4.0, 4.0, 4.0), longest=65),
+    'c256': dict(B=1, yaws=[25.0, -155.0], pitch=[14.0, -16.0], feature=(8, 9), image=(256, 704), C=256, in_channels=3,
+                 dbound=(1.2, 49.2, 8.0), xbound=(-9.0, 9.0, 6.0), ybound=(-17.5, 17.5, 1.0), zbound=(-4.0, 4.0, 4.0), longest=48),
 }
-NAMES = list(CASES)
+NAMES = list(CASES)             # a case's seeds follow its place here: new cases are appended
 ALL_FACES = ['x-', 'x+', 'y-', 'y+', 'z-', 'z+']
 LSS_RUN = 32               # the pooling block's run of iy cells (ddp_lss.hip)
 
@@ -105,6 +115,57 @@ def case(name):
     D = int(torch.arange(*s['dbound'], dtype=torch.float).shape[0])
     c = dict(name=name, spec=s, kwargs=kwargs, img=img, camera2lidar=f32(c2l), camera_intrinsics=f32(intr), img_aug_matrix=f32(aug),
              lidar_aug_matrix=f32(laug), B=B, N=N, D=D, C=s['C'], nx=nx, fH=fH, fW=fW, P=B * N * D * fH * fW, K=B * nx[2] * nx[0] * nx[1])
+    _cache[name] = c
+    return c
+
+
+# ---- synthetic cases: a chosen rank table for ``plan_from_ranks``, no geometry, no fixture, no plugin run; not in NAMES ----------------
+# list length by cell on a 3 x 37 x 1 grid (K = 111, K % 4 = 3): 1..5 around the four rows the pool keeps in flight, 63 / 64 / 65 and
+# 127 / 128 / 129 around the 64 entries a wave takes at a time; 36 and 37 are the last cell of row ix = 0 and the first of row ix = 1;
+# 108, 109 and 110 are the three counts of the scan's scalar tail
+LENS = {0: 1, 1: 2, 2: 3, 3: 4, 4: 5, 31: 7, 32: 8, 36: 63, 37: 64, 73: 65, 74: 127, 107: 128, 108: 129, 109: 1, 110: 3}
+# 1025 scan tiles of 1024 cells, the last of 3: the one-block scan of the tile sums takes two values per thread.  The named cells sit
+# on either side of the first tile boundary and of the last, and in the last tile's scalar tail.
+SCAN_NX1 = 1024 * 1024 + 3
+SCAN_CELLS = {0: 2, 1023: 1, 1024: 3, SCAN_NX1 - 4: 1, SCAN_NX1 - 3: 2, SCAN_NX1 - 2: 1, SCAN_NX1 - 1: 5}
+SCAN_SINGLES = 600         # further cells, drawn by the seed, of one point each
+_lens = lambda C: dict(C=C, D=16, feature=(8, 9), nx=[3, 37, 1], lens=LENS, singles=0, table_seed=2000)
+SYNTH = {
+    'lens_c64': _lens(64), 'lens_c65': _lens(65), 'lens_c128': _lens(128), 'lens_c192': _lens(192), 'lens_c193': _lens(193),
+    'scan': dict(C=1, D=4, feature=(32, 32), nx=[1, SCAN_NX1, 1], lens=SCAN_CELLS, singles=SCAN_SINGLES, table_seed=2001),
+}
+SYNTH_NAMES = list(SYNTH)
+
+
+def synth(name):
+    """-> dict with the keys ``pool_f64``, ``pool_bound`` and ``workspace_bytes`` read (and ``spec``, whose bounds make ``LssPool``
+    derive the stated nx and D), plus ``ranks`` (P,) int32 and the pool's input ``x`` (B * N, D + C, fH, fW) fp32 in [-2, 2): a
+    logit range of at most 4.  B = N = 1.  The points are dealt to the cells through a seeded permutation of the point ids, so no
+    list is a run of consecutive ids; every other point is dropped (-1).  Built once per name and never modified."""
+    if name in _cache:
+        return _cache[name]
+    s = SYNTH[name]
+    fH, fW = s['feature']
+    D, C = s['D'], s['C']
+    bounds = dict(xbound=(0.0, float(s['nx'][0]), 1.0), ybound=(0.0, float(s['nx'][1]), 1.0), zbound=(0.0, float(s['nx'][2]), 1.0),
+                  dbound=(1.0, 1.0 + D, 1.0))
+    nx = [int(v) for v in torch.LongTensor([(r[1] - r[0]) / r[2] for r in (bounds['xbound'], bounds['ybound'], bounds['zbound'])])]
+    assert nx == s['nx'] and int(torch.arange(*bounds['dbound'], dtype=torch.float).shape[0]) == D
+    P, K = D * fH * fW, nx[2] * nx[0] * nx[1]
+    rng = np.random.default_rng(s['table_seed'])
+    lens = dict(s['lens'])
+    free = np.setdiff1d(np.arange(K), np.fromiter(lens, dtype=np.int64))
+    lens.update((int(cell), 1) for cell in rng.choice(free, s['singles'], replace=False))
+    order = rng.permutation(P)
+    ranks = np.full(P, -1, dtype=np.int32)
+    at = 0
+    for cell, n in lens.items():
+        ranks[order[at:at + n]] = cell
+        at += n
+    assert at <= P
+    x = np.random.default_rng(3000 + SYNTH_NAMES.index(name)).uniform(-2.0, 2.0, (1, D + C, fH, fW)).astype(np.float32)
+    c = dict(name=name, spec=dict(bounds, image=(256, 704), feature=(fH, fW), lens=lens), B=1, N=1, D=D, C=C, nx=nx, fH=fH, fW=fW, P=P, K=K,
+             ranks=ranks, x=torch.from_numpy(x))
     _cache[name] = c
     return c
 

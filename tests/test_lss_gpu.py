@@ -3,11 +3,15 @@ tests/lss_cases.py.  Every buffer is exactly sized and guarded; the workspace an
 floats, -1 as integers).
 
   1  the rank table of ``plan`` against the float64 restatement, every point (a point within DELTA of a cell boundary may take
-     either side)
-  2  ``pool`` on injected ranks against the float64 sum over the same table, inside the derived bound; empty cells exactly +0.0
-  3  pool(plan(matrices)) is bit-identical to pool(plan_from_ranks(ranks()))
-  4  ten runs give the same bits (ranks, lists, output); B = 2 equals two B = 1 calls; a replayed graph follows new inputs
-  5  the plugin on the fixtures' state dicts, ``downsample`` 1 and 2
+     either side): the geometric cases (``NAMES``)
+  2  ``pool`` on injected ranks against the float64 sum over the same table, inside the derived bound; empty cells exactly +0.0:
+     the geometric cases and the synthetic rank tables (``SYNTH_NAMES``: chosen list lengths at 64 to 193 channels, 1025 scan tiles)
+  3  pool(plan(matrices)) is bit-identical to pool(plan_from_ranks(ranks())): the geometric cases
+  4  ten runs give the same bits (ranks, lists, output) and leave a plan whose segment lengths are the counts of its rank table,
+     cell for cell (``odd``, ``cfg``, ``long``, ``tiles``, ``c256``; ``lens_c193`` and ``scan`` through ``plan_from_ranks``);
+     B = 2 equals two B = 1 calls (``odd``, ``tiles``); a replayed graph follows new inputs
+  5  the plugin on the fixtures' state dicts, ``downsample`` 1 and 2 (2 where nz = 1): the geometric cases
+The parts loop over their cases inside one test each: the GPU suite stays below 5000 test ids.
 Reads only tests/golden/ and tests/lss_cases.py."""
 import os
 
@@ -92,7 +96,11 @@ _shared = {}
 
 def _reference(name):
     """per case, computed once and left unchanged: the float64 cells, the fp32 restatement's ranks, the depthnet output of the
-    fixture's weights, the float64 pool over the fp32 ranks"""
+    fixture's weights, the float64 pool over the fp32 ranks; for a synthetic case its own rank table and input, and the float64 pool"""
+    if name in LC.SYNTH and name not in _shared:
+        c = LC.synth(name)
+        want, absum, lists = LC.pool_f64(c, c['x'].numpy(), c['ranks'])
+        _shared[name] = dict(c=c, r32=c['ranks'], x=c['x'], want=want, absum=absum, lists=lists, bound=LC.pool_bound(c, absum, lists))
     if name not in _shared:
         c = LC.case(name)
         fix = LC.load_fixture(name, GOLDEN)[0]
@@ -156,7 +164,7 @@ def _rank_table_against_float64(name):
 def test_pool_on_injected_ranks_within_the_bound():
     """one test for all the cases (each is a few launches on small shapes, and the GPU suite stays below 5000 test ids); a failure
     names its case"""
-    _each(LC.NAMES, _pool_on_injected_ranks_within_the_bound)
+    _each(LC.NAMES + LC.SYNTH_NAMES, _pool_on_injected_ranks_within_the_bound)
 
 
 def _pool_on_injected_ranks_within_the_bound(name):
@@ -213,19 +221,24 @@ def _plan_from_matrices_equals_plan_from_its_ranks(name):
 def test_ten_runs_give_the_same_bits():
     """one test for all the cases (each is a few launches on small shapes, and the GPU suite stays below 5000 test ids); a failure
     names its case"""
-    _each(['odd', 'cfg', 'long'], _ten_runs_give_the_same_bits)
+    _each(['odd', 'cfg', 'long', 'tiles', 'c256', 'lens_c193', 'scan'], _ten_runs_give_the_same_bits)
 
 
 def _ten_runs_give_the_same_bits(name):
     ref = _reference(name)
     c = ref['c']
     x = ref['x'].cuda()
-    cam, extra = _cameras(c)
+    if name in LC.SYNTH:                                                  # no geometry: the plan is that of the injected table
+        table = torch.from_numpy(ref['r32']).view(c['B'], c['N'], c['D'], c['fH'], c['fW']).cuda()
+        plan = lambda: rig.pool.plan_from_ranks(table)
+    else:
+        cam, extra = _cameras(c)
+        plan = lambda: rig.pool.plan(cam, extra)
     rig = Rig(c)
     first = None
     for i in range(10):
         rig.refill()
-        rig.pool.plan(cam, extra)
+        plan()
         out = rig.run_pool(x)
         state = (_regions(rig), out.tobytes())                            # rank table, offsets, lists, probabilities, rows; output
         if first is None:
@@ -236,6 +249,11 @@ def _ten_runs_give_the_same_bits(name):
     kept = lists.size
     assert np.array_equal(ranks, rig.pool.ranks().reshape(-1).cpu().numpy())
     assert offs[0] == 0 and offs[-1] == kept and (np.diff(offs) >= 0).all()
+    if name in LC.SYNTH:
+        assert np.array_equal(ranks, ref['r32'])
+    # every segment is as long as its cell's count in the rank table, the empty cells too: a dropped tile start or a dropped count
+    # of the scan's tail shows here even where the cells around it are empty
+    assert offs.size == c['K'] + 1 and np.array_equal(np.diff(offs), np.bincount(ranks[ranks >= 0], minlength=c['K']))
     assert np.array_equal(np.sort(lists), np.flatnonzero(ranks >= 0))
     for cell in np.flatnonzero(np.diff(offs) > 0):
         seg = lists[offs[cell]:offs[cell + 1]]
@@ -243,7 +261,12 @@ def _ten_runs_give_the_same_bits(name):
 
 
 def test_batch_of_two_equals_two_single_calls():
-    ref = _reference('odd')
+    """``odd``: two slabs per sample; ``tiles``: the second sample's cells start in the middle of a scan tile"""
+    _each(['odd', 'tiles'], _batch_of_two_equals_two_single_calls)
+
+
+def _batch_of_two_equals_two_single_calls(name):
+    ref = _reference(name)
     c = ref['c']
     assert c['B'] == 2
     x = ref['x'].cuda()

@@ -1,6 +1,8 @@
 """CPU side of the device-side LSS lift and pool (tests/test_lss_gpu.py runs the cases on an MI355X): the fixtures recorded from the
 reference's own ``LSSTransform`` equal the restatements of tests/lss_cases.py (ranks exactly); every case holds the witnesses its name
-promises, counted in float64; a restatement with ``floor`` instead of truncation changes every kept mask; the near-boundary share
+promises, counted in float64 - the synthetic rank tables of ``lss_cases.SYNTH`` included -; a restatement with ``floor`` instead of
+truncation changes every kept mask; five wrong kernels (a pixel index modulo 64, channel groups read as zero, segment starts without
+the tile starts, the last K % 4 counts dropped, list tails dropped), restated in float64, leave the bound; the near-boundary share
 stays below 1 %; the library is a library of its own (exports, hash, stamp, ABI); every refusal happens before any launch; the
 workspace formula; no kernel touches scratch; the device-free plugin surface.  No GPU compute is invoked."""
 import ctypes as C
@@ -22,6 +24,7 @@ from ddp_amd.bev.lss import LSSTransform
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'lss')
 WITNESSED = [n for n in LC.NAMES if n != 'empty']
+SCAN_TILE, PRE_PIX = 1024, 64          # ddp_lss.hip: counts a block of the tiled scan owns; pixels a pre-pass block owns
 
 
 # ---- fixture = restatement -----------------------------------------------------------------------------------------------------------
@@ -57,10 +60,11 @@ def test_fixture_equals_the_restatement(name):
     assert (np.abs(fix['out'] - want) <= LC.pool_bound(c, absum, Ls)).all()
     assert (fix['out'][absum == 0] == 0).all()
     if ds2 is not None:
+        assert c['nx'][2] == 1
         assert ds2['out'].shape == (c['B'], c['C'], (c['nx'][0] + 1) // 2, (c['nx'][1] + 1) // 2)
         assert np.array_equal(ds2['sd/depthnet.weight'], fix['sd/depthnet.weight'])
     else:
-        assert name == 'odd'
+        assert c['nx'][2] > 1 and not os.path.exists(os.path.join(GOLDEN, f'lss_{name}_ds2.npz'))
 
 
 # ---- witnesses -----------------------------------------------------------------------------------------------------------------------
@@ -108,6 +112,124 @@ def test_each_name_keeps_its_promise():
     assert c['nx'][1] % LC.LSS_RUN != 0 and c['nx'][1] > LC.LSS_RUN
     c, q, r, kept = _witness('empty')
     assert not kept.any() and (r == -1).all()
+    # past the first tile of every tiling of ddp_lss.hip (1024 cells per scan tile, 4 counts per thread, 64 pixels per pre-pass
+    # block, 64 channels per pool group, 32 iy cells per pool block)
+    c, q, r, kept = _witness('tiles')
+    assert (c['B'], c['N'], c['D'], c['fH'], c['fW'], c['C'], c['nx']) == (2, 3, 10, 9, 15, 5, [45, 47, 1]) and c['P'] == 8100
+    assert c['K'] == 4230 > 4 * SCAN_TILE and c['K'] % 4 == 2 and (c['K'] // 2) % SCAN_TILE != 0     # the second sample starts inside a tile
+    assert c['fH'] * c['fW'] == 135 == 2 * PRE_PIX + 7
+    assert sorted(set(r[kept] // SCAN_TILE)) == [0, 1, 2, 3, 4]
+    assert sorted(set((np.flatnonzero(kept) % 135) // PRE_PIX)) == [0, 1, 2]
+    assert sorted(set((r[kept] % 47) // LC.LSS_RUN)) == [0, 1] and sorted(set(r[kept] // 2115)) == [0, 1]
+    lists = np.bincount(r[kept], minlength=c['K'])
+    assert lists.max() > 64 and sorted(set(lists[lists > 0] % 4)) == [0, 1, 2, 3]
+    for name, groups in (('c129', 3), ('c256', 4)):
+        c, q, r, kept = _witness(name)
+        HW, cells = c['fH'] * c['fW'], c['nx'][0] * c['nx'][1]
+        assert (c['C'] + 63) // 64 == groups and HW > PRE_PIX and HW % PRE_PIX != 0 and c['nx'][2] == 2
+        assert sorted(set(r[kept] // cells)) == [0, 1]                     # both slabs hold points
+        assert (np.flatnonzero(kept) % HW >= PRE_PIX).any()
+    assert LC.case('c129')['C'] == 2 * 64 + 1 and LC.case('c129')['fH'] * LC.case('c129')['fW'] == PRE_PIX + 1
+    assert LC.case('c256')['C'] == M.MAX_CHANNELS and LC.case('c256')['K'] % 4 == 2
+    # the synthetic rank tables: the exact list lengths, and the scan past one block's 1024 tile sums
+    assert [LC.SYNTH[n]['C'] for n in LC.SYNTH_NAMES if n.startswith('lens_')] == [64, 65, 128, 192, 193]
+    for name in LC.SYNTH_NAMES:
+        c = LC.synth(name)
+        kept = c['ranks'] >= 0
+        lists = np.bincount(c['ranks'][kept], minlength=c['K'])
+        assert c['K'] % 4 == 3 and c['x'].shape == (1, c['D'] + c['C'], c['fH'], c['fW']) and c['x'].dtype == torch.float32
+        assert float(c['x'].max() - c['x'].min()) <= 4.0
+        if name == 'scan':
+            assert (c['D'], c['fH'] * c['fW'], c['P'], c['C'], c['nx']) == (4, 16 * PRE_PIX, 4096, 1, [1, 1048579, 1])
+            tiles = (c['K'] + SCAN_TILE - 1) // SCAN_TILE
+            assert tiles == 1025 and (tiles + 1023) // 1024 == 2 and c['K'] - 1024 * SCAN_TILE == 3
+            assert all(lists[cell] >= 1 for cell in (0, 1023, 1024, 1048575, 1048576, 1048577, 1048578))
+            assert (lists > 0).sum() == 7 + 600 and lists.sum() == 15 + 600
+        else:
+            assert (c['D'], c['fH'] * c['fW'], c['P'], c['nx'], c['K']) == (16, 72, 1152, [3, 37, 1], 111)
+            assert {int(k): int(lists[k]) for k in np.flatnonzero(lists)} == LC.LENS == {
+                0: 1, 1: 2, 2: 3, 3: 4, 4: 5, 31: 7, 32: 8, 36: 63, 37: 64, 73: 65, 74: 127, 107: 128, 108: 129, 109: 1, 110: 3}
+            assert lists.sum() == 610 and np.array_equal(c['ranks'], LC.synth('lens_c64')['ranks'])          # one table
+            assert 36 % 37 == 36 and 37 % 37 == 0 and 37 - LC.LSS_RUN == 5                                     # row edge; a run of 5 cells
+        for cell in np.flatnonzero(lists >= 3):                            # dealt through a permutation: no list is a run of ids
+            assert (np.diff(np.flatnonzero(c['ranks'] == cell)) > 1).any(), cell
+
+
+def test_no_lss_fixture_outgrows_the_largest_of_the_first_set():
+    sizes = {f: os.path.getsize(os.path.join(GOLDEN, f)) for f in os.listdir(GOLDEN) if f.endswith('.npz')}
+    assert len(sizes) == 17 and max(sizes.values()) == sizes['lss_cfg.npz'] == 451541, sizes
+
+
+# ---- what a wrong kernel would show: each variant, restated in float64, leaves the bound on the case that is there for it ---------------
+def _pool_inputs(name):
+    if name in LC.SYNTH:
+        c = LC.synth(name)
+        return c, c['x'].numpy(), c['ranks']
+    c = LC.case(name)
+    fix = LC.load_fixture(name, GOLDEN)[0]
+    return c, LC.depthnet_out(c, fix['sd/depthnet.weight'], fix['sd/depthnet.bias']).numpy(), fix['ranks']
+
+
+def _pixel_modulo_64(c, x, ranks):
+    """(a) the pre-pass forgets its tile: pixel px reads pixel px % 64"""
+    px = np.arange(c['fH'] * c['fW']) % PRE_PIX
+    return x.reshape(x.shape[0], x.shape[1], -1)[:, :, px].reshape(x.shape), ranks
+
+
+def _channels_from(first):
+    def mutate(c, x, ranks):
+        """(b) the pool's channel groups past ``first`` read as zero"""
+        x = x.copy()
+        x[:, c['D'] + first:] = 0.0
+        return x, ranks
+    return mutate
+
+
+def _last_counts_dropped(c, x, ranks):
+    """(d) the scan drops the last K % 4 counts: those cells' lists are empty"""
+    return x, np.where(ranks >= c['K'] - c['K'] % 4, -1, ranks).astype(np.int32)
+
+
+def _list_tails_dropped(c, x, ranks):
+    """(e) the pool walks four entries at a time and forgets the rest: the last L % 4 entries of every list"""
+    ranks = ranks.copy()
+    for cell in np.unique(ranks[ranks >= 0]):
+        ids = np.flatnonzero(ranks == cell)
+        ranks[ids[ids.size - ids.size % 4:]] = -1
+    return x, ranks
+
+
+WRONG = ([('pixel % 64', _pixel_modulo_64, n) for n in ('tiles', 'c129')]
+         + [(f'channels from {first} zero', _channels_from(first), n) for n, first in (('c129', 128), ('c256', 128), ('c256', 192),
+                                                                                      ('lens_c193', 128), ('lens_c193', 192))]
+         + [('last K % 4 counts dropped', _last_counts_dropped, n) for n in LC.SYNTH_NAMES if n.startswith('lens_')]
+         + [('list tails dropped', _list_tails_dropped, n) for n in LC.SYNTH_NAMES if n.startswith('lens_')])
+
+
+@pytest.mark.parametrize('what,mutate,name', WRONG, ids=[f'{w}-{n}' for w, _, n in WRONG])
+def test_a_wrong_pool_leaves_the_bound(what, mutate, name):
+    c, x, ranks = _pool_inputs(name)
+    want, absum, lists = LC.pool_f64(c, x, ranks)
+    bound = LC.pool_bound(c, absum, lists)
+    got = LC.pool_f64(c, *mutate(c, x, ranks))[0]
+    assert (np.abs(got - want) > bound).any(), (what, name)
+    assert (np.abs(LC.pool_f64(c, x.copy(), ranks.copy())[0] - want) <= bound).all()          # and the restatement itself stays inside
+
+
+@pytest.mark.parametrize('name', ['tiles', 'scan'])
+def test_segment_starts_without_the_tile_starts_are_wrong(name):
+    """(c) the tiled scan forgets ``sums[tile]``: the starts of every tile begin at zero again.  Offsets compared, not the pool."""
+    c, x, ranks = _pool_inputs(name)
+    lists = np.bincount(ranks[ranks >= 0], minlength=c['K']).astype(np.int64)
+    starts = np.cumsum(lists) - lists
+    tile = np.arange(c['K']) // SCAN_TILE
+    local = starts - starts[tile * SCAN_TILE]
+    assert tile.max() >= 4 and np.array_equal(local[:SCAN_TILE], starts[:SCAN_TILE])
+    wrong = np.flatnonzero((local != starts) & (lists > 0))               # a non-empty cell whose list would be read from elsewhere
+    assert wrong.size and set(tile[wrong]) == set(tile[(lists > 0) & (tile > 0)])
+    # and the lengths alone do not show it: np.diff of the wrong starts differs from the counts only at tile starts
+    diff = np.diff(np.append(local, local[-1] + lists[-1]))
+    assert set(np.flatnonzero(diff != lists)) <= set(np.arange(SCAN_TILE, c['K'], SCAN_TILE) - 1)
 
 
 @pytest.mark.parametrize('name', WITNESSED)
@@ -234,8 +356,8 @@ def test_refusals_happen_before_any_launch():
 
 def test_workspace_formula_and_rank_table_place():
     lib = M.load()
-    for name in LC.NAMES:
-        c = LC.case(name)
+    for name in LC.NAMES + LC.SYNTH_NAMES:                                 # the synthetic bounds make LssPool derive the stated nx and D
+        c = LC.synth(name) if name in LC.SYNTH else LC.case(name)
         s = c['spec']
         pool = L.LssPool(s['image'], s['feature'], s['xbound'], s['ybound'], s['zbound'], s['dbound'], c['C'])
         assert (pool.D, pool.nx, pool.C) == (c['D'], c['nx'], c['C'])
