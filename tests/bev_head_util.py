@@ -160,3 +160,50 @@ def sample(x, noise, sd, cfg, trace=None):
         mask_t = x0 * alpha_next + pred_noise * sigma_next
         outs.append(prob)
     return torch.cat(outs, dim=0).mean(dim=0, keepdim=True), torch.stack(outs)
+
+
+# ---- oracle-driven cases beyond the fixtures (tests/test_bev_head_gpu.py; the step record's bev cases) -----------------------------
+# seeds: the first of 900, 901, ... for which every probability of every step of the RESTATEMENT is >= 1e-3 off the threshold (the
+# rule of golden/gen_golden_bev_head.py; oracle() asserts it), so that the thresholded maps can be compared for equality
+SEEDS = {'seg3_kc1': 900, 'seg3_kc6': 901, 'seg3_kc8': 902, 'seg3_kc9': 902, 'seg3_kc32': 902, 'prescale_05': 901, 'prescale_2_kc9': 901,
+         'prescale_3': 901, 'one_row': 904, 'prescale_09_w10': 900, 'seg3_prescale_07': 901, 'one_row_head_grid': 900}
+
+
+def case(name, **kw):
+    c = dict(name=name, h=12, w=10, feat_channels=256, timesteps=3, randsteps=1, bit_scale=0.01, num_layers=2, seg_gain=16.0,
+             seed=SEEDS.get(name, 900), input_scope=[[-51.2, 51.2, 1.0]] * 2, output_scope=[[-50, 50, 100.0 / 14], [-50, 50, 100.0 / 11]])
+    c.update(kw)
+    return c
+
+
+ORACLE_CASES = {c['name']: c for c in [
+    case('seg3_kc1', seg_conv_kernel=3, num_classes=1, randsteps=2),
+    case('seg3_kc6', seg_conv_kernel=3, num_classes=6),
+    case('seg3_kc8', seg_conv_kernel=3, num_classes=8),
+    case('seg3_kc9', seg_conv_kernel=3, num_classes=9, randsteps=2),
+    case('seg3_kc32', seg_conv_kernel=3, num_classes=32),
+    case('prescale_05', prescale_factor=0.5),
+    case('prescale_2_kc9', prescale_factor=2, num_classes=9),
+    case('prescale_3', prescale_factor=3, randsteps=2),
+    case('one_row', h=1, w=11, prescale_factor=2, seg_conv_kernel=3),
+    # a factor float32 cannot hold: floor(10 * 0.9) = 9 in F.interpolate's double arithmetic, 8 with float32(0.9)
+    case('prescale_09_w10', prescale_factor=0.9),
+    case('seg3_prescale_07', prescale_factor=0.7, seg_conv_kernel=3, h=10, w=10, randsteps=2),
+    case('one_row_head_grid', seg_conv_kernel=3, prescale_factor=1.5, output_scope=[[-50, 50, 100.0], [-50, 50, 100.0 / 13]]),
+]}
+ORACLE_REF = {}
+
+
+def oracle(c, B=1):
+    """-> (state dict, x, noise, the restatement's output) of an oracle-driven case, once per (case, B) and process;
+    ORACLE_REF[(name, 1)][4] is the per-step trace of the single-image run"""
+    if (c['name'], B) not in ORACLE_REF:
+        sd = state_dict_of(c)
+        x, noise = synthetic.make_inputs(B, c['h'], c['w'], c['randsteps'], c['feat_channels'], 256, seed=c['seed'])
+        traces = [[] for _ in range(B)]
+        with torch.no_grad():
+            ref = torch.cat([sample(x[b:b + 1], noise[b], sd, c, traces[b])[0] for b in range(B)])
+        if B == 1 and c['name'] in SEEDS:
+            assert min(t['margin'] for t in traces[0]) >= 1e-3, (c['name'], 'seed does not keep the probabilities off the threshold')
+        ORACLE_REF[(c['name'], B)] = (sd, x, noise, ref, traces[0])
+    return ORACLE_REF[(c['name'], B)][:4]

@@ -35,6 +35,7 @@ import torch
 
 import config_space_cases as CS
 from oracle import ddp_oracle as O
+from support import max_rel64 as max_rel, round256  # noqa: F401  (the float64 measure: P.max_rel at every call site)
 
 REL = CS.REL
 COND = CS.COND
@@ -211,13 +212,28 @@ def rows(c, kind):
     return r
 
 
-def max_rel(a, b):
-    """the parity measure of tests/test_hip_parity.py: largest absolute difference over the largest magnitude of the expectation"""
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max())
+def routes(c):
+    """(id, gemm, flags): both engines and every flag that selects another route for the case"""
+    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False)),
+         ('unfused-prologue', 'bf16x3', dict(fused_prologue=False))]
+    if c['sampler'] == 'ddim':
+        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
+        if c['r'] == 1:
+            v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
+    else:
+        v += [('chain', 'bf16x3', dict(ddpm_chain=True)), ('chain-unfused-tail', 'bf16x3', dict(ddpm_chain=True, fused_tail=False)),
+              ('chain-sb-head', 'bf16x3', dict(ddpm_chain=True, nchw_head=False))]
+    return v
 
 
-def round256(n):
-    return (n + 255) // 256 * 256
+def rel_live(got, want, rows):
+    """max-rel over the classes the rows leave in (an excluded class's score is -1e30 on both sides: it would be the whole scale)"""
+    live = clamp(rows) > -CLAMP                                            # (B, Kc)
+    if not bool(live.any()):
+        live = torch.ones_like(live)
+    m = live[:, :, None, None].expand_as(want)
+    d = (got.double() - want.double()).abs()[m].max()
+    return float(d / want.double()[m].abs().max())
 
 
 def prior_bytes(c):

@@ -27,9 +27,10 @@ import torch
 
 from ddp_amd import _lib, schedule
 from ddp_amd.utils import synthetic
+from golden_util import max_rel
 from oracle import ddp_oracle as O
+from support import REL  # noqa: F401  (the bar of every parity test against the fp32 reference)
 
-REL = 2e-4              # tests/test_hip_parity.py:24 - the bar of every parity test against the fp32 reference
 COND = REL / 20         # the fp32 oracle must sit this close to its own fp64 evaluation for REL to apply unchanged
 BEV_FUSED_UNFUSED = 5e-5   # tests/test_hip_parity.py::test_fused_and_unfused_step_boundary_depth_bev (the same regrouping)
 
@@ -270,3 +271,66 @@ def steps_of(c):
         for k, v in r.items():
             setattr(steps[i], k, v)
     return steps
+
+
+# every caller-visible buffer of the workspace tail in one engine, at the smallest shape where every rounding matters
+# (tests/test_workspace_regions_gpu.py; a target of tests/workspace_history_cases.py)
+REGION_SHAPE = dict(B=2, r=2, h=3, w=5, K=2, L=1)
+REGION_CASES = {'seg': dict(CASES['seg_L12'], name='regions_seg', Kc=19, **REGION_SHAPE),
+                'depth': dict(CASES['depth_K1'], name='regions_depth', **REGION_SHAPE)}
+
+
+# ---- what the GPU files of the sweep share (tests/test_config_space_gpu.py and the files that borrow its routes) ---------------
+def variants(c):
+    """(id, gemm, flags) of the case: both engines, and every diagnostic flag that selects another route for the configuration
+    (flags act on the bf16x3 engine only; include/ddp_mi355x.h:66-92)"""
+    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False))]
+    seg_ddim = c['task'] == 'seg' and c['sampler'] == 'ddim'
+    if c['task'] == 'seg' and c['sampler'] == 'ddpm':           # (no tail kernels on the DDPM path: the step prologue is the only other switch)
+        v.append(('unfused-prologue', 'bf16x3', dict(fused_prologue=False)))
+    if seg_ddim or (c['task'] == 'depth' and not c['n_bins']) or (c['task'] == 'bev' and c['Kc'] <= 8):
+        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
+        v.append(('unfused-prologue', 'bf16x3', dict(fused_prologue=False)))
+    if c['task'] == 'depth' and c['n_bins']:
+        v.append(('unfused-prologue', 'bf16x3', dict(fused_prologue=False)))
+    if seg_ddim and c['Cx'] == 256 and c['r'] == 1:
+        v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
+    return v
+
+
+def check_against_oracle(c, out, label):
+    ref = oracle_batch(c)
+    assert out.shape == ref.shape, (out.shape, ref.shape)
+    assert torch.isfinite(out).all(), f'{label}: non-finite output'
+    errs = [max_rel(out[b:b + 1], ref[b:b + 1]) for b in range(c['B'])]
+    d, dr = decisions(c, out), decisions(c, ref)
+    agree = 1.0 if d is None else float((d == dr).float().mean())
+    print(f'CONFIG-SPACE {c["family"]} {label}: max-rel per image {" ".join(f"{e:.3e}" for e in errs)} (bar {REL:.0e}), '
+          f'decisions equal {agree:.4f}')
+    assert max(errs) < REL and agree > 0.999
+    return max(errs)
+
+
+def expected_launches(path, K, L):
+    """Launch counts per tag a path implies, from the launch sites (csrc/ddp_api.hip sample_* / encoder_forward, the prof_begin
+    calls of csrc/ddp_gemm_bf16.hip and csrc/ddp_layer_tail.hip).  Tags: 1 x-projection GEMM (256 outputs, TAG_XPROJ), 2 step
+    prologue / first head from NCHW (k_layer MODE 2 / 7) and the concat-conv GEMM to SB, 3 layer-0 projection kernel (k_layer
+    MODE 3), 7 a plain layer kernel, 8 head GEMMs / seg tails - and EVERY launch_b3_linear of <= 160 outputs or of 256 outputs
+    with a tag other than 1 / 3 (launch_b3_linear's dispatch), 10 last layer + tail (k_layer MODE 6 / 8 / 9)."""
+    return {
+        # xproj hoist; u_0 = W_m . noise is a 256-output GEMM tagged TAG_FEAT, which launch_b3_linear records under 8; layer 0's
+        # projections (MODE 3) every step: the BEV head follows a grid resampling
+        'bev_chain': {1: 1, 2: 0, 3: K, 7: K * (L - 1), 8: 1, 10: K},
+        # the concat-conv GEMM of every step carries TAG_XPROJ; conv_seg is a head GEMM
+        'bev_separate': {1: 1 + K, 2: 0, 3: K, 7: K * L, 8: K, 10: 0},
+        'seg_head7': {1: 0, 2: 1, 3: 0, 7: K * (L - 1), 8: 0, 10: K},
+        'seg_prologue': {1: 1, 2: 1, 3: 0, 7: K * (L - 1), 8: 0, 10: K},
+        # once per sample: xproj, rvpad (MODE 3 on xproj), rs0 (96 outputs: recorded under 8); layer 0 is MODE 10 under tag 7
+        'depth_chain': {1: 1, 2: 0, 3: 1, 7: K * (L - 1), 8: 1, 10: K},
+        'depth_lt': {1: 1, 2: 0, 3: K, 7: K * (L - 1), 8: 0, 10: K},
+        'depth_bins': {1: 1, 2: 0, 3: K, 7: K * L, 8: K, 10: 0},
+        # DDP_FLAG_UNFUSED_TAIL
+        'seg_unfused_tail_head7': {1: 0, 2: 1, 3: 0, 7: K * L, 8: K, 10: 0},
+        'seg_unfused_tail_prologue': {1: 1, 2: 1, 3: 0, 7: K * L, 8: K, 10: 0},
+        'depth_unfused_tail': {1: 1, 2: 0, 3: K, 7: K * L, 8: K, 10: 0},
+    }[path]

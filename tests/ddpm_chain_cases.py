@@ -21,6 +21,7 @@ import torch
 
 import config_space_cases as S
 from ddp_amd import _lib, schedule
+from golden_util import max_rel
 from oracle import ddp_oracle as O
 
 REL, COND = S.REL, S.COND
@@ -115,3 +116,16 @@ def oracle_batch(c, dtype=torch.float32):
                                               sample_range0=c['sample_range0'], accumulation=c['accumulation']))
         _ORACLE[key] = torch.cat(outs, dim=0)
     return _ORACLE[key]
+
+
+# ---- what the GPU file shares with tests/workspace_history_cases.py -----------------------------------------------------------------
+VIDS = {'chain': {}, 'chain-unfused-tail': dict(fused_tail=False)}
+
+
+def check_against_oracle(c, out, label):
+    ref = oracle_batch(c)
+    assert out.shape == ref.shape and torch.isfinite(out).all(), label
+    errs = [max_rel(out[b:b + 1], ref[b:b + 1]) for b in range(c['B'])]
+    agree = float((out.argmax(1) == ref.argmax(1)).float().mean())
+    print(f'DDPM-CHAIN {label}: max-rel per image {" ".join(f"{e:.3e}" for e in errs)} (bar {REL:.0e}), decisions equal {agree:.4f}')
+    assert max(errs) < REL and agree > 0.999

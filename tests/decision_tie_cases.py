@@ -35,7 +35,7 @@ from config_space_cases import COND, REL  # noqa: F401  (the suite bar and the c
 from ddp_amd.utils import synthetic
 from next_rows_cases import MARGIN, TIE_SHARE  # noqa: F401
 from oracle import ddp_oracle as O
-from test_hip_parity import VARIANTS as PARITY_VARIANTS
+from support import VARIANTS as PARITY_VARIANTS
 
 OTHERS = -64.0            # added to the bias of every class outside the tie set
 MIN_GAP = 16.0            # every other class sits at least this far under the level (host condition; far beyond any rounding)

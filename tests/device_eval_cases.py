@@ -9,6 +9,7 @@ pixels), a head that is not 16-byte aligned, two maps that disagree in alignment
 import functools
 
 import numpy as np
+import torch
 
 BINS = 256
 SEG_TILE, DEPTH_TILE, BEV_TILE = 8192, 1024, 2048
@@ -308,3 +309,35 @@ def bev_expect(prob, gt, thresholds):
     pred = prob.reshape(K, -1)[:, :, None] >= np.asarray(thresholds, dtype=np.float32)
     label = (gt.reshape(K, -1) != 0)[:, :, None]
     return np.stack([(pred & label).sum(1), (pred & ~label).sum(1), (~pred & label).sum(1)], axis=-1).astype(np.int64)
+
+
+# ---- what the two GPU files share (tests/test_device_eval_gpu.py, tests/test_confusion_gpu.py) -----------------------------------
+GUARD = 64           # elements on either side of every output buffer a guarded test hands to the libraries
+
+
+def flat_at(arr, off, dtype):
+    """``arr`` on the device, ``off`` bytes into a 256-byte aligned allocation"""
+    t = torch.from_numpy(np.ascontiguousarray(arr)).reshape(-1)
+    buf = torch.empty(off + t.numel() * t.element_size() + 16, dtype=torch.uint8, device='cuda')
+    assert buf.data_ptr() % 256 == 0
+    view = buf[off:off + t.numel() * t.element_size()].view(dtype).reshape(arr.shape)
+    view.copy_(torch.from_numpy(np.ascontiguousarray(arr)))
+    return view
+
+
+def seg_dev(case):
+    offs = case.get('offsets') or [(0, 0)] * len(case['preds'])
+    P = [flat_at(p, o[0], torch.uint8) for p, o in zip(case['preds'], offs)]
+    L = [flat_at(l, o[1], torch.uint8) for l, o in zip(case['labels'], offs)]
+    return P, L
+
+
+class PerImageBackbone(torch.nn.Module):
+    """stands in for the frozen backbone + neck: the fixture's feature map, once per image of the batch"""
+
+    def __init__(self, x):
+        super().__init__()
+        self.x = x
+
+    def forward(self, img):
+        return [self.x.expand(img.shape[0], -1, -1, -1).contiguous()]

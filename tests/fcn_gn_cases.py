@@ -18,8 +18,8 @@ import torch.nn.functional as F
 from ddp_amd import _lib, schedule
 from ddp_amd.utils import synthetic
 from oracle import ddp_oracle as O
+from support import REL, FcnLoop  # noqa: F401  (REL: the project's bar, restated by test_fcn_gn_host.py::test_bars)
 
-REL = 2e-4                 # the project's bar (tests/test_hip_parity.py), restated by test_fcn_gn_host.py::test_bars
 F32_VS_F64 = 1e-5          # the fp32 expectation against the fp64 one
 MARGIN = 1e-3              # loop cases: smallest top-2 margin, as a share of the largest |score| of the step (5 x REL: a decision
 #                            cannot flip under two scores each REL off)
@@ -375,3 +375,10 @@ def unchanged_path_hashes(dev):
         else:
             out[name] = sha(model.ddim_sample(x.to(dev), noise=dn))
     return out
+
+
+def device_loop(c, sd, dev, batch=None, flags=0):
+    """ddp_prepare_fcn / ddp_sample_fcn through the C ABI on a guarded, exactly sized workspace; the conv array from the state dict"""
+    B = c['B'] if batch is None else batch
+    return FcnLoop(c, sd, dev, B, conv_array(sd, c, dev, prefix='decode_head.'), loop_cfg(c, B, flags), loop_steps(c),
+                   loop_query(_lib.load(), c, B, flags), 'fcn_gn loop')

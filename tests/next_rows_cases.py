@@ -28,6 +28,7 @@ from config_space_cases import COND, REL  # noqa: F401  (the suite bar and the c
 from ddp_amd import _lib, schedule
 from ddp_amd.utils import synthetic
 from oracle import ddp_oracle as O
+from support import FcnLoop, Guarded, assert_guards, finite, stream
 
 STAGE_BYTES = 48 * 1024        # one stage image of the stream GEMM (b3::LYR_STAGE_B, csrc/layer_bf16x3.h)
 MARGIN = 1e-5                  # top-2 margin below which a decision may fall either way (tests/test_hip_parity.py epilogue tests)
@@ -426,3 +427,90 @@ def slide_oracle(c):
 def depth_inputs(c):
     maps = [synthetic.make_depth_map(c['B'], a['h'], a['w'], c['seed'] * 100 + i) for i, a in enumerate(c['augs'])]
     return maps, [a['flip'] for a in c['augs']]
+
+
+# ---- device runners: the workspace-taking entries through the C ABI, each on a guarded workspace of exactly the queried size ------
+# (tests/test_next_rows_gpu.py; tests/test_workspace_history_gpu.py runs the same entries under other workspace histories)
+NECK_DEV = {}
+
+
+def neck_dev(c, dev):
+    """device copies of a neck case's weights and inputs (made once per case)"""
+    if c['name'] not in NECK_DEV:
+        NECK_DEV.clear()                     # one case at a time: tiles_gt_cus and swin_l hold tens of MB
+        sdf = {k: v.to(dev).contiguous() for k, v in fpn_state(c).items()}
+        sdm = {k: v.to(dev).contiguous() for k, v in msm_state(c).items()}
+        sdm['w'] = sdm['down.conv.weight'].reshape(256, 1024).contiguous()
+        NECK_DEV[c['name']] = (sdf, sdm, [t.to(dev) for t in backbone_levels(c)],
+                               [t.to(dev) for t in fpn_like_levels(c)] if c['msm'] else None)
+    return NECK_DEV[c['name']]
+
+
+def images(ts, b):
+    return ts if b is None else [t[b:b + 1].contiguous() for t in ts]
+
+
+def run_fpn(c, dev, sdf, xs, flags=0, g=None, what=''):
+    """ddp_neck_fpn on a guarded workspace of exactly the queried size -> (four NCHW outputs, the workspace)"""
+    lib = _lib.load()
+    B = xs[0].shape[0]
+    lv = fpn_level_structs(c, sdf)
+    g = g or Guarded(neck_queries(lib, c, B)[0], dev)
+    outs = [torch.full((B, 256, h, w), float('nan'), device=dev) for h, w in c['levels']]
+    pin = (C.c_void_p * 4)(*[x.data_ptr() for x in xs])
+    pout = (C.c_void_p * 4)(*[o.data_ptr() for o in outs])
+    _lib.check(lib.ddp_neck_fpn(lv, B, pin, pout, flags, g.ptr(), stream(dev)), lib)
+    torch.cuda.synchronize()
+    assert_guards(g, f'fpn {c["name"]} {what}')
+    for l, o in enumerate(outs):
+        finite(o, f'fpn {c["name"]} level {l} {what}')
+    return outs, g
+
+
+def run_msm(c, dev, sdm, lvls, align, flags=0, g=None, what=''):
+    lib = _lib.load()
+    B = lvls[0].shape[0]
+    lh, lw = level_sizes(c)
+    g = g or Guarded(neck_queries(lib, c, B)[1], dev)
+    out = torch.full((B, 256) + c['levels'][0], float('nan'), device=dev)
+    ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in lvls])
+    _lib.check(lib.ddp_neck_msm(ptrs, lh, lw, B, sdm['w'].data_ptr(), sdm['down.gn.weight'].data_ptr(), sdm['down.gn.bias'].data_ptr(),
+                                int(align), flags, out.data_ptr(), g.ptr(), stream(dev)), lib)
+    torch.cuda.synchronize()
+    assert_guards(g, f'msm {c["name"]} {what}')
+    finite(out, f'msm {c["name"]} {what}')
+    return out, g
+
+
+def run_chain(c, dev, sdf, sdm, xs, align=False, flags=0, g=None, what=''):
+    lib = _lib.load()
+    B = xs[0].shape[0]
+    lv = fpn_level_structs(c, sdf)
+    g = g or Guarded(neck_queries(lib, c, B)[2], dev)
+    out = torch.full((B, 256) + c['levels'][0], float('nan'), device=dev)
+    pin = (C.c_void_p * 4)(*[x.data_ptr() for x in xs])
+    _lib.check(lib.ddp_neck_fpn_msm(lv, B, pin, sdm['w'].data_ptr(), sdm['down.gn.weight'].data_ptr(), sdm['down.gn.bias'].data_ptr(),
+                                    int(align), flags, out.data_ptr(), g.ptr(), stream(dev)), lib)
+    torch.cuda.synchronize()
+    assert_guards(g, f'chain {c["name"]} {what}')
+    finite(out, f'chain {c["name"]} {what}')
+    return out, g
+
+
+def fcn_head(c, sd, dev):
+    import ddp_amd
+    head = ddp_amd.FCNHeadWithTime(num_convs=c['num_convs'], kernel_size=3, concat_input=False, dilation=c['dilation'], in_channels=256,
+                                   channels=256, num_classes=c['classes'], in_index=0, norm_cfg=dict(type='BN') if c['bn'] else None)
+    head.load_state_dict(sd, strict=True)
+    return head.to(dev).eval()
+
+
+def device_loop(c, dev, gemm='bf16x3', batch=None):
+    """ddp_prepare_fcn / ddp_sample_fcn through the C ABI for a LOOP case (ddp_amd.engine.FcnSamplerEngine fixes 256 feature
+    channels; the C ABI takes any multiple of 32)"""
+    B = c['B'] if batch is None else batch
+    sd = loop_state(c)
+    head = fcn_head(dict(c, maps=1), {k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, dev)
+    loop = FcnLoop(c, sd, dev, B, head.conv_array(), loop_cfg(c, gemm, B), loop_steps(c), loop_query(_lib.load(), c, gemm, B), 'loop')
+    loop.head = head
+    return loop

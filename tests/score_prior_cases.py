@@ -51,8 +51,18 @@ MARGIN = PC.MARGIN
 clamp = PC.clamp
 max_rel = PC.max_rel
 round256 = PC.round256
+routes = PC.routes          # both engines and every flag that selects another route: the class prior's table
 
 CASES = {}
+
+
+def rel_live(got, want, total):
+    """max-rel over the entries the prior leaves in (an excluded entry's score is -1e30 on both sides: it would be the whole scale)"""
+    live = clamp(total) > -CLAMP
+    if not bool(live.any()):                                               # (one class, excluded everywhere: the uniform shift)
+        live = torch.ones_like(live)
+    d = (got.double() - want.double()).abs()[live].max()
+    return float(d / want.double()[live].abs().max())
 
 
 def _add(name, soft, excl, both=None, **kw):

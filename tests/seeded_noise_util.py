@@ -7,6 +7,7 @@ Philox4x32-10 (Salmon et al., SC'11) in uint64 arithmetic, Box-Muller in fp64 on
 import numpy as np
 
 import config_space_cases as S
+from support import round256
 
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 W0, W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
@@ -98,10 +99,6 @@ def cm_of(c):
 
 def per_image(c):
     return c['r'] * cm_of(c) * c['h'] * c['w']
-
-
-def round256(n):
-    return (n + 255) // 256 * 256
 
 
 def noise_bytes(c):

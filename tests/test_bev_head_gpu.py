@@ -5,53 +5,32 @@ map, batches, hipGraph replay), and the route of each case read from the library
 
 Every engine of this file samples through a workspace with 4 KiB guards, filled with a NaN pattern (as
 tests/test_config_space_gpu.py): a carve() that undersizes a new buffer, or a kernel that reads bytes nobody wrote, shows."""
-import ctypes as C
-
 import pytest
 import torch
 
 import ddp_amd  # noqa: F401
-from ddp_amd import _lib, schedule
+from ddp_amd import schedule
 from ddp_amd.bev.ddp import DDP as BEVDDP, BEVDeformableHeadWithTime
 from ddp_amd.engine import DDPEngine
 from ddp_amd.utils import synthetic
 import bev_head_util as U
 from golden_util import max_rel
+from support import REL, assert_guards, guard, launch_counts
 
 pytestmark = pytest.mark.gpu
-REL = 2e-4                   # tests/test_hip_parity.py: the project's bar against the fp32 reference
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
-
 VARIANTS = {'bf16x3': ('bf16x3', {}), 'f32': ('f32', {}), 'unfused_tail': ('bf16x3', dict(fused_tail=False)),
             'unfused_layer': ('bf16x3', dict(fused_layer=False)), 'gather_guess_zero': ('bf16x3', dict(gather_guess_zero=True))}
 
 
-def _guard(eng):
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=eng.device)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    assert eng.workspace.data_ptr() % 256 == 0
-    return eng
-
-
-def _assert_guards(eng, what):
-    bits = eng.guarded.view(torch.int32)
-    bad_f, bad_b = int((bits[:GUARD] != PATTERN).sum()), int((bits[-GUARD:] != PATTERN).sum())
-    assert bad_f == 0 and bad_b == 0, f'{what}: {bad_f} words written in front of the workspace, {bad_b} behind it'
-
-
 def _engine(cfg, sd, gemm='bf16x3', batch=1, **flags):
-    return _guard(DDPEngine(sd, 'bev', gemm=gemm, **flags, **U.engine_kwargs(cfg, batch)))
+    return guard(DDPEngine(sd, 'bev', gemm=gemm, **flags, **U.engine_kwargs(cfg, batch)))
 
 
 def _sample(cfg, sd, x, noise, gemm='bf16x3', **flags):
     eng = _engine(cfg, sd, gemm, batch=x.shape[0], **flags)
     out = eng.sample(x.cuda().contiguous(), noise.cuda().contiguous())
     torch.cuda.synchronize()
-    _assert_guards(eng, cfg.get('name'))
+    assert_guards(eng, cfg.get('name'))
     return out.cpu()
 
 
@@ -78,7 +57,7 @@ def _step_probs(cfg, sd, x, masks, s, gemm):
         setattr(eng.steps[0], k, v)
     out = eng.sample(x.repeat(r, 1, 1, 1).cuda().contiguous(), masks.unsqueeze(1).cuda().contiguous())
     torch.cuda.synchronize()
-    _assert_guards(eng, cfg.get('name'))
+    assert_guards(eng, cfg.get('name'))
     return out.cpu()
 
 
@@ -127,11 +106,11 @@ def test_plugin_sampler_matches_reference(name):
 def test_head_forward_matches_reference(gemm):
     cfg, sd, feat, _, g = U.load('head_forward')
     _, head = _plugin(cfg, sd)
-    eng = _guard(DDPEngine(head._state_for_engine(), 'bev', h=cfg['h'], w=cfg['w'], batch=cfg['R'], timesteps=1, gemm=gemm,
-                           **head._engine_kwargs()))
+    eng = guard(DDPEngine(head._state_for_engine(), 'bev', h=cfg['h'], w=cfg['w'], batch=cfg['R'], timesteps=1, gemm=gemm,
+                          **head._engine_kwargs()))
     out = eng.head_forward(feat.cuda().contiguous(), g['temb'].cuda())
     torch.cuda.synchronize()
-    _assert_guards(eng, 'head_forward')
+    assert_guards(eng, 'head_forward')
     assert out.shape == g['out'].shape
     assert max_rel(out.cpu(), g['out']) < REL, gemm
     if gemm == 'bf16x3':        # the module's own forward (the plugin surface of the head)
@@ -139,7 +118,7 @@ def test_head_forward_matches_reference(gemm):
 
 
 def test_head_forward_with_prescale_matches_restatement():
-    cfg = _case('hf_prescale', prescale_factor=1.5, h=13, w=9, seg_conv_kernel=3)
+    cfg = U.case('hf_prescale', prescale_factor=1.5, h=13, w=9, seg_conv_kernel=3)
     sd = U.state_dict_of(cfg)
     feat, _ = synthetic.make_inputs(2, 13, 9, 1, 256, 256, seed=cfg['seed'])
     from oracle import ddp_oracle as O
@@ -151,59 +130,15 @@ def test_head_forward_with_prescale_matches_restatement():
     assert max_rel(out, ref) < REL
 
 
-# ---- oracle-driven cases beyond the fixtures ------------------------------------------------------------------------------------
-# seeds: the first of 900, 901, ... for which every probability of every step of the RESTATEMENT is >= 1e-3 off the threshold (the
-# rule of golden/gen_golden_bev_head.py; _oracle asserts it), so that the thresholded maps can be compared for equality
-SEEDS = {'seg3_kc1': 900, 'seg3_kc6': 901, 'seg3_kc8': 902, 'seg3_kc9': 902, 'seg3_kc32': 902, 'prescale_05': 901, 'prescale_2_kc9': 901,
-         'prescale_3': 901, 'one_row': 904, 'prescale_09_w10': 900, 'seg3_prescale_07': 901, 'one_row_head_grid': 900}
-
-
-def _case(name, **kw):
-    c = dict(name=name, h=12, w=10, feat_channels=256, timesteps=3, randsteps=1, bit_scale=0.01, num_layers=2, seg_gain=16.0,
-             seed=SEEDS.get(name, 900), input_scope=[[-51.2, 51.2, 1.0]] * 2, output_scope=[[-50, 50, 100.0 / 14], [-50, 50, 100.0 / 11]])
-    c.update(kw)
-    return c
-
-
-ORACLE_CASES = {c['name']: c for c in [
-    _case('seg3_kc1', seg_conv_kernel=3, num_classes=1, randsteps=2),
-    _case('seg3_kc6', seg_conv_kernel=3, num_classes=6),
-    _case('seg3_kc8', seg_conv_kernel=3, num_classes=8),
-    _case('seg3_kc9', seg_conv_kernel=3, num_classes=9, randsteps=2),
-    _case('seg3_kc32', seg_conv_kernel=3, num_classes=32),
-    _case('prescale_05', prescale_factor=0.5),
-    _case('prescale_2_kc9', prescale_factor=2, num_classes=9),
-    _case('prescale_3', prescale_factor=3, randsteps=2),
-    _case('one_row', h=1, w=11, prescale_factor=2, seg_conv_kernel=3),
-    # a factor float32 cannot hold: floor(10 * 0.9) = 9 in F.interpolate's double arithmetic, 8 with float32(0.9)
-    _case('prescale_09_w10', prescale_factor=0.9),
-    _case('seg3_prescale_07', prescale_factor=0.7, seg_conv_kernel=3, h=10, w=10, randsteps=2),
-    _case('one_row_head_grid', seg_conv_kernel=3, prescale_factor=1.5, output_scope=[[-50, 50, 100.0], [-50, 50, 100.0 / 13]]),
-]}
-_REF = {}
-
-
-def _oracle(c, B=1):
-    if (c['name'], B) not in _REF:
-        sd = U.state_dict_of(c)
-        x, noise = synthetic.make_inputs(B, c['h'], c['w'], c['randsteps'], c['feat_channels'], 256, seed=c['seed'])
-        traces = [[] for _ in range(B)]
-        with torch.no_grad():
-            ref = torch.cat([U.sample(x[b:b + 1], noise[b], sd, c, traces[b])[0] for b in range(B)])
-        if B == 1 and c['name'] in SEEDS:
-            assert min(t['margin'] for t in traces[0]) >= 1e-3, (c['name'], 'seed does not keep the probabilities off the threshold')
-        _REF[(c['name'], B)] = (sd, x, noise, ref, traces[0])
-    return _REF[(c['name'], B)][:4]
-
-
+# ---- oracle-driven cases beyond the fixtures (tests/bev_head_util.py: ORACLE_CASES, oracle) ----------------------------------------
 @pytest.mark.parametrize('gemm', ['bf16x3', 'f32'])
-@pytest.mark.parametrize('name', sorted(ORACLE_CASES))
+@pytest.mark.parametrize('name', sorted(U.ORACLE_CASES))
 def test_every_step_thresholded_maps_equal_the_restatement(name, gemm):
     """as test_every_step_thresholded_maps_equal_the_reference, on the cases beyond the fixtures: every step, every noise replica,
     torch.equal against the restatement's thresholded maps (seeds chosen by the generator's margin rule)"""
-    c = ORACLE_CASES[name]
-    sd, x, _, _ = _oracle(c)
-    trace = _REF[(name, 1)][4]
+    c = U.ORACLE_CASES[name]
+    sd, x, _, _ = U.oracle(c)
+    trace = U.ORACLE_REF[(name, 1)][4]
     _assert_every_step_thresholds_equal(c, sd, x, trace, [t['prob'] for t in trace], gemm)
 
 
@@ -214,10 +149,10 @@ def _oracle_variants(c):
     return v
 
 
-@pytest.mark.parametrize('name,variant', [(n, v) for n, c in ORACLE_CASES.items() for v in _oracle_variants(c)])
+@pytest.mark.parametrize('name,variant', [(n, v) for n, c in U.ORACLE_CASES.items() for v in _oracle_variants(c)])
 def test_case_matches_restatement(name, variant):
-    c = ORACLE_CASES[name]
-    sd, x, noise, ref = _oracle(c)
+    c = U.ORACLE_CASES[name]
+    sd, x, noise, ref = U.oracle(c)
     gemm, flags = VARIANTS[variant]
     out = _sample(c, sd, x, noise, gemm, **flags)
     assert out.shape == ref.shape and torch.isfinite(out).all()
@@ -229,8 +164,8 @@ def test_case_matches_restatement(name, variant):
 
 @pytest.mark.parametrize('name', ['seg3_kc6', 'seg3_kc9', 'prescale_3', 'one_row'])
 def test_batch_of_two_equals_two_independent_runs(name):
-    c = ORACLE_CASES[name]
-    sd, x, noise, ref = _oracle(c, B=2)
+    c = U.ORACLE_CASES[name]
+    sd, x, noise, ref = U.oracle(c, B=2)
     out = _sample(c, sd, x, noise)
     assert max_rel(out, ref) < REL
     for b in range(2):
@@ -240,22 +175,22 @@ def test_batch_of_two_equals_two_independent_runs(name):
 
 @pytest.mark.parametrize('name', ['seg3_kc6', 'seg3_kc9', 'prescale_05', 'one_row'])
 def test_graph_replay_is_bit_identical(name):
-    c = ORACLE_CASES[name]
-    sd, x, noise, _ = _oracle(c)
+    c = U.ORACLE_CASES[name]
+    sd, x, noise, _ = U.oracle(c)
     eng = _engine(c, sd)
     xb, nb = x.cuda().contiguous(), noise.cuda().contiguous()
     out = eng.sample(xb, nb).clone()
     g = eng.capture(xb, nb)
     rep = g.replay().clone()
     torch.cuda.synchronize()
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
     assert torch.equal(rep, out)
 
 
 def test_packed_weights_of_the_wrong_kernel_are_refused():
     """a pre-packed 1x1 conv_seg with bev_seg_kernel = 3 (the library would read 9x the tensor) and the other way round"""
     from ddp_amd.engine import PackedWeights
-    c = ORACLE_CASES['seg3_kc6']
+    c = U.ORACLE_CASES['seg3_kc6']
     for packed_k, asked_k in ((1, 3), (3, 1)):
         sd = U.state_dict_of(dict(c, seg_conv_kernel=packed_k))
         pw = PackedWeights(sd, 'bev', c['num_layers'], torch.device('cuda:0'))
@@ -281,32 +216,13 @@ def test_one_sampler_with_two_heads_that_differ_in_prescale_only():
 def test_chain_and_separate_kernels_agree_with_the_3x3_head():
     """the u chain around the 3x3 head against DDP_FLAG_UNFUSED_TAIL's launches: the same operators regrouped (the bar of
     tests/config_space_cases.py for that pair, 5e-5)"""
-    c = ORACLE_CASES['seg3_kc8']
-    sd, x, noise, _ = _oracle(c)
+    c = U.ORACLE_CASES['seg3_kc8']
+    sd, x, noise, _ = U.oracle(c)
     a, b = _sample(c, sd, x, noise), _sample(c, sd, x, noise, fused_tail=False)
     assert max_rel(a, b) < 5e-5
 
 
 # ---- routes, from the library's launch records ----------------------------------------------------------------------------------
-def _launch_counts(eng, x, noise):
-    lib = eng.lib
-    eng.prepare()
-    torch.cuda.synchronize()
-    ms, n = C.c_float(0), C.c_int(0)
-    _lib.check(lib.ddp_profile_begin(255), lib)
-    try:
-        eng.sample(x, noise)
-        torch.cuda.synchronize()
-    finally:
-        rc = lib.ddp_profile_end(C.byref(ms), C.byref(n))
-    _lib.check(rc, lib)
-    counts = {}
-    for tag in range(11):
-        _lib.check(lib.ddp_profile_read(tag, C.byref(ms), C.byref(n)), lib)
-        counts[tag] = n.value
-    return counts
-
-
 def _expected(route, K, L):
     """tags as tests/test_config_space_gpu.py::_expected: 1 x-projection / concat-conv GEMM, 3 layer-0 projection kernel, 7 a plain
     layer kernel, 8 head launches (and the u_0 GEMM of the chain), 10 last layer + tail (k_layer MODE 8).  The 3x3 head records TWO
@@ -324,28 +240,28 @@ def _expected(route, K, L):
     ('prescale_05', dict(fused_tail=False), 'separate')])
 def test_route_witness(name, flags, route):
     """k_bev_seg3 present and MODE 8 absent with the 3x3 head; MODE 8 present without it"""
-    c = ORACLE_CASES[name]
-    sd, x, noise, _ = _oracle(c)
+    c = U.ORACLE_CASES[name]
+    sd, x, noise, _ = U.oracle(c)
     eng = _engine(c, sd, **flags)
-    got = _launch_counts(eng, x.cuda().contiguous(), noise.cuda().contiguous())
-    _assert_guards(eng, name)
+    got = launch_counts(eng, x.cuda().contiguous(), noise.cuda().contiguous())
+    assert_guards(eng, name)
     want = _expected(route, c['timesteps'], c['num_layers'])
     print(f'BEV-HEAD witness {name} ({route}): {got}')
     assert {t: got[t] for t in want} == want, (route, got)
 
 
 def test_f32_engine_runs_seg3_once_per_step():
-    c = ORACLE_CASES['seg3_kc6']
-    sd, x, noise, _ = _oracle(c)
-    got = _launch_counts(_engine(c, sd, 'f32'), x.cuda().contiguous(), noise.cuda().contiguous())
+    c = U.ORACLE_CASES['seg3_kc6']
+    sd, x, noise, _ = U.oracle(c)
+    got = launch_counts(_engine(c, sd, 'f32'), x.cuda().contiguous(), noise.cuda().contiguous())
     assert got[10] == 0 and got[2] == 0 and got[8] == c['timesteps'], got     # (the nine shifted GEMMs carry no tag; k_bev_seg3 does)
 
 
 def test_plain_configs_launch_what_they_launched():
     """a 1x1 head without prescale: the launch records of the u chain and of the separate kernels, as before ABI 7"""
     for kc, route in ((6, 'chain'), (9, 'separate')):
-        c = _case(f'plain_kc{kc}', num_classes=kc)
-        sd, x, noise, _ = _oracle(c)
-        got = _launch_counts(_engine(c, sd), x.cuda().contiguous(), noise.cuda().contiguous())
+        c = U.case(f'plain_kc{kc}', num_classes=kc)
+        sd, x, noise, _ = U.oracle(c)
+        got = launch_counts(_engine(c, sd), x.cuda().contiguous(), noise.cuda().contiguous())
         want = _expected(route, c['timesteps'], c['num_layers'])
         assert {t: got[t] for t in want} == want, (route, got)

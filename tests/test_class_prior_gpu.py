@@ -27,65 +27,21 @@ import torch
 
 import class_prior_cases as P
 import config_space_cases as S
+import support
 from ddp_amd import _lib
-from test_hip_parity import REL
+from support import REL, dev, guards_ok as _guards_ok  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def routes(c):
-    """(id, gemm, flags): both engines and every flag that selects another route for the case"""
-    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False)),
-         ('unfused-prologue', 'bf16x3', dict(fused_prologue=False))]
-    if c['sampler'] == 'ddim':
-        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
-        if c['r'] == 1:
-            v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
-    else:
-        v += [('chain', 'bf16x3', dict(ddpm_chain=True)), ('chain-unfused-tail', 'bf16x3', dict(ddpm_chain=True, fused_tail=False)),
-              ('chain-sb-head', 'bf16x3', dict(ddpm_chain=True, nchw_head=False))]
-    return v
-
-
-ROUTES = {(n, vid): (gemm, fl) for n, c in P.CASES.items() for vid, gemm, fl in routes(c)}
-_SD, _IN = {}, {}
-
-
-def _state(c, dev):
-    if c['name'] not in _SD:
-        _SD[c['name']] = S.state_dict(c)
-        _IN[c['name']] = tuple(None if t is None else t.to(dev) for t in S.inputs(c))
-    return _SD[c['name']], _IN[c['name']]
+ROUTES = {(n, vid): (gemm, fl) for n, c in P.CASES.items() for vid, gemm, fl in P.routes(c)}
+_state = support.state_cache(S.state_dict, S.inputs)
 
 
 def _engine(c, dev, gemm='bf16x3', batch=None, sd=None, **kw):
     """DDPEngine of the (seeded) case on a guarded, NaN-patterned workspace.  The table of a class_prior engine holds the PATTERN
     afterwards (a NaN: it reads as 0); the caller sets or clears it, as the library's contract says."""
-    from ddp_amd.engine import DDPEngine
-    ekw = S.engine_kwargs(c)
-    if batch is not None:
-        ekw['batch'] = batch
-    eng = DDPEngine(sd if sd is not None else _state(c, dev)[0], 'seg', device=dev, gemm=gemm, **kw, **ekw)
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    return eng
-
-
-def _guards_ok(eng):
-    bits = eng.guarded.view(torch.int32)
-    return int((bits[:GUARD] != PATTERN).sum()) == 0 and int((bits[-GUARD:] != PATTERN).sum()) == 0
+    return support.engine(sd if sd is not None else _state(c, dev)[0], 'seg', S.engine_kwargs(c), dev, gemm, batch, **kw)
 
 
 def _sample(eng, c, dev, rows=None, sl=None, seed=None):
@@ -103,16 +59,6 @@ def _sample(eng, c, dev, rows=None, sl=None, seed=None):
     torch.cuda.synchronize()
     assert _guards_ok(eng), f'{c["name"]}: workspace guards overwritten'
     return out.cpu()
-
-
-def _rel_live(got, want, rows):
-    """max-rel over the classes the rows leave in (an excluded class's score is -1e30 on both sides: it would be the whole scale)"""
-    live = P.clamp(rows) > -P.CLAMP                                        # (B, Kc)
-    if not bool(live.any()):
-        live = torch.ones_like(live)
-    m = live[:, :, None, None].expand_as(want)
-    d = (got.double() - want.double()).abs()[m].max()
-    return float(d / want.double()[m].abs().max())
 
 
 def test_bars():
@@ -147,7 +93,7 @@ def test_output_and_decisions_match_the_expectation(dev, name, vid, kind):
     eng = _engine(c, dev, gemm, class_prior=True, record_steps=True, **fl)
     got = _sample(eng, c, dev, rows)
     rec = eng.step_record().cpu()                                          # (K, B, r, h, w)
-    err = _rel_live(got, e['out'], rows)
+    err = P.rel_live(got, e['out'], rows)
     agree = float((rec == e['record']).float().mean())
     print(f'CLASS-PRIOR {name}[{vid}]/{kind}: max-rel {err:.2e} (bar {REL:.0e}), decisions equal {agree:.4f}')
     assert torch.isfinite(got).all()
@@ -202,7 +148,7 @@ def test_forced_decisions_are_fed_back_and_the_scores_carry_the_prior(dev, vid):
     forced = _engine(c, dev, gemm, class_prior=True, force_x0=True, **fl)
     forced.set_x0_decisions(e['record'].reshape(K, B * r, h, w).to(dev))
     got = _sample(forced, c, dev, rows)
-    assert _rel_live(got, e['out'], rows) < REL
+    assert P.rel_live(got, e['out'], rows) < REL
     assert torch.equal(forced.x0_trace().cpu().view(K, B, r, h, w), e['record'])        # its own argmax, under the prior
     # other decisions fed back: the first step's scores are the same, the later ones move
     other = (e['record'].long() + 1) % c['Kc']
@@ -318,30 +264,8 @@ def test_engine_class_prior_methods(dev):
 
 
 # ---- 8 ------------------------------------------------------------------------------------------------------------------------------
-class _PoolBackbone(torch.nn.Module):
-    """a stand-in backbone whose feature map depends on the image it is given (slide windows, flipped augmentations): the image
-    pooled to (h, w) and spread over 256 channels by a fixed seeded projection"""
-
-    def __init__(self, h, w):
-        super().__init__()
-        self.hw = (h, w)
-        self.register_buffer('proj', torch.randn(256, 3, generator=torch.Generator().manual_seed(17)))
-
-    def forward(self, img):
-        p = torch.nn.functional.adaptive_avg_pool2d(img, self.hw)
-        return [torch.einsum('oc,bchw->bohw', self.proj, p).contiguous()]
-
-
-def _seg_plugin(c, dev, sd):
-    import ddp_amd
-    from test_host_logic import ENCODER, seg_cfg
-    head = dict(seg_cfg()['decode_head'], num_classes=c['Kc'], encoder=dict(ENCODER, num_layers=c['L']))
-    model = ddp_amd.build_segmentor(seg_cfg(timesteps=c['K'], randsteps=c['r'], bit_scale=c['bit_scale'], accumulation=c['accumulation'],
-                                            diffusion=c['sampler'], sample_range=(0, 0.999), time_difference=c['td'], decode_head=head,
-                                            noise_seed=5))
-    model.load_state_dict(sd, strict=True)
-    model = model.to(dev).eval()
-    model.backbone = _PoolBackbone(c['h'], c['w']).to(dev)
+def _plugin(c, dev, sd):
+    model = support.seg_plugin(c, dev, sd, pool_backbone=True, noise_seed=5)
     # ddpm: on the fused step boundary, where - as on the ddim product route - the prior row is the accumulator start of conv_seg and
     # the edited bias gives the same bits (the GEMM routes add the row behind the GEMM: equal to rounding, test 2 bounds them)
     model.ddpm_chain = c['sampler'] == 'ddpm'
@@ -357,7 +281,7 @@ def test_plugin_class_prior_is_the_edited_bias(dev, name, kind):
     row = P.rows(P.CASES[name], kind)[:1]
     edited = dict(sd)
     edited['decode_head.conv_seg.bias'] = sd['decode_head.conv_seg.bias'] + P.clamp(row[0])
-    model, ref = _seg_plugin(c, dev, sd), _seg_plugin(c, dev, edited)
+    model, ref = _plugin(c, dev, sd), _plugin(c, dev, edited)
     g = torch.Generator().manual_seed(23)
     H, W = 4 * c['h'], 4 * c['w']
     img = torch.randn(1, 3, H, W, generator=g).to(dev)
@@ -403,7 +327,7 @@ def test_plugin_class_prior_is_the_edited_bias(dev, name, kind):
 
 def test_plugin_self_aligned_predict_and_fcn_head(dev):
     import ddp_amd
-    from test_host_logic import ENCODER, seg_cfg
+    from support import ENCODER, seg_cfg
     name = 'kc19_7x13_b3'
     c = P.seeded(P.CASES[name], 'soft')
     sd, (x, noise, _) = _state(c, dev)

@@ -17,6 +17,7 @@ import torch
 import class_prior_cases as P
 import config_space_cases as S
 from ddp_amd import _lib
+from support import refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -234,15 +235,6 @@ def test_host_side_places_are_the_headers_formulas():
             assert rc0 == 0 and table_at - P.round256(bb) == total0 - trailing
 
 
-def _refused(lib, cfg, *words):
-    n = C.c_size_t(0)
-    for entry in (lib.ddp_query_workspace, lib.ddp_query_const_workspace):
-        assert entry(C.byref(cfg), C.byref(n)) == -1               # DDP_E_BADCFG
-        msg = lib.ddp_last_error()
-        for w in words:
-            assert w.encode() in msg, msg
-
-
 def test_refusals_carry_their_message():
     import prior_start_cases as PS
     lib = _lib.load()
@@ -251,7 +243,7 @@ def test_refusals_carry_their_message():
     for other in ('depth_9x14', 'depth_1x37_bins', 'bev_kc8_r1', 'bev_kc9_r2'):
         base = S.make_cfg(PS.CASES[other])
         assert S.query(lib, base)[0] == 0
-        _refused(lib, _with(base, _lib.FLAG_CLASS_PRIOR), 'DDP_FLAG_CLASS_PRIOR')
+        refused(lib, _with(base, _lib.FLAG_CLASS_PRIOR), 'DDP_FLAG_CLASS_PRIOR')
     # the FCN loop: workspace query, prepare and sample
     import seeded_noise_util as U
     n = C.c_size_t(0)
@@ -270,8 +262,8 @@ def test_refusals_carry_their_message():
     # bits 8192 and 32768 are still bits nobody defines, and so is every bit above the new one
     for bit in (8192, 32768, 262144, 1 << 19, 1 << 30):
         for extra in (bit, bit | _lib.FLAG_CLASS_PRIOR):
-            _refused(lib, _with(S.make_cfg(seg), extra), 'unknown flags')
-    _refused(lib, _with(S.make_cfg(PS.CASES['depth_9x14']), 262144), 'unknown flags')
+            refused(lib, _with(S.make_cfg(seg), extra), 'unknown flags')
+    refused(lib, _with(S.make_cfg(PS.CASES['depth_9x14']), 262144), 'unknown flags')
     # what combines: every other flag of ddp_sample, 256 classes included
     for name in sorted(P.CASES):
         c = P.seeded(P.CASES[name], 'soft')
@@ -412,7 +404,7 @@ def test_plugin_surface_without_a_device():
 
 def test_fcn_head_segmentor_raises():
     import ddp_amd
-    from test_host_logic import seg_cfg
+    from support import seg_cfg
     head = dict(type='FCNHeadWithTime', in_channels=256, channels=256, in_index=0, num_convs=1, num_classes=19, dropout_ratio=0.,
                 norm_cfg=None, align_corners=False)
     try:

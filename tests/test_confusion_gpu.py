@@ -16,13 +16,13 @@ import device_eval_cases as V
 from ddp_amd import _cm_lib as M
 from ddp_amd import confusion as cf
 from ddp_amd import evaluation as ev
-from test_device_eval_gpu import GUARD, _Backbone, _seg_dev
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'device_eval')
 SEG_NAMES = list(V.seg_cases())
 IN_RANGE_NAMES = list(CC.in_range_cases())
 SENTINEL = -7
+GUARD, _seg_dev, _Backbone = V.GUARD, V.seg_dev, V.PerImageBackbone
 
 
 def _guarded(n_elem):
@@ -251,7 +251,7 @@ def _calculate_confusion_matrix(n, ignore_index, gt_maps, results):
 
 def test_harness_accumulates_the_matrix_of_the_host_path():
     from golden_util import load_case
-    from test_plugin_gpu import _seg_model
+    from support import seg_model as _seg_model
     from ddp_amd import apis
     cfg, sd, x, _, _, _ = load_case('seg_ade_k3')
     model = _seg_model(cfg)

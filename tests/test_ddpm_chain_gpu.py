@@ -2,8 +2,6 @@
 bar, against the flag-clear sampler under teacher forcing, and the route, seeded-noise, graph and step-record properties the header
 states.  Cases: tests/ddpm_chain_cases.py (tests/test_ddpm_chain_host.py shows on the CPU that the oracle is well conditioned on
 each).  Engines sample through guarded, NaN-filled, exactly sized workspaces as in tests/test_config_space_gpu.py."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -11,54 +9,25 @@ import torch
 import config_space_cases as S
 import ddpm_chain_cases as D
 import seeded_noise_util as U
+import support
 from ddp_amd import _lib
 from golden_util import load_case, max_rel
-from test_hip_parity import REL
+from support import REL, assert_guards, dev, fixture_engine, guard, launch_counts, ref_disagreement, seg_model  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
-VIDS = {'chain': {}, 'chain-unfused-tail': dict(fused_tail=False)}
-_SD, _IN, _OUT = {}, {}, {}
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def _state(c):
-    if c['name'] not in _SD:
-        _SD[c['name']] = S.state_dict(c)
-        _IN[c['name']] = S.inputs(c)
-    return _SD[c['name']], _IN[c['name']]
-
-
-def _guard(eng):
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=eng.device)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    assert eng.workspace.data_ptr() % 256 == 0
-    return eng
-
-
-def _assert_guards(eng, what):
-    bits = eng.guarded.view(torch.int32)
-    bad_f, bad_b = int((bits[:GUARD] != PATTERN).sum()), int((bits[-GUARD:] != PATTERN).sum())
-    assert bad_f == 0 and bad_b == 0, f'{what}: {bad_f} words written in front of the workspace, {bad_b} behind it'
+VIDS = D.VIDS
+_OUT = {}
+_state = support.state_cache(S.state_dict, S.inputs)
 
 
 def _engine(c, dev, chain=True, gemm='bf16x3', sampler=None, **flags):
-    from ddp_amd.engine import DDPEngine
     kw = D.engine_kwargs(c)
     if sampler is not None:
         kw['sampler'] = sampler
-    eng = DDPEngine(_state(c)[0], 'seg', device=dev, gemm=gemm, ddpm_chain=chain if kw['sampler'] == 'ddpm' else False, **flags, **kw)
+    eng = support.engine(_state(c)[0], 'seg', kw, dev, gemm, ddpm_chain=chain if kw['sampler'] == 'ddpm' else False, **flags)
     assert bool(eng.cfg.flags & _lib.FLAG_DDPM_CHAIN) == bool(chain and kw['sampler'] == 'ddpm')
-    return _guard(eng)
+    return eng
 
 
 def _dev_inputs(c, dev):
@@ -70,7 +39,7 @@ def _sample(c, dev, chain=True, gemm='bf16x3', **flags):
     eng = _engine(c, dev, chain, gemm, **flags)
     out = eng.sample(*_dev_inputs(c, dev))
     torch.cuda.synchronize()
-    _assert_guards(eng, c['name'])
+    assert_guards(eng, c['name'])
     return out.cpu()
 
 
@@ -78,15 +47,6 @@ def _output(name, vid, dev):
     if (name, vid) not in _OUT:
         _OUT[(name, vid)] = _sample(D.ALL[name], dev, True, **VIDS[vid])
     return _OUT[(name, vid)]
-
-
-def _check_against_oracle(c, out, label):
-    ref = D.oracle_batch(c)
-    assert out.shape == ref.shape and torch.isfinite(out).all(), label
-    errs = [max_rel(out[b:b + 1], ref[b:b + 1]) for b in range(c['B'])]
-    agree = float((out.argmax(1) == ref.argmax(1)).float().mean())
-    print(f'DDPM-CHAIN {label}: max-rel per image {" ".join(f"{e:.3e}" for e in errs)} (bar {REL:.0e}), decisions equal {agree:.4f}')
-    assert max(errs) < REL and agree > 0.999
 
 
 # ---- 1. against the oracle / the reference-made fixture -------------------------------------------------------------------------
@@ -97,7 +57,7 @@ def test_bar_is_the_suite_bar():
 @pytest.mark.parametrize('vid', sorted(VIDS))
 @pytest.mark.parametrize('name', sorted(D.ALL))
 def test_case_matches_oracle(dev, name, vid):
-    _check_against_oracle(D.ALL[name], _output(name, vid, dev), f'{name}[{vid}]')
+    D.check_against_oracle(D.ALL[name], _output(name, vid, dev), f'{name}[{vid}]')
 
 
 @pytest.mark.parametrize('name', sorted(D.ALL))
@@ -108,21 +68,19 @@ def test_fused_and_unfused_tail_same_bits(dev, name):
 
 @pytest.mark.parametrize('vid', sorted(VIDS))
 def test_fixture_through_the_engine(dev, vid):
-    from test_hip_parity import _engine as fixture_engine
     cfg, sd, x, noise, step_noise, g = load_case('seg_ddpm')
-    eng = _guard(fixture_engine(cfg, sd, dev, ddpm_chain=True, **VIDS[vid]))
+    eng = guard(fixture_engine(cfg, sd, dev, ddpm_chain=True, **VIDS[vid]))
     assert eng.cfg.flags & _lib.FLAG_DDPM_CHAIN
     out = eng.sample(x.to(dev), noise.unsqueeze(0).contiguous().to(dev), step_noise.unsqueeze(1).contiguous().to(dev)).cpu()
-    _assert_guards(eng, 'seg_ddpm')
+    assert_guards(eng, 'seg_ddpm')
     err = max_rel(out, g['out'])
     print(f'DDPM-CHAIN fixture seg_ddpm[{vid}]: max-rel {err:.3e} (bar {REL:.0e})')
     assert err < REL
 
 
 def test_fixture_through_the_plugin(dev):
-    from test_plugin_gpu import _seg_model
     cfg, sd, x, noise, step_noise, g = load_case('seg_ddpm')
-    model = _seg_model(cfg)
+    model = seg_model(cfg)
     model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval()
     args = dict(noise=noise.unsqueeze(0).to(dev), step_noise=step_noise.unsqueeze(1).to(dev))
@@ -179,7 +137,7 @@ def test_chain_agrees_with_the_flag_clear_sampler_under_teacher_forcing(dev, nam
         eng.set_x0_decisions(trace)
         outs.append(eng.sample(x, noise, sn).cpu())
         torch.cuda.synchronize()
-        _assert_guards(eng, name)
+        assert_guards(eng, name)
         if not chain:
             assert torch.equal(eng.x0_trace(), trace) and torch.equal(outs[0], free)     # forcing its own decisions changes nothing
     err = max_rel(outs[1], outs[0])
@@ -188,32 +146,13 @@ def test_chain_agrees_with_the_flag_clear_sampler_under_teacher_forcing(dev, nam
 
 
 # ---- 3. route witness -------------------------------------------------------------------------------------------------------------
-def _launch_counts(eng, *args, **kw):
-    lib = eng.lib
-    eng.prepare()
-    torch.cuda.synchronize()
-    ms, n = C.c_float(0), C.c_int(0)
-    _lib.check(lib.ddp_profile_begin(255), lib)
-    try:
-        eng.sample(*args, **kw)
-        torch.cuda.synchronize()
-    finally:
-        rc = lib.ddp_profile_end(C.byref(ms), C.byref(n))
-    _lib.check(rc, lib)
-    counts = {}
-    for tag in range(11):
-        _lib.check(lib.ddp_profile_read(tag, C.byref(ms), C.byref(n)), lib)
-        counts[tag] = n.value
-    return counts
-
-
 @pytest.mark.parametrize('vid', sorted(VIDS))
 @pytest.mark.parametrize('name', sorted(D.ALL))
 def test_route_is_the_ddim_chain_plus_the_prepasses(dev, name, vid):
     c = D.ALL[name]
     x, noise, sn = _dev_inputs(c, dev)
-    got = _launch_counts(_engine(c, dev, True, **VIDS[vid]), x, noise, sn)
-    ddim = _launch_counts(_engine(c, dev, sampler='ddim', **VIDS[vid]), x, noise)
+    got = launch_counts(_engine(c, dev, True, **VIDS[vid]), x, noise, sn)
+    ddim = launch_counts(_engine(c, dev, sampler='ddim', **VIDS[vid]), x, noise)
     print(f'DDPM-CHAIN witness {name}[{vid}]: {got}')
     assert {t: got[t] for t in range(1, 11)} == {t: ddim[t] for t in range(1, 11)}, (got, ddim)
     assert got[0] == D.prepasses(c) == D.NOISE_STEPS[name][0] and ddim[0] == 0
@@ -225,7 +164,7 @@ def test_route_seeded(dev, name):
     """seeded: tag 0 = the start-noise fill + one token-major fill and one pre-pass per noise-adding step that has a next step"""
     c = D.ALL[name]
     x = _dev_inputs(c, dev)[0]
-    got = _launch_counts(_engine(c, dev, True, seeded_noise=True), x, seed=U.SEED)
+    got = launch_counts(_engine(c, dev, True, seeded_noise=True), x, seed=U.SEED)
     assert got[0] == 1 + 2 * D.prepasses(c), got
 
 
@@ -234,7 +173,7 @@ def test_route_flag_clear_is_unchanged(dev, name):
     """flag clear: the separate launches - x-projection GEMM, per step the step prologue, L plain layers and the head GEMM; no tail
     kernel, nothing under tag 0 (the noise transposes and k_seg_update carry no tag)"""
     c = D.ALL[name]
-    got = _launch_counts(_engine(c, dev, False), *_dev_inputs(c, dev))
+    got = launch_counts(_engine(c, dev, False), *_dev_inputs(c, dev))
     want = {0: 0, 1: 1, 2: c['K'], 3: 0, 7: c['K'] * c['L'], 8: c['K'], 10: 0}
     assert {t: got[t] for t in want} == want, got
 
@@ -250,7 +189,7 @@ def test_seeded_chain_equals_unseeded_chain_fed_the_rebuilt_noise(dev, name):
     eng = _engine(c, dev, True, seeded_noise=True)
     out = eng.sample(x, seed=U.SEED, image_base=5, call=2).cpu()
     start = eng.last_noise().clone()
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
     ddim = _engine(c, dev, sampler='ddim', seeded_noise=True)
     stack = torch.zeros((c['K'],) + tuple(start.shape), device=dev)
     per = U.per_image(c)
@@ -263,7 +202,7 @@ def test_seeded_chain_equals_unseeded_chain_fed_the_rebuilt_noise(dev, name):
             assert err.max() <= U.BOUND_UNIT
     plain = _engine(c, dev, True)
     again = plain.sample(x, start.clone(), stack).cpu()
-    _assert_guards(plain, name)
+    assert_guards(plain, name)
     assert torch.equal(again, out)
     if D.prepasses(c):
         assert not torch.equal(plain.sample(x, start.clone(), torch.zeros_like(stack)).cpu(), out)      # the step noise does count
@@ -293,19 +232,18 @@ def test_graph_capture_and_replay_same_bits(dev, name, seeded):
     torch.cuda.synchronize()
     assert torch.equal(got, want)
     assert torch.equal(g.replay().clone(), other if seeded else want)       # (seeded: replay() alone repeats the LAST key)
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
 
 
 # ---- 6. step record ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('vid', sorted(VIDS))
 @pytest.mark.parametrize('name', ['dc_15tok', 'dc_1x37_r2_cx96', 'seg_ddpm_acc'])
 def test_step_record_is_the_x0_trace_and_the_map_its_definition(dev, name, vid):
-    from test_step_record_gpu import ref_disagreement
     c = D.ALL[name]
     x, noise, sn = _dev_inputs(c, dev)
     rec = _engine(c, dev, True, record_steps=True, **VIDS[vid])
     out = rec.sample(x, noise, sn).cpu()
-    _assert_guards(rec, name)
+    assert_guards(rec, name)
     assert torch.equal(out, _output(name, vid, dev))                       # the flag does not move the output
     record, smap = rec.step_record().cpu(), rec.step_disagreement().cpu()
     assert record.shape == (c['K'], c['B'], c['r'], c['h'], c['w']) and record.dtype == torch.uint8

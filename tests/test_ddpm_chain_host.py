@@ -16,6 +16,7 @@ import config_space_cases as S
 import ddpm_chain_cases as D
 from ddp_amd import _lib
 from golden_util import max_rel
+from support import refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -122,13 +123,6 @@ def test_flag_clear_sizes_are_the_parent_builds(name):
     assert rc == 0 and (total, model) == PARENT_BYTES[name]
 
 
-def _refused(lib, cfg, word):
-    n = C.c_size_t(0)
-    for entry in (lib.ddp_query_workspace, lib.ddp_query_const_workspace):
-        assert entry(C.byref(cfg), C.byref(n)) == -1               # DDP_E_BADCFG
-        assert word.encode() in lib.ddp_last_error(), lib.ddp_last_error()
-
-
 def test_flag_is_refused_elsewhere_by_message():
     lib = _lib.load()
     for name in ('seg_L12', 'seg_cx96_r2', 'depth_K1', 'depth_9x11_L1_bins', 'bev_kc8_r1', 'bev_kc9_r2'):     # seg + ddim, depth, bev
@@ -136,7 +130,7 @@ def test_flag_is_refused_elsewhere_by_message():
             cfg = S.make_cfg(S.CASES[name], gemm)
             assert S.query(lib, cfg)[0] == 0
             cfg.flags |= _lib.FLAG_DDPM_CHAIN
-            _refused(lib, cfg, 'DDP_FLAG_DDPM_CHAIN exists for the segmentation ddpm sampler only')
+            refused(lib, cfg, 'DDP_FLAG_DDPM_CHAIN exists for the segmentation ddpm sampler only')
     # the FCN loop: seg + ddpm is its configuration too, the flag is not
     import seeded_noise_util as U
     n = C.c_size_t(0)
@@ -152,7 +146,7 @@ def test_flag_is_refused_elsewhere_by_message():
     # a bit nobody defines is still unknown
     cfg = D.make_cfg(D.CASES['dc_L1'])
     cfg.flags |= 8192
-    _refused(lib, cfg, 'unknown flags')
+    refused(lib, cfg, 'unknown flags')
 
 
 def test_plugin_attribute_and_engine_key():

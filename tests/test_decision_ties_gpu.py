@@ -31,27 +31,9 @@ import config_space_cases as S
 import decision_tie_cases as T
 from ddp_amd import _lib
 from golden_util import max_rel
-from test_config_space_gpu import GUARD, PATTERN, _assert_guards
-from test_hip_parity import REL
-from test_step_record_gpu import ref_disagreement
+from support import REL, assert_guards, dev, guard, ref_disagreement  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def _guard(eng, dev, floats=None):
-    """move the engine onto a workspace with a 4 KiB guard on either side, NaN-patterned throughout"""
-    n = eng.workspace.numel() if floats is None else floats
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    assert eng.workspace.data_ptr() % 256 == 0
-    return eng
 
 
 def test_bar_is_the_suite_bar():
@@ -63,14 +45,13 @@ def _seg_engine(c, route, dev):
     from ddp_amd.engine import DDPEngine, FcnSamplerEngine
     sd = T.seg_state(c)
     if route != 'fcn':
-        return _guard(DDPEngine(sd, 'seg', device=dev, record_x0=True, record_steps=True, **T.engine_flags(route), **S.engine_kwargs(c)), dev)
-    from test_next_rows_gpu import _fcn_head
-    head = _fcn_head(dict(c, classes=c['Kc']), {k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, dev)
+        return guard(DDPEngine(sd, 'seg', device=dev, record_x0=True, record_steps=True, **T.engine_flags(route), **S.engine_kwargs(c)))
+    head = T.N.fcn_head(dict(c, classes=c['Kc']), {k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, dev)
     eng = FcnSamplerEngine(sd, head, h=c['h'], w=c['w'], batch=c['B'], randsteps=c['r'], timesteps=c['K'], num_classes=c['Kc'],
                            bit_scale=c['bit_scale'], time_difference=c['td'], sampler=c['sampler'], accumulation=c['accumulation'], device=dev,
                            record_steps=True)
     assert eng._ws_bytes % 4 == 0
-    return _guard(eng, dev, eng._ws_bytes // 4)          # exactly the queried size (the engine's own allocation has 64 floats of slack)
+    return guard(eng, floats=eng._ws_bytes // 4)         # exactly the queried size (the engine's own allocation has 64 floats of slack)
 
 
 @pytest.mark.parametrize('name,route', T.seg_pairs())
@@ -81,7 +62,7 @@ def test_seg_sampler_takes_the_first_maximum(dev, name, route):
     eng = _seg_engine(c, route, dev)
     out = eng.sample(x.to(dev), noise.to(dev), sn.to(dev) if sn is not None else None)
     torch.cuda.synchronize()
-    _assert_guards(eng, f'{name} {route}')
+    assert_guards(eng, f'{name} {route}')
     out = out.cpu()
     ref = T.seg_oracle(c)['out']
     assert out.shape == ref.shape and torch.isfinite(out).all(), f'{name} {route}: shape or non-finite output'
@@ -214,10 +195,10 @@ def test_bev_threshold_is_strict(dev, name, vid):
     kw = dict(T.bev_variants(c))[vid]
     Kc, thr = c['Kc'], c['threshold']
     x, noise, _ = S.inputs(c)
-    eng = _guard(DDPEngine(T.bev_state(c), 'bev', device=dev, record_steps=True, **kw, **T.bev_engine_kwargs(c)), dev)
+    eng = guard(DDPEngine(T.bev_state(c), 'bev', device=dev, record_steps=True, **kw, **T.bev_engine_kwargs(c)))
     out = eng.sample(x.to(dev), noise.to(dev))
     torch.cuda.synchronize()
-    _assert_guards(eng, f'{name} {vid}')
+    assert_guards(eng, f'{name} {vid}')
     out, rec, dmap = out.cpu(), eng.step_record().cpu(), eng.step_disagreement().cpu()
     o = T.bev_oracle(c)
     assert out.shape == o['out'].shape and torch.isfinite(out).all()

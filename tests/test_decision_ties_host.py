@@ -18,13 +18,13 @@ import torch
 
 import decision_tie_cases as T
 from golden_util import max_rel
-from test_hip_parity import VARIANTS as PARITY_VARIANTS
+from support import VARIANTS as PARITY_VARIANTS
 
 
 def test_constants_are_the_suites():
     import config_space_cases as S
     import next_rows_cases as N
-    from test_hip_parity import REL
+    from support import REL
     assert T.REL == REL == S.REL == 2e-4 and T.COND == S.COND == REL / 20
     assert T.MARGIN == N.MARGIN and T.TIE_SHARE == N.TIE_SHARE
 

@@ -15,9 +15,9 @@ from ddp_amd.engine import DDPEngine  # noqa: E402
 from ddp_amd.utils import synthetic  # noqa: E402
 import depth_bins_util as U  # noqa: E402
 from golden_util import max_rel  # noqa: E402
+from support import REL  # noqa: E402  (the depth bar of test_hip_parity.py)
 
 pytestmark = pytest.mark.gpu
-REL = 2e-4          # the depth bar of test_hip_parity.py
 
 
 def _engine_kwargs(cfg):

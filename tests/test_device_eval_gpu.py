@@ -18,24 +18,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dev
 SEG_NAMES = list(V.seg_cases())
 DEPTH_NAMES = V.FIXTURE_DEPTH + ['kitti']
 BEV_NAMES = list(V.bev_cases())
-GUARD = 64
-
-
-def _flat_at(arr, off, dtype):
-    """``arr`` on the device, ``off`` bytes into a 256-byte aligned allocation"""
-    t = torch.from_numpy(np.ascontiguousarray(arr)).reshape(-1)
-    buf = torch.empty(off + t.numel() * t.element_size() + 16, dtype=torch.uint8, device='cuda')
-    assert buf.data_ptr() % 256 == 0
-    view = buf[off:off + t.numel() * t.element_size()].view(dtype).reshape(arr.shape)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(arr)))
-    return view
-
-
-def _seg_dev(case):
-    offs = case.get('offsets') or [(0, 0)] * len(case['preds'])
-    P = [_flat_at(p, o[0], torch.uint8) for p, o in zip(case['preds'], offs)]
-    L = [_flat_at(l, o[1], torch.uint8) for l, o in zip(case['labels'], offs)]
-    return P, L
+GUARD, _seg_dev, _Backbone = V.GUARD, V.seg_dev, V.PerImageBackbone
 
 
 def _seg_run(case, P=None, L=None, out=None):
@@ -285,20 +268,9 @@ def _intersect_and_union(pred_label, label, num_classes, ignore_index, reduce_ze
     return area_intersect, area_union, area_pred_label, area_label
 
 
-class _Backbone(torch.nn.Module):
-    """stands in for the frozen backbone + neck: the fixture's feature map, once per image of the batch"""
-
-    def __init__(self, x):
-        super().__init__()
-        self.x = x
-
-    def forward(self, img):
-        return [self.x.expand(img.shape[0], -1, -1, -1).contiguous()]
-
-
 def test_harness_device_eval_equals_the_host_path():
     from golden_util import load_case
-    from test_plugin_gpu import _seg_model
+    from support import seg_model as _seg_model
     from ddp_amd import apis
     cfg, sd, x, _, _, _ = load_case('seg_ade_k3')
     model = _seg_model(cfg)
@@ -366,7 +338,7 @@ def test_harness_device_eval_equals_the_host_path():
 
 def test_slide_mode_on_device_equals_the_default():
     from golden_util import load_case
-    from test_plugin_gpu import _seg_model
+    from support import seg_model as _seg_model
     cfg, sd, x, _, _, _ = load_case('seg_city_r2')
     model = _seg_model(dict(cfg, randsteps=1))
     model.load_state_dict(sd, strict=True)
@@ -393,7 +365,7 @@ def test_slide_mode_on_device_equals_the_default():
 def test_depther_on_device_and_harness():
     from ddp_amd import apis
     from ddp_amd.utils import synthetic
-    from test_plugin_gpu import _depth_model
+    from support import depth_model as _depth_model
     model = _depth_model({}, synthetic.make_state_dict('depth', 1, 6, 256, seed=0))
     model.extract_feat = lambda img: [None]
     H, W = 44, 152

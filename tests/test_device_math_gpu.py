@@ -11,17 +11,13 @@ import pytest
 import torch
 
 import device_math_util as U
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GELU_ROUTES = ('fast', 'ops', 'sched', 'packed')
 SPLIT_ROUTES = ('split8', 'split8_packed', 'split_ops')
 ULP = 2.0 ** -23
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
 
 
 @pytest.fixture(scope='module')

@@ -10,6 +10,7 @@ import pytest
 
 import device_math_util as U
 from ddp_amd import _lib, build
+from support import dynamic_symbols as _dynamic_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_REF_CAP = 5e-7
@@ -86,11 +87,6 @@ def probe_so(tmp_path_factory):
     r = subprocess.run(build.probe_cmd(out), capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
     return out
-
-
-def _dynamic_symbols(path):
-    out = subprocess.run(['nm', '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if l.split()[1:2] and l.split()[1] in 'TDBRW')
 
 
 def test_probe_builds_and_exports_only_probes(probe_so):

@@ -3,7 +3,6 @@ tests/test_fcn_gn_host.py).  ``ddp_fcn_head_forward`` and ``ddp_sample_fcn`` thr
 (as tests/test_next_rows_gpu.py), through the plugin class and the segmentor; against the fp32 expectation and the fixtures made by
 the reference class at the project's REL = 2e-4 (max_rel).  Every GroupNorm case fails on the parent commit with DDP_E_NULL
 ("incomplete norm"), the plugin tests with NotImplementedError.  The BatchNorm / norm-free paths: same bits as the parent's build."""
-import ctypes as C
 import json
 import os
 
@@ -14,18 +13,11 @@ import torch.nn.functional as F
 import fcn_gn_cases as G
 from ddp_amd import _lib
 from golden_util import max_rel
-from test_config_space_gpu import _assert_guards
-from test_hip_parity import REL
-from test_next_rows_gpu import Guarded, _finite, _stream
+from support import REL, FixedBackbone as _Backbone, Guarded, assert_guards as _assert_guards, dev, finite as _finite, stream as _stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
 
 
 def test_bar_is_the_suite_bar():
@@ -103,65 +95,25 @@ def test_head_matches_reference_fixture(dev, name):
 
 
 # ---- the sampler loop ----------------------------------------------------------------------------------------------------------
-class _Loop:
-    """ddp_prepare_fcn / ddp_sample_fcn through the C ABI on a guarded, exactly sized workspace; the conv array from the state dict"""
-
-    def __init__(self, c, sd, dev, batch=None, flags=0):
-        from ddp_amd.engine import PackedWeights
-        self.c, self.dev, self.lib = c, dev, _lib.load()
-        self.B = c['B'] if batch is None else batch
-        self.weights = PackedWeights(sd, 'seg', 0, dev)
-        self.convs, self.keep = G.conv_array(sd, c, dev, prefix='decode_head.')
-        self.cfg = G.loop_cfg(c, self.B, flags)
-        self.steps = G.loop_steps(c)
-        self.nbytes = G.loop_query(self.lib, c, self.B, flags)
-        self.g = Guarded(self.nbytes, dev)
-
-    def _args(self):
-        return (C.byref(self.cfg), C.byref(self.weights.struct), self.convs, self.c['num_convs'], self.c['dilation'], self.steps)
-
-    def prepare(self):
-        self.cfg.flags &= ~_lib.FLAG_FCN_PREPARED
-        _lib.check(self.lib.ddp_prepare_fcn(*self._args(), self.g.ptr(), _stream(self.dev)), self.lib)
-        torch.cuda.synchronize()
-        _assert_guards(self.g, f'fcn_gn loop {self.c["name"]} ddp_prepare_fcn')
-        self.cfg.flags |= _lib.FLAG_FCN_PREPARED
-
-    def sample(self, x, noise, sn, what=''):
-        c = self.c
-        out = torch.full((self.B, c['classes'], c['h'], c['w']), float('nan'), device=self.dev)
-        _lib.check(self.lib.ddp_sample_fcn(*self._args(), x.data_ptr(), noise.data_ptr(), sn.data_ptr() if sn is not None else None,
-                                           out.data_ptr(), self.g.ptr(), _stream(self.dev)), self.lib)
-        torch.cuda.synchronize()
-        _assert_guards(self.g, f'fcn_gn loop {c["name"]} {what}')
-        _finite(out, f'fcn_gn loop {c["name"]} {what}')
-        return out
-
-    def record(self):
-        """(K, B, r, h, w) uint8: the step record at the end of the workspace (include/ddp_mi355x.h, DDP_FLAG_STEP_RECORD)"""
-        from ddp_amd.engine import caller_regions, step_record_view
-        return step_record_view(self.g.ws, caller_regions(self.cfg, self.nbytes)['step_rec'][0], self.cfg).clone().cpu()
-
-
 def _loop_checks(c, sd, dev, x, noise, sn, ref, decisions):
     x, noise, sn = [t.contiguous().to(dev) if t is not None else None for t in (x, noise, sn)]
-    out = _Loop(c, sd, dev).sample(x, noise, sn, what='self-preparing')
+    out = G.device_loop(c, sd, dev).sample(x, noise, sn, what='self-preparing')
     o = out.cpu()
     errs = [max_rel(o[b:b + 1], ref[b:b + 1]) for b in range(c['B'])]
     print(f'FCN-GN loop {c["name"]}: max-rel per image {" ".join(f"{e:.3e}" for e in errs)} (bar {REL:.0e})')
     assert out.shape == ref.shape and max(errs) < REL
-    prepared = _Loop(c, sd, dev)
+    prepared = G.device_loop(c, sd, dev)
     prepared.prepare()
     assert torch.equal(prepared.sample(x, noise, sn, what='prepared'), out), 'prepared and self-preparing calls differ'
     assert torch.equal(prepared.sample(x, noise, sn, what='prepared, second call'), out)
-    rec = _Loop(c, sd, dev, flags=_lib.FLAG_STEP_RECORD)
+    rec = G.device_loop(c, sd, dev, flags=_lib.FLAG_STEP_RECORD)
     assert torch.equal(rec.sample(x, noise, sn, what='step record'), out), 'DDP_FLAG_STEP_RECORD changed the output'
     got = rec.record()
     if decisions is not None:
         assert got.shape == decisions.shape and torch.equal(got, decisions), \
             f'{int((got != decisions).sum())} of {decisions.numel()} recorded decisions differ from the expectation\'s'
     if c['B'] > 1:
-        one = _Loop(c, sd, dev, batch=1)
+        one = G.device_loop(c, sd, dev, batch=1)
         for b in range(c['B']):
             ob = one.sample(x[b:b + 1].contiguous(), noise[b:b + 1].contiguous(), sn[:, b:b + 1].contiguous() if sn is not None else None,
                             what=f'image {b} alone')
@@ -187,7 +139,7 @@ def test_loop_matches_reference_fixture(dev, name):
     for a seed that keeps the margin everywhere: smallest 6.5e-5 and 5.1e-4)."""
     c, sd, x, noise, sn, ref, logits = G.load_fixture_loop(name)
     out = _loop_checks(c, sd, dev, x, noise, sn, ref, None)
-    rec = _Loop(c, sd, dev, flags=_lib.FLAG_STEP_RECORD)
+    rec = G.device_loop(c, sd, dev, flags=_lib.FLAG_STEP_RECORD)
     rec.sample(x.to(dev), noise.contiguous().to(dev), sn.contiguous().to(dev) if sn is not None else None, what='step record')
     got = rec.record()[:, 0]                                                         # (K, r, h, w)
     t = logits.topk(2, dim=2).values
@@ -208,15 +160,6 @@ def _segmentor(c, sd, dev, **kw):
     return model.to(dev).eval()
 
 
-class _Backbone(torch.nn.Module):
-    def __init__(self, x):
-        super().__init__()
-        self.x = x
-
-    def forward(self, img):
-        return [self.x]
-
-
 @pytest.mark.parametrize('name', ['b1_ddim_fused', 'b2_ddpm_odd', 'b2_r2_ddim'])
 def test_segmentor_with_gn_head(dev, name):
     """the seg ``DDP`` segmentor with ``norm_cfg=dict(type='GN', num_groups=32)`` in its FCN decode head: ddim_sample / ddpm_sample
@@ -226,7 +169,7 @@ def test_segmentor_with_gn_head(dev, name):
     x, noise, sn = [t.to(dev) if t is not None else None for t in G.loop_inputs(c)]
     model = _segmentor(c, sd, dev)
     out = model.ddpm_sample(x, noise=noise, step_noise=sn) if c['sampler'] == 'ddpm' else model.ddim_sample(x, noise=noise)
-    assert torch.equal(out, _Loop(c, sd, dev).sample(x, noise, sn, what='beside the segmentor'))
+    assert torch.equal(out, G.device_loop(c, sd, dev).sample(x, noise, sn, what='beside the segmentor'))
     assert max_rel(out.cpu(), G.loop_expect(c)[0]) < REL
     model.backbone = _Backbone(x)
     H, W = c['h'] * 4, c['w'] * 4

@@ -14,6 +14,7 @@ import torch
 
 import fcn_gn_cases as G
 from ddp_amd import _lib
+from support import max_rel64 as _rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -21,12 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
 import ref_shim  # noqa: E402
 
 
-def _rel(a, b):
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max())
-
-
 def test_bars():
-    from test_hip_parity import REL
+    from support import REL
     assert G.REL == REL == 2e-4 and G.F32_VS_F64 == 1e-5 and G.MARGIN == 1e-3 and G.MARGIN >= 5 * G.REL
 
 
@@ -192,7 +189,7 @@ def test_segmentor_builds_with_a_gn_head():
 def test_abi_version_exports_and_workspace_bytes_are_the_parents():
     lib = _lib.load()
     assert _lib.ABI_VERSION == 7 and lib.ddp_abi_version() == 7
-    from test_device_math_host import _dynamic_symbols
+    from support import dynamic_symbols as _dynamic_symbols
     assert _dynamic_symbols(_lib.lib_path()) == sorted(_lib.EXPORTS) and len(_lib.EXPORTS) == 36
     want = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'fcn_gn', 'parent_workspace_bytes.json')))
     got = G.workspace_bytes(lib)

@@ -25,10 +25,10 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from golden_util import class_projection_weights, load_fullsize_case
 from parity_report import record
+from support import dependency_cone as _dependency_cone, dev, dilate as _dilate  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,11 +36,6 @@ GATE = 1e-3
 REACH = 16           # px: 2 x the largest tight reach of a flipped decision measured at full size (C2: 3, C3: 8)
 ORACLE_THREADS = 8      # the free-running draws depend on the CPU GEMMs' summation order: one thread count on every host
 BEV_SCOPES = dict(input_scope=((-51.2, 51.2, 0.8), (-51.2, 51.2, 0.8)), output_scope=((-50, 50, 0.5), (-50, 50, 0.5)))
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
 
 
 def _usable_cores():
@@ -85,32 +80,6 @@ def _oracle_threads(n=ORACLE_THREADS):
         yield
     finally:
         torch.set_num_threads(old)
-
-
-def _dilate(mask, r):
-    """binary dilation of an (h,w) bool map by a (2r+1)^2 square, separable"""
-    if r <= 0 or not bool(mask.any()):
-        return mask.clone()
-    m = mask[None, None].float()
-    m = F.max_pool2d(m, (1, 2 * r + 1), stride=1, padding=(0, r))
-    m = F.max_pool2d(m, (2 * r + 1, 1), stride=1, padding=(r, 0))
-    return m[0, 0] > 0
-
-
-def _dependency_cone(differ, reach, accumulation):
-    """Pixels of the FINAL output that a set of differing x0 decisions can influence (segmentors/ddp.py:215-246).
-    ``differ[s]`` (h,w) bool: the two runs fed different classes back at step s.  The update (:238-239) and the concat-conv
-    are pointwise, so the noisy map entering step s differs exactly where some earlier decision differed; one pass of the
-    decoder then carries a changed input at most ``reach`` pixels (layers x (largest sampling offset + the bilinear tap)).
-    Output = last step's scores, or with accumulation the mean over all steps."""
-    K = len(differ)
-    changed = torch.zeros_like(differ[0])
-    cone = torch.zeros_like(differ[0])
-    for s in range(K):
-        if accumulation or s == K - 1:
-            cone |= _dilate(changed, reach)
-        changed = changed | differ[s]
-    return cone
 
 
 def _single_step_vs_fp64(name, g1, fn32, fn64):

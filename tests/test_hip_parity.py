@@ -18,35 +18,11 @@ import pytest
 import torch
 
 from golden_util import case_names, load_case, max_rel
+from support import REL, VARIANTS, dev, fixture_engine as _engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-REL = 2e-4          # asserted;  north_star gate is 1e-3
 GATE = 1e-3
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def _engine(cfg, sd, dev, batch=1, **over):
-    from ddp_amd.engine import DDPEngine
-    task = cfg['task']
-    kw = dict(h=cfg['h'], w=cfg['w'], batch=batch, randsteps=cfg['randsteps'], timesteps=cfg['timesteps'],
-              bit_scale=cfg['bit_scale'], time_difference=cfg.get('time_difference', 1), device=dev)
-    if task == 'seg':
-        kw.update(num_classes=cfg['num_classes'], accumulation=cfg['accumulation'],
-                  noise_schedule=cfg['noise_schedule'], sampler=cfg['diffusion'],
-                  sample_range0=cfg.get('sample_range', (0.0, 0.999))[0])
-    elif task == 'depth':
-        kw.update(min_depth=cfg['min_depth'], max_depth=cfg['max_depth'], depth_scale_up=cfg.get('scale_up', False),
-                  depth_use_eps=cfg.get('use_eps', True))
-    else:
-        kw.update(num_classes=6, feat_channels=cfg['feat_channels'], bev_input_scope=cfg['input_scope'],
-                  bev_output_scope=cfg['output_scope'])
-    kw.update(over)
-    return DDPEngine(sd, task, **kw)
 
 
 def test_library_is_loaded_native():
@@ -239,20 +215,6 @@ def test_head_forward_trace(dev, name):
     temb = O.time_mlp(ls, sd).to(dev)
     out = eng.head_forward(feat, temb)
     assert max_rel(out.cpu(), g['logits_steps'][0]) < REL
-
-
-# every engine / fusion level of the library runs the reference-made fixtures: the default path (bf16x3 split products,
-# persistent layer kernel, fused step head and seg tail), the same arithmetic as separate tile GEMMs, and the exact
-# f32-input MFMA engine (include/ddp_mi355x.h DDP_GEMM_*, DDP_FLAG_*)
-VARIANTS = {'bf16x3': dict(gemm='bf16x3'), 'f32': dict(gemm='f32'),
-            'bf16x3-unfused-layer': dict(gemm='bf16x3', fused_layer=False),
-            'bf16x3-unfused-prologue': dict(gemm='bf16x3', fused_prologue=False),
-            # the last layer of a step and the seg tail as the two kernels they were fused from (DDP_FLAG_UNFUSED_TAIL)
-            'bf16x3-unfused-tail': dict(gemm='bf16x3', fused_tail=False),
-            # the first step's head as NCHW -> SB conversions + x-projection GEMM + k_layer MODE 2 (DDP_FLAG_SB_HEAD)
-            'bf16x3-sb-head': dict(gemm='bf16x3', nchw_head=False),
-            # the LDS gather's "actual mean offset is far from the guess: refill the window" branch (DDP_FLAG_GATHER_GUESS_ZERO)
-            'bf16x3-gather-refill': dict(gemm='bf16x3', gather_guess_zero=True)}
 
 
 _FP64_DIST = {}
@@ -875,7 +837,7 @@ def test_self_aligned_prepass_golden(dev, name):
     inside the reference's forward_train (self_aligned_ddp.py:150-164)."""
     import ddp_amd
     cfg, sd, x, noise, g = load_aligned_case(name)
-    from test_host_logic import seg_cfg
+    from support import seg_cfg
     mc = seg_cfg(type='SelfAlignedDDP', bit_scale=cfg['bit_scale'], noise_schedule=cfg['noise_schedule'])
     mc['decode_head']['num_classes'] = cfg['num_classes']
     model = ddp_amd.build_segmentor(mc)

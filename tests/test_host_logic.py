@@ -12,29 +12,9 @@ from ddp_amd import _lib, schedule
 from ddp_amd.engine import PackedWeights, hot_path_keys
 from ddp_amd.utils import synthetic
 from oracle import ddp_oracle as O
+from support import ENCODER, POSENC, seg_cfg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-ENCODER = dict(type='DetrTransformerEncoder', num_layers=6,
-               transformerlayers=dict(type='BaseTransformerLayer', use_time_mlp=True,
-                                      attn_cfgs=dict(type='MultiScaleDeformableAttention', embed_dims=256,
-                                                     num_levels=1, num_heads=8, dropout=0.),
-                                      ffn_cfgs=dict(type='FFN', embed_dims=256, feedforward_channels=1024,
-                                                    ffn_drop=0., act_cfg=dict(type='GELU')),
-                                      operation_order=('self_attn', 'norm', 'ffn', 'norm')))
-POSENC = dict(type='SinePositionalEncoding', num_feats=128, normalize=True, offset=-0.5)
-
-
-def seg_cfg(**over):
-    # model dict of segmentation/configs/ade/ddp_swin_t_2x8_512x512_160k_ade20k.py:11-108 (hot-path part)
-    cfg = dict(type='DDP', timesteps=3, bit_scale=0.01, accumulation=True,
-               decode_head=dict(type='DeformableHeadWithTime', in_channels=[256], channels=256, in_index=[0],
-                                dropout_ratio=0., num_classes=150, norm_cfg=dict(type='SyncBN'), align_corners=False,
-                                num_feature_levels=1, encoder=ENCODER, positional_encoding=POSENC,
-                                loss_decode=dict(type='CrossEntropyLoss')),
-               train_cfg=dict(), test_cfg=dict(mode='whole'))
-    cfg.update(over)
-    return cfg
 
 
 def test_exports_match_header():
@@ -188,10 +168,10 @@ def test_dependency_cone_of_flipped_decisions():
     """The localisation assertion of the full-size parity tests (tests/test_full_size_parity.py::_dependency_cone): a decision that
     differs at step s changes the noisy map entering the LATER steps at that pixel only (the update and the concat-conv are
     pointwise, segmentors/ddp.py:223-239) and one decoder pass spreads a changed input by at most `reach` pixels."""
-    import test_full_size_parity as T
+    import support as T
     h, w, K, reach = 40, 60, 4, 5
     none = [torch.zeros(h, w, dtype=torch.bool) for _ in range(K)]
-    assert not T._dependency_cone(none, reach, False).any() and not T._dependency_cone(none, reach, True).any()
+    assert not T.dependency_cone(none, reach, False).any() and not T.dependency_cone(none, reach, True).any()
 
     def flip_at(step, y, x):
         d = [m.clone() for m in none]
@@ -200,19 +180,19 @@ def test_dependency_cone_of_flipped_decisions():
     box = torch.zeros(h, w, dtype=torch.bool)
     box[20 - reach:20 + reach + 1, 30 - reach:30 + reach + 1] = True
     for step in range(K - 1):                                   # any step before the last reaches the last step's scores
-        assert torch.equal(T._dependency_cone(flip_at(step, 20, 30), reach, False), box)
-        assert torch.equal(T._dependency_cone(flip_at(step, 20, 30), reach, True), box)
+        assert torch.equal(T.dependency_cone(flip_at(step, 20, 30), reach, False), box)
+        assert torch.equal(T.dependency_cone(flip_at(step, 20, 30), reach, True), box)
     # a decision of the LAST step feeds nothing back into the output (the sampler returns that step's scores / their mean)
-    assert not T._dependency_cone(flip_at(K - 1, 20, 30), reach, False).any()
-    assert not T._dependency_cone(flip_at(K - 1, 20, 30), reach, True).any()
+    assert not T.dependency_cone(flip_at(K - 1, 20, 30), reach, False).any()
+    assert not T.dependency_cone(flip_at(K - 1, 20, 30), reach, True).any()
     # the image border clips the box; two flips give the union
-    c = T._dependency_cone(flip_at(0, 0, 0), reach, False)
+    c = T.dependency_cone(flip_at(0, 0, 0), reach, False)
     assert int(c.sum()) == (reach + 1) ** 2 and bool(c[reach, reach]) and not bool(c[reach + 1, 0])
     d = flip_at(1, 20, 30)
     d[2][5, 50] = True
-    u = T._dependency_cone(d, reach, True)
+    u = T.dependency_cone(d, reach, True)
     assert bool(u[20, 30]) and bool(u[5, 50]) and int(u.sum()) == 2 * (2 * reach + 1) ** 2
-    assert torch.equal(T._dilate(none[0], 3), none[0])
+    assert torch.equal(T.dilate(none[0], 3), none[0])
 
 
 def test_depth_and_bev_state_dict_layout():

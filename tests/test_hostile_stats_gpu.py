@@ -30,8 +30,7 @@ import pytest
 import torch
 
 import hostile_stats_cases as S
-from test_config_space_gpu import GUARD, PATTERN, _assert_guards
-from test_hip_parity import VARIANTS as PARITY_VARIANTS
+from support import VARIANTS as PARITY_VARIANTS, assert_guards, dev, guard  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -43,22 +42,6 @@ PAIRS = [(n, r) for n, c in S.CASES.items() for r in c['routes']]
 _OUT = {}
 
 
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def _guard(eng, dev):
-    """move the engine onto a workspace with a 4 KiB guard on either side, NaN-patterned throughout"""
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    assert eng.workspace.data_ptr() % 256 == 0
-    return eng
-
-
 def _run(name, route, variant, dev):
     """the engine's output of (case, route, variant) on the CPU, computed once per process"""
     key = (name, route, variant)
@@ -66,7 +49,7 @@ def _run(name, route, variant, dev):
         return _OUT[key]
     from ddp_amd.engine import DDPEngine
     c = S.CASES[name]
-    eng = _guard(DDPEngine(S.state_dict(c), c['task'], device=dev, **VARIANTS[variant], **S.engine_kwargs(c, route)), dev)
+    eng = guard(DDPEngine(S.state_dict(c), c['task'], device=dev, **VARIANTS[variant], **S.engine_kwargs(c, route)))
     if route == 'head':
         feat, temb = S.head_inputs(c)
         out = eng.head_forward(feat.to(dev), temb.to(dev))
@@ -76,7 +59,7 @@ def _run(name, route, variant, dev):
             eng.set_x0_decisions(S.oracle_pair(c, route)['decisions'])
         out = eng.sample(x.to(dev), noise.to(dev))
     torch.cuda.synchronize()
-    _assert_guards(eng, f'{name} {route} {variant}')
+    assert_guards(eng, f'{name} {route} {variant}')
     _OUT[key] = out.cpu()
     return _OUT[key]
 

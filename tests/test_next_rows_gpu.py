@@ -21,8 +21,7 @@ import next_rows_cases as N
 from ddp_amd import _lib
 from golden_util import max_rel
 from oracle import ddp_oracle as O
-from test_config_space_gpu import GUARD, PATTERN, _assert_guards
-from test_hip_parity import REL
+from support import REL, Guarded, assert_guards as _assert_guards, dev, finite as _finite, stream as _stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,122 +30,28 @@ PROB_BAR = 2e-6              # tests/test_hip_parity.py epilogue tests: probabil
 DEPTH_BAR = 2e-5             # x max_depth (test_depth_epilogue_golden)
 
 
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-class Guarded:
-    """``nbytes`` of workspace between two 4 KiB guards, everything filled with the NaN pattern"""
-
-    def __init__(self, nbytes, dev):
-        assert nbytes % 4 == 0
-        n = nbytes // 4
-        self.guarded = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-        self.guarded.view(torch.int32).fill_(PATTERN)
-        self.ws = self.guarded[GUARD:GUARD + n]
-        assert self.ws.data_ptr() % 256 == 0
-
-    def ptr(self):
-        return self.ws.data_ptr()
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _finite(t, what):
-    assert torch.isfinite(t).all(), f'{what}: non-finite output (a NaN is a read of workspace bytes nobody wrote)'
-
-
 def test_bar_is_the_suite_bar():
     assert N.REL == REL == 2e-4
 
 
 # ---- necks ----------------------------------------------------------------------------------------------------------------------
-_NECK_DEV = {}
-
-
-def _neck_dev(c, dev):
-    """device copies of a neck case's weights and inputs (made once per case)"""
-    if c['name'] not in _NECK_DEV:
-        _NECK_DEV.clear()                    # one case at a time: tiles_gt_cus and swin_l hold tens of MB
-        sdf = {k: v.to(dev).contiguous() for k, v in N.fpn_state(c).items()}
-        sdm = {k: v.to(dev).contiguous() for k, v in N.msm_state(c).items()}
-        sdm['w'] = sdm['down.conv.weight'].reshape(256, 1024).contiguous()
-        _NECK_DEV[c['name']] = (sdf, sdm, [t.to(dev) for t in N.backbone_levels(c)],
-                                [t.to(dev) for t in N.fpn_like_levels(c)] if c['msm'] else None)
-    return _NECK_DEV[c['name']]
-
-
-def _images(ts, b):
-    return ts if b is None else [t[b:b + 1].contiguous() for t in ts]
-
-
-def _run_fpn(c, dev, sdf, xs, flags=0, g=None, what=''):
-    """ddp_neck_fpn on a guarded workspace of exactly the queried size -> (four NCHW outputs, the workspace)"""
-    lib = _lib.load()
-    B = xs[0].shape[0]
-    lv = N.fpn_level_structs(c, sdf)
-    g = g or Guarded(N.neck_queries(lib, c, B)[0], dev)
-    outs = [torch.full((B, 256, h, w), float('nan'), device=dev) for h, w in c['levels']]
-    pin = (C.c_void_p * 4)(*[x.data_ptr() for x in xs])
-    pout = (C.c_void_p * 4)(*[o.data_ptr() for o in outs])
-    _lib.check(lib.ddp_neck_fpn(lv, B, pin, pout, flags, g.ptr(), _stream(dev)), lib)
-    torch.cuda.synchronize()
-    _assert_guards(g, f'fpn {c["name"]} {what}')
-    for l, o in enumerate(outs):
-        _finite(o, f'fpn {c["name"]} level {l} {what}')
-    return outs, g
-
-
-def _run_msm(c, dev, sdm, lvls, align, flags=0, g=None, what=''):
-    lib = _lib.load()
-    B = lvls[0].shape[0]
-    lh, lw = N.level_sizes(c)
-    g = g or Guarded(N.neck_queries(lib, c, B)[1], dev)
-    out = torch.full((B, 256) + c['levels'][0], float('nan'), device=dev)
-    ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in lvls])
-    _lib.check(lib.ddp_neck_msm(ptrs, lh, lw, B, sdm['w'].data_ptr(), sdm['down.gn.weight'].data_ptr(), sdm['down.gn.bias'].data_ptr(),
-                                int(align), flags, out.data_ptr(), g.ptr(), _stream(dev)), lib)
-    torch.cuda.synchronize()
-    _assert_guards(g, f'msm {c["name"]} {what}')
-    _finite(out, f'msm {c["name"]} {what}')
-    return out, g
-
-
-def _run_chain(c, dev, sdf, sdm, xs, align=False, flags=0, g=None, what=''):
-    lib = _lib.load()
-    B = xs[0].shape[0]
-    lv = N.fpn_level_structs(c, sdf)
-    g = g or Guarded(N.neck_queries(lib, c, B)[2], dev)
-    out = torch.full((B, 256) + c['levels'][0], float('nan'), device=dev)
-    pin = (C.c_void_p * 4)(*[x.data_ptr() for x in xs])
-    _lib.check(lib.ddp_neck_fpn_msm(lv, B, pin, sdm['w'].data_ptr(), sdm['down.gn.weight'].data_ptr(), sdm['down.gn.bias'].data_ptr(),
-                                    int(align), flags, out.data_ptr(), g.ptr(), _stream(dev)), lib)
-    torch.cuda.synchronize()
-    _assert_guards(g, f'chain {c["name"]} {what}')
-    _finite(out, f'chain {c["name"]} {what}')
-    return out, g
-
-
 @pytest.mark.parametrize('name', N.neck_names())
 def test_fpn_matches_oracle(dev, name):
     """ddp_neck_fpn: all four outputs against the fp32 oracle (max-rel < REL); two calls give equal bits; image b of the batched
     call equals the single-image call bit for bit; guards untouched"""
     c = N.NECK[name]
-    sdf, _, xs, _ = _neck_dev(c, dev)
-    outs, _ = _run_fpn(c, dev, sdf, xs)
+    sdf, _, xs, _ = N.neck_dev(c, dev)
+    outs, _ = N.run_fpn(c, dev, sdf, xs)
     ref = N.neck_oracle(c)['fpn']
     errs = [max_rel(o.cpu(), r) for o, r in zip(outs, ref)]
     print(f'NEXT-ROWS neck {name}: ddp_neck_fpn routes {"/".join(r[0] for r in c["routes"])}{" all-32" if c["all32"] else ""}, max-rel per '
           f'level {" ".join(f"{e:.3e}" for e in errs)} (bar {REL:.0e})')
     assert [tuple(o.shape) for o in outs] == [tuple(r.shape) for r in ref] and max(errs) < REL
-    again, _ = _run_fpn(c, dev, sdf, xs, what='second call')
+    again, _ = N.run_fpn(c, dev, sdf, xs, what='second call')
     assert all(torch.equal(a, b) for a, b in zip(outs, again)), f'{name}: two calls differ'
     if c['B'] > 1:
         for b in range(c['B']):
-            one, _ = _run_fpn(c, dev, sdf, _images(xs, b), what=f'image {b} alone')
+            one, _ = N.run_fpn(c, dev, sdf, N.images(xs, b), what=f'image {b} alone')
             for l in range(4):
                 assert torch.equal(one[l][0], outs[l][b]), f'{name}: level {l} of image {b} differs between the batched and the single call'
 
@@ -156,20 +61,20 @@ def test_chain_matches_oracle_and_members(dev, name):
     """ddp_neck_fpn_msm: the merged map against the fp32 oracle chain (< REL) and against ddp_neck_fpn followed by ddp_neck_msm
     (< 1e-5); equal bits on a second call and, image by image, from single-image calls"""
     c = N.NECK[name]
-    sdf, sdm, xs, _ = _neck_dev(c, dev)
-    out, _ = _run_chain(c, dev, sdf, sdm, xs)
+    sdf, sdm, xs, _ = N.neck_dev(c, dev)
+    out, _ = N.run_chain(c, dev, sdf, sdm, xs)
     ref = N.neck_oracle(c)['chain']
     err = max_rel(out.cpu(), ref)
-    outs, _ = _run_fpn(c, dev, sdf, xs)
-    members, _ = _run_msm(c, dev, sdm, outs, False)
+    outs, _ = N.run_fpn(c, dev, sdf, xs)
+    members, _ = N.run_msm(c, dev, sdm, outs, False)
     pair = max_rel(out.cpu(), members.cpu())
     print(f'NEXT-ROWS neck {name}: ddp_neck_fpn_msm max-rel {err:.3e} (bar {REL:.0e}), vs member-by-member {pair:.3e} (bar {CHAIN_VS_MEMBERS:.0e})')
     assert out.shape == ref.shape and err < REL and pair < CHAIN_VS_MEMBERS
-    again, _ = _run_chain(c, dev, sdf, sdm, xs, what='second call')
+    again, _ = N.run_chain(c, dev, sdf, sdm, xs, what='second call')
     assert torch.equal(out, again), f'{name}: two calls differ'
     if c['B'] > 1:
         for b in range(c['B']):
-            one, _ = _run_chain(c, dev, sdf, sdm, _images(xs, b), what=f'image {b} alone')
+            one, _ = N.run_chain(c, dev, sdf, sdm, N.images(xs, b), what=f'image {b} alone')
             assert torch.equal(one[0], out[b]), f'{name}: image {b} differs between the batched and the single call'
 
 
@@ -178,17 +83,17 @@ def test_chain_matches_oracle_and_members(dev, name):
 def test_msm_alone_matches_oracle(dev, name, align):
     """ddp_neck_msm on four 256-channel NCHW levels (read in place by the stream GEMM), both align_corners"""
     c = N.NECK[name]
-    _, sdm, _, lvls = _neck_dev(c, dev)
-    out, _ = _run_msm(c, dev, sdm, lvls, align)
+    _, sdm, _, lvls = N.neck_dev(c, dev)
+    out, _ = N.run_msm(c, dev, sdm, lvls, align)
     ref = N.neck_oracle(c)['msm'][align]
     err = max_rel(out.cpu(), ref)
     print(f'NEXT-ROWS neck {name}: ddp_neck_msm align_corners={align} max-rel {err:.3e} (bar {REL:.0e})')
     assert out.shape == ref.shape and err < REL
-    again, _ = _run_msm(c, dev, sdm, lvls, align, what='second call')
+    again, _ = N.run_msm(c, dev, sdm, lvls, align, what='second call')
     assert torch.equal(out, again)
     if c['B'] > 1:
         for b in range(c['B']):
-            one, _ = _run_msm(c, dev, sdm, _images(lvls, b), align, what=f'image {b} alone')
+            one, _ = N.run_msm(c, dev, sdm, N.images(lvls, b), align, what=f'image {b} alone')
             assert torch.equal(one[0], out[b]), f'{name}: image {b} differs between the batched and the single call'
 
 
@@ -214,22 +119,22 @@ def test_neck_weights_ready_survives_a_geometry_change(dev, first, second):
     ready = _lib.NECK_WEIGHTS_READY
     # ddp_neck_fpn
     g = Guarded(sizes[0], dev)
-    _run_fpn(a, dev, sdf, xa, g=g, what='packing call')
-    kept, _ = _run_fpn(b, dev, other_f, xb, flags=ready, g=g, what='weights ready')
-    fresh, _ = _run_fpn(b, dev, sdf, xb)
-    handed, _ = _run_fpn(b, dev, other_f, xb)
+    N.run_fpn(a, dev, sdf, xa, g=g, what='packing call')
+    kept, _ = N.run_fpn(b, dev, other_f, xb, flags=ready, g=g, what='weights ready')
+    fresh, _ = N.run_fpn(b, dev, sdf, xb)
+    handed, _ = N.run_fpn(b, dev, other_f, xb)
     assert all(torch.equal(p, q) for p, q in zip(kept, fresh)) and not any(torch.equal(p, q) for p, q in zip(kept, handed))
     # ddp_neck_msm
     g = Guarded(sizes[1], dev)
-    _run_msm(a, dev, sdm, la, False, g=g, what='packing call')
-    kept, _ = _run_msm(b, dev, other_m, lb, False, flags=ready, g=g, what='weights ready')
-    assert torch.equal(kept, _run_msm(b, dev, sdm, lb, False)[0]) and not torch.equal(kept, _run_msm(b, dev, other_m, lb, False)[0])
+    N.run_msm(a, dev, sdm, la, False, g=g, what='packing call')
+    kept, _ = N.run_msm(b, dev, other_m, lb, False, flags=ready, g=g, what='weights ready')
+    assert torch.equal(kept, N.run_msm(b, dev, sdm, lb, False)[0]) and not torch.equal(kept, N.run_msm(b, dev, other_m, lb, False)[0])
     # ddp_neck_fpn_msm
     g = Guarded(sizes[2], dev)
-    _run_chain(a, dev, sdf, sdm, xa, g=g, what='packing call')
-    kept, _ = _run_chain(b, dev, other_f, other_m, xb, flags=ready, g=g, what='weights ready')
-    fresh, _ = _run_chain(b, dev, sdf, sdm, xb)
-    assert torch.equal(kept, fresh) and not torch.equal(kept, _run_chain(b, dev, other_f, other_m, xb)[0])
+    N.run_chain(a, dev, sdf, sdm, xa, g=g, what='packing call')
+    kept, _ = N.run_chain(b, dev, other_f, other_m, xb, flags=ready, g=g, what='weights ready')
+    fresh, _ = N.run_chain(b, dev, sdf, sdm, xb)
+    assert torch.equal(kept, fresh) and not torch.equal(kept, N.run_chain(b, dev, other_f, other_m, xb)[0])
     err = max_rel(fresh.cpu(), O.neck_multi_stage_merging(list(O.neck_fpn(N.backbone_levels(b), N.fpn_state(a))), N.msm_state(a)))
     print(f'NEXT-ROWS neck weights_ready: {second} after {first} in one buffer with the flag set and other weights handed in, bit-equal '
           f'to a fresh run with the packed weights; vs oracle {err:.3e}')
@@ -237,14 +142,6 @@ def test_neck_weights_ready_survives_a_geometry_change(dev, first, second):
 
 
 # ---- FCNHeadWithTime ------------------------------------------------------------------------------------------------------------
-def _fcn_head(c, sd, dev):
-    import ddp_amd
-    head = ddp_amd.FCNHeadWithTime(num_convs=c['num_convs'], kernel_size=3, concat_input=False, dilation=c['dilation'], in_channels=256,
-                                   channels=256, num_classes=c['classes'], in_index=0, norm_cfg=dict(type='BN') if c['bn'] else None)
-    head.load_state_dict(sd, strict=True)
-    return head.to(dev).eval()
-
-
 def _run_fcn(c, dev, head, feat, temb, what=''):
     """ddp_fcn_head_forward through the C ABI (the parameter arrays are the plugin class's) on a guarded, exactly sized workspace"""
     lib = _lib.load()
@@ -269,7 +166,7 @@ def test_fcn_head_matches_oracle(dev, name):
     batched call equals its single-map call bit for bit (tap_ok is all that keeps a tap out of the neighbouring map)."""
     c = N.FCN[name]
     sd = N.fcn_state(c)
-    head = _fcn_head(c, sd, dev)
+    head = N.fcn_head(c, sd, dev)
     feat, temb = N.fcn_inputs(c)
     feat = feat.to(dev)
     temb = temb[0].contiguous().to(dev) if temb is not None else None
@@ -294,44 +191,6 @@ def test_fcn_head_matches_oracle(dev, name):
 
 
 # ---- sampler loop around the FCN head -------------------------------------------------------------------------------------------
-class _Loop:
-    """ddp_prepare_fcn / ddp_sample_fcn through the C ABI for a LOOP case (ddp_amd.engine.FcnSamplerEngine fixes 256 feature
-    channels; the C ABI takes any multiple of 32)"""
-
-    def __init__(self, c, dev, gemm='bf16x3', batch=None):
-        from ddp_amd.engine import PackedWeights
-        self.c, self.dev, self.lib = c, dev, _lib.load()
-        self.B = c['B'] if batch is None else batch
-        sd = N.loop_state(c)
-        self.weights = PackedWeights(sd, 'seg', 0, dev)
-        fc = dict(c, maps=1)
-        self.head = _fcn_head(fc, {k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, dev)
-        self.convs, self.keep = self.head.conv_array()
-        self.cfg = N.loop_cfg(c, gemm, self.B)
-        self.steps = N.loop_steps(c)
-        self.g = Guarded(N.loop_query(self.lib, c, gemm, self.B), dev)
-
-    def _args(self):
-        return (C.byref(self.cfg), C.byref(self.weights.struct), self.convs, self.c['num_convs'], self.c['dilation'], self.steps)
-
-    def prepare(self):
-        self.cfg.flags &= ~_lib.FLAG_FCN_PREPARED
-        _lib.check(self.lib.ddp_prepare_fcn(*self._args(), self.g.ptr(), _stream(self.dev)), self.lib)
-        torch.cuda.synchronize()
-        _assert_guards(self.g, f'loop {self.c["name"]} ddp_prepare_fcn')
-        self.cfg.flags |= _lib.FLAG_FCN_PREPARED
-
-    def sample(self, x, noise, sn, what=''):
-        c = self.c
-        out = torch.full((self.B, c['classes'], c['h'], c['w']), float('nan'), device=self.dev)
-        _lib.check(self.lib.ddp_sample_fcn(*self._args(), x.data_ptr(), noise.data_ptr(), sn.data_ptr() if sn is not None else None,
-                                           out.data_ptr(), self.g.ptr(), _stream(self.dev)), self.lib)
-        torch.cuda.synchronize()
-        _assert_guards(self.g, f'loop {c["name"]} {what}')
-        _finite(out, f'loop {c["name"]} {what}')
-        return out
-
-
 @pytest.mark.parametrize('name', list(N.LOOP))
 def test_fcn_loop_matches_oracle(dev, name):
     """ddp_sample_fcn, B images in one call, each against its own run of the reference sampler around the reference head:
@@ -344,7 +203,7 @@ def test_fcn_loop_matches_oracle(dev, name):
     c = N.LOOP[name]
     gemm = 'bf16x3'
     x, noise, sn = [t.to(dev) if t is not None else None for t in N.loop_inputs(c)]
-    loop = _Loop(c, dev, gemm)
+    loop = N.device_loop(c, dev, gemm)
     out = loop.sample(x, noise, sn, what='self-preparing')
     ref = N.loop_oracle(c)
     assert out.shape == ref.shape
@@ -354,11 +213,11 @@ def test_fcn_loop_matches_oracle(dev, name):
     print(f'NEXT-ROWS loop {name}: max-rel per image {" ".join(f"{e:.3e}" for e in errs)} (bar {REL:.0e}), argmax equal '
           f'{" ".join(f"{a:.4f}" for a in agree)}')
     assert max(errs) < REL and min(agree) > 0.999
-    prepared = _Loop(c, dev, gemm)
+    prepared = N.device_loop(c, dev, gemm)
     prepared.prepare()
     assert torch.equal(prepared.sample(x, noise, sn, what='prepared'), out), f'{name}: prepared and self-preparing calls differ'
     assert torch.equal(prepared.sample(x, noise, sn, what='prepared, second call'), out)
-    one = _Loop(c, dev, gemm, batch=1)
+    one = N.device_loop(c, dev, gemm, batch=1)
     for b in range(c['B']):
         ob = one.sample(x[b:b + 1].contiguous(), noise[b:b + 1].contiguous(), sn[:, b:b + 1].contiguous() if sn is not None else None,
                         what=f'image {b} alone')

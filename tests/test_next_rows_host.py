@@ -30,7 +30,7 @@ _rows = _r256      # rows of a GEMM operand: whole 256-row tiles (the same round
 
 
 def test_bar_is_the_suite_bar():
-    from test_hip_parity import REL
+    from support import REL
     import config_space_cases as S
     assert N.REL is S.REL and N.COND is S.COND and N.REL == REL == 2e-4 and N.COND == REL / 20
 

@@ -5,30 +5,9 @@ import torch
 
 import ddp_amd
 from golden_util import load_case, max_rel
-from test_host_logic import ENCODER, POSENC, seg_cfg
+from support import ENCODER, POSENC, REL, FixedBackbone as FakeBackbone, depth_model as _depth_model, seg_cfg, seg_model as _seg_model
 
 pytestmark = pytest.mark.gpu
-REL = 2e-4
-
-
-class FakeBackbone(torch.nn.Module):
-    """stands in for Swin+FPN+MultiStageMerging (frozen, upstream of the hot path): returns [x]."""
-
-    def __init__(self, x):
-        super().__init__()
-        self.x = x
-
-    def forward(self, img):
-        return [self.x]
-
-
-def _seg_model(cfg):
-    model = ddp_amd.build_segmentor(seg_cfg(
-        timesteps=cfg['timesteps'], randsteps=cfg['randsteps'], bit_scale=cfg['bit_scale'],
-        accumulation=cfg['accumulation'], noise_schedule=cfg['noise_schedule'], diffusion=cfg['diffusion'],
-        sample_range=tuple(cfg.get('sample_range', (0, 0.999))),
-        decode_head=dict(seg_cfg()['decode_head'], num_classes=cfg['num_classes'])))
-    return model
 
 
 @pytest.mark.parametrize('name', ['seg_ade_k3', 'seg_city_r2', 'seg_linear'])
@@ -106,17 +85,6 @@ def test_depther_sample():
     model.backbone = FakeBackbone(x.cuda())
     o = model.encode_decode(torch.zeros(1, 3, cfg['h'] * 4, cfg['w'] * 4, device='cuda'), None, rescale=True)
     assert o.shape == (1, 1, cfg['h'] * 4, cfg['w'] * 4) and float(o.min()) >= 1e-3 and float(o.max()) <= 80
-
-
-def _depth_model(cfg, sd, align_corners=False, min_depth=1e-3, max_depth=80):
-    dcfg = dict(type='DDP', bit_scale=cfg.get('bit_scale', 0.1), timesteps=cfg.get('timesteps', 3), randsteps=cfg.get('randsteps', 1),
-                min_depth=min_depth, max_depth=max_depth, test_cfg=dict(mode='whole'),
-                decode_head=dict(type='DeformableHeadWithTime', in_channels=[256], channels=256, in_index=[0],
-                                 dropout_ratio=0., scale_up=False, min_depth=min_depth, max_depth=max_depth, use_eps=True,
-                                 align_corners=align_corners, num_feature_levels=1, encoder=ENCODER, positional_encoding=POSENC))
-    model = ddp_amd.build_depther(dcfg)
-    model.load_state_dict(sd, strict=True)
-    return model.cuda().eval()
 
 
 @pytest.mark.parametrize('name', ['dpost_kitti_flip', 'dpost_simple_hflip', 'dpost_vflip_ac3', 'dpost_norescale'])

@@ -21,68 +21,21 @@ import torch.nn.functional as F
 
 import config_space_cases as S
 import prior_start_cases as P
+import support
 from ddp_amd import _lib
-from test_hip_parity import REL
+from support import PATTERN, REL, FixedBackbone as _Backbone, dev, guards_ok as _guards_ok  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
 START_BAR = 2.0 ** -21
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def routes(c):
-    """(id, gemm, flags): both engines and every flag that selects another route for the case (tests/test_config_space_gpu.py)"""
-    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False)),
-         ('unfused-prologue', 'bf16x3', dict(fused_prologue=False)), ('gather-refill', 'bf16x3', dict(gather_guess_zero=True))]
-    if c['task'] == 'seg' and c['sampler'] == 'ddim':
-        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
-        if c['r'] == 1:
-            v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
-    if c['task'] == 'seg' and c['sampler'] == 'ddpm':
-        v += [('chain', 'bf16x3', dict(ddpm_chain=True)), ('chain-unfused-tail', 'bf16x3', dict(ddpm_chain=True, fused_tail=False)),
-              ('chain-sb-head', 'bf16x3', dict(ddpm_chain=True, nchw_head=False))]
-    if c['task'] == 'bev' or (c['task'] == 'depth' and not c['n_bins']):
-        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
-    return v
-
-
-ROUTES = {(n, vid): (gemm, fl) for n, c in P.CASES.items() for vid, gemm, fl in routes(c)}
-_SD, _IN = {}, {}
-
-
-def _state(c, dev):
-    if c['name'] not in _SD:
-        _SD[c['name']] = P.state_dict(c)
-        _IN[c['name']] = tuple(None if t is None else t.to(dev) for t in S.inputs(c))
-    return _SD[c['name']], _IN[c['name']]
+ROUTES = {(n, vid): (gemm, fl) for n, c in P.CASES.items() for vid, gemm, fl in P.routes(c)}
+_state = support.state_cache(P.state_dict, S.inputs)
 
 
 def _engine(c, dev, gemm='bf16x3', batch=None, **kw):
     """DDPEngine of the case on a guarded, NaN-patterned workspace.  The prior map of a prior_start engine holds the PATTERN
     afterwards: the caller sets or clears it, as the library's contract says."""
-    from ddp_amd.engine import DDPEngine
-    sd, _ = _state(c, dev)
-    ekw = S.engine_kwargs(c)
-    if batch is not None:
-        ekw['batch'] = batch
-    eng = DDPEngine(sd, c['task'], device=dev, gemm=gemm, **kw, **ekw)
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    return eng
-
-
-def _guards_ok(eng):
-    bits = eng.guarded.view(torch.int32)
-    return int((bits[:GUARD] != PATTERN).sum()) == 0 and int((bits[-GUARD:] != PATTERN).sum()) == 0
+    return support.engine(_state(c, dev)[0], c['task'], S.engine_kwargs(c), dev, gemm, batch, **kw)
 
 
 def _sample(eng, c, dev, prior=None, noise=None, sl=None, seed=None):
@@ -155,7 +108,7 @@ def test_start_map_with_more_items_than_blocks(dev):
     bar = START_BAR * (ax0.abs() + se.abs()) + START_BAR * c['bit_scale']
     worst = float(((eng.last_start().double() - (ax0 + se)).abs() / bar).max())
     print(f'PRIOR-START start map {c["name"]}: worst |error| / bar {worst:.3f}')
-    _SD.pop(c['name']), _IN.pop(c['name'])                                # (the only large inputs of this file)
+    _state.forget(c['name'])                                              # (the only large inputs of this file)
     assert worst <= 1.0
 
 
@@ -348,15 +301,6 @@ def off_of(eng):
 
 
 # ---- 9 ------------------------------------------------------------------------------------------------------------------------------
-class _Backbone(torch.nn.Module):
-    def __init__(self, x):
-        super().__init__()
-        self.x = x
-
-    def forward(self, img):
-        return [self.x]
-
-
 def _image_frame(c, prior_map, ratio=(3.5, 2.75)):
     """the prior in the frame of a network input whose size is a NON-integer multiple of the map: every map pixel's value is written
     to the image pixel nearest resampling reads for it - floor(dst * in / out) - and everything else is poison, so that any other
@@ -371,23 +315,13 @@ def _image_frame(c, prior_map, ratio=(3.5, 2.75)):
     return img
 
 
-def _seg_plugin(c, dev):
-    import ddp_amd
-    from test_host_logic import ENCODER, seg_cfg
-    head = dict(seg_cfg()['decode_head'], num_classes=c['Kc'], encoder=dict(ENCODER, num_layers=c['L']))
-    model = ddp_amd.build_segmentor(seg_cfg(timesteps=c['K'], randsteps=c['r'], bit_scale=c['bit_scale'], accumulation=c['accumulation'],
-                                            diffusion=c['sampler'], sample_range=(0, 0.999), time_difference=c['td'], decode_head=head))
-    model.load_state_dict(P.state_dict(c), strict=True)
-    return model.to(dev).eval()
-
-
 @pytest.mark.parametrize('name', ['seg_kc19_7x13', 'seg_kc255_5x10_r2', 'seg_ddpm_7x13'])
 def test_plugin_seg_prior(dev, name):
     c = P.CASES[name]
     _, (x, noise, sn) = _state(c, dev)
     t = c['t_start']
     img_prior = _image_frame(c, P.prior(c, 0)).to(dev)
-    model = _seg_plugin(c, dev)
+    model = support.seg_plugin(c, dev, P.state_dict(c))
     want, _ = P.expected(c, 0)
     if c['sampler'] == 'ddim':
         sample, kw = model.ddim_sample, dict(noise=noise)
@@ -433,21 +367,11 @@ def test_plugin_seg_prior(dev, name):
 
 @pytest.mark.parametrize('name', ['depth_9x14', 'depth_5x10_r2', 'depth_1x37_bins'])
 def test_plugin_depth_prior(dev, name):
-    import ddp_amd
-    from test_host_logic import ENCODER, POSENC
     c = P.CASES[name]
     _, (x, noise, _) = _state(c, dev)
     t = c['t_start']
     img_prior = _image_frame(c, P.prior(c, 0)).to(dev)
-    head = dict(type='DeformableHeadWithTime', in_channels=[256], channels=256, in_index=[0], dropout_ratio=0., scale_up=False,
-                min_depth=c['min_depth'], max_depth=c['max_depth'], use_eps=True, align_corners=False, num_feature_levels=1,
-                encoder=dict(ENCODER, num_layers=c['L']), positional_encoding=POSENC)
-    if c['n_bins']:
-        head.update(classify=True, n_bins=c['n_bins'], bins_strategy='UD', norm_strategy=c['norm'])
-    model = ddp_amd.build_depther(dict(type='DDP', bit_scale=c['bit_scale'], timesteps=c['K'], randsteps=c['r'], time_difference=c['td'],
-                                       min_depth=c['min_depth'], max_depth=c['max_depth'], test_cfg=dict(mode='whole'), decode_head=head))
-    model.load_state_dict(P.state_dict(c), strict=True)
-    model = model.to(dev).eval()
+    model = support.depth_plugin(c, dev, P.state_dict(c))
     out = model.sample(x, None, noise=noise, prior=img_prior, t_start=t)
     e = _rel(out.cpu(), P.expected(c, 0)[0])
     e_t = _rel(model.sample(x, None, noise=noise, t_start=t).cpu(), P.expected(c, 'noise')[0])
@@ -475,21 +399,13 @@ def test_plugin_depth_prior(dev, name):
 
 def test_plugin_bev_prior(dev):
     """the bev plugin class has the reference's six classes: the geometry of bev_kc8_r1 with 6"""
-    import ddp_amd
-    from test_host_logic import ENCODER, POSENC
     c = dict(P.CASES['bev_kc8_r1'], Kc=6, name='bev_kc6_plugin')
     sd, (x, noise, _) = _state(c, dev)
     t = c['t_start']
     pr = P.prior(c, 0)
     img_prior = _image_frame(c, pr).to(dev)
-    scopes = S.bev_scopes(c)
-    head = ddp_amd.BEVDeformableHeadWithTime(num_feature_levels=1, encoder=dict(ENCODER, num_layers=c['L']), positional_encoding=POSENC,
-                                             classes=list('abcdef'), loss='focal', grid_transform=scopes)
-    model = ddp_amd.BEVDDP(bit_scale=c['bit_scale'], timesteps=c['K'], randsteps=c['r'], feat_channels=c['Cx'], threshold=c['threshold'],
-                           time_difference=c['td'])
-    model.load_state_dict({k: v for k, v in sd.items() if not k.startswith('decode_head.')}, strict=True)
-    head.load_state_dict({k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, strict=True)
-    model, head = model.to(dev).eval(), head.to(dev).eval()
+    model, head = support.bev_plugin(sd, dev, c['L'], S.bev_scopes(c), bit_scale=c['bit_scale'], timesteps=c['K'], randsteps=c['r'],
+                                     feat_channels=c['Cx'], threshold=c['threshold'], time_difference=c['td'])
     out = model.ddim_sample([x], head, noise=noise, prior=img_prior, t_start=t)
     want = P.run_from(c, P.starts_of(c, pr, t), t)
     away = P.run_from(c, S.inputs(c)[1], t)

@@ -17,6 +17,7 @@ import torch
 import config_space_cases as S
 import prior_start_cases as P
 from ddp_amd import _lib, schedule
+from support import refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -310,21 +311,12 @@ def test_host_side_places_are_the_headers_formulas():
             assert rc0 == 0 and min(prior_at, start_at) == total0 - trailing
 
 
-def _refused(lib, cfg, *words):
-    n = C.c_size_t(0)
-    for entry in (lib.ddp_query_workspace, lib.ddp_query_const_workspace):
-        assert entry(C.byref(cfg), C.byref(n)) == -1               # DDP_E_BADCFG
-        msg = lib.ddp_last_error()
-        for w in words:
-            assert w.encode() in msg, msg
-
-
 def test_refusals_carry_their_message():
     lib = _lib.load()
     # bev with more than 32 classes: the flag's own message in front of the class limit's
     b = dict(P.CASES['bev_kc9_r2'], Kc=33)
-    _refused(lib, _with(S.make_cfg(b), _lib.FLAG_PRIOR_START), 'DDP_FLAG_PRIOR_START', '32')
-    _refused(lib, S.make_cfg(b), 'bev supports at most 32 classes')
+    refused(lib, _with(S.make_cfg(b), _lib.FLAG_PRIOR_START), 'DDP_FLAG_PRIOR_START', '32')
+    refused(lib, S.make_cfg(b), 'bev supports at most 32 classes')
     assert S.query(lib, _with(S.make_cfg(dict(b, Kc=32)), _lib.FLAG_PRIOR_START))[0] == 0
     # seg with 256 classes is accepted (every byte value is a class)
     assert S.query(lib, _with(S.make_cfg(P.CASES['seg_kc256_3x11']), _lib.FLAG_PRIOR_START))[0] == 0
@@ -346,8 +338,8 @@ def test_refusals_carry_their_message():
     # bits 8192 and 32768 are still bits nobody defines
     for bit in (8192, 32768):
         for extra in (bit, bit | _lib.FLAG_PRIOR_START):
-            _refused(lib, _with(S.make_cfg(P.CASES['seg_kc19_7x13']), extra), 'unknown flags')
-            _refused(lib, _with(S.make_cfg(P.CASES['depth_9x14']), extra), 'unknown flags')
+            refused(lib, _with(S.make_cfg(P.CASES['seg_kc19_7x13']), extra), 'unknown flags')
+            refused(lib, _with(S.make_cfg(P.CASES['depth_9x14']), extra), 'unknown flags')
 
 
 # ---- host layer ---------------------------------------------------------------------------------------------------------------------

@@ -29,66 +29,21 @@ import torch
 
 import config_space_cases as S
 import score_prior_cases as P
+import support
 from ddp_amd import _lib
-from test_hip_parity import REL
+from support import REL, dev, guards_ok as _guards_ok  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def routes(c):
-    """(id, gemm, flags): both engines and every flag that selects another route for the case"""
-    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False)),
-         ('unfused-prologue', 'bf16x3', dict(fused_prologue=False))]
-    if c['sampler'] == 'ddim':
-        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
-        if c['r'] == 1:
-            v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
-    else:
-        v += [('chain', 'bf16x3', dict(ddpm_chain=True)), ('chain-unfused-tail', 'bf16x3', dict(ddpm_chain=True, fused_tail=False)),
-              ('chain-sb-head', 'bf16x3', dict(ddpm_chain=True, nchw_head=False))]
-    return v
-
-
-ROUTES = {(n, vid): (gemm, fl) for n, c in P.CASES.items() for vid, gemm, fl in routes(c)}
-_SD, _IN = {}, {}
-
-
-def _state(c, dev):
-    if c['name'] not in _SD:
-        _SD[c['name']] = S.state_dict(c)
-        _IN[c['name']] = tuple(None if t is None else t.to(dev) for t in S.inputs(c))
-    return _SD[c['name']], _IN[c['name']]
+ROUTES = {(n, vid): (gemm, fl) for n, c in P.CASES.items() for vid, gemm, fl in P.routes(c)}
+_state = support.state_cache(S.state_dict, S.inputs)
 
 
 def _engine(c, dev, gemm='bf16x3', batch=None, **kw):
     """DDPEngine of the (seeded) case on a guarded, NaN-patterned workspace of exactly the queried size.  The map of a score_prior engine
     holds the PATTERN afterwards (a NaN: it reads as 0); the caller sets or clears it, as the library's contract says."""
-    from ddp_amd.engine import DDPEngine
-    ekw = S.engine_kwargs(c)
-    if batch is not None:
-        ekw['batch'] = batch
-    eng = DDPEngine(_state(c, dev)[0], 'seg', device=dev, gemm=gemm, **kw, **ekw)
-    n = eng.workspace.numel()
-    assert n * 4 == eng._workspace_bytes()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    return eng
-
-
-def _guards_ok(eng):
-    bits = eng.guarded.view(torch.int32)
-    return int((bits[:GUARD] != PATTERN).sum()) == 0 and int((bits[-GUARD:] != PATTERN).sum()) == 0
+    return support.engine(_state(c, dev)[0], 'seg', S.engine_kwargs(c), dev, gemm, batch, exact=True, **kw)
 
 
 def _sample(eng, c, dev, pm=None, sl=None, seed=None):
@@ -106,15 +61,6 @@ def _sample(eng, c, dev, pm=None, sl=None, seed=None):
     torch.cuda.synchronize()
     assert _guards_ok(eng), f'{c["name"]}: workspace guards overwritten'
     return out.cpu()
-
-
-def _rel_live(got, want, total):
-    """max-rel over the entries the prior leaves in (an excluded entry's score is -1e30 on both sides: it would be the whole scale)"""
-    live = P.clamp(total) > -P.CLAMP
-    if not bool(live.any()):                                               # (one class, excluded everywhere: the uniform shift)
-        live = torch.ones_like(live)
-    d = (got.double() - want.double()).abs()[live].max()
-    return float(d / want.double()[live].abs().max())
 
 
 def test_bars():
@@ -182,7 +128,7 @@ def test_output_and_decisions_match_the_expectation(dev, name, vid, kind):
     eng = _engine(c, dev, gemm, score_prior=True, record_steps=True, **fl)
     got = _sample(eng, c, dev, pm)
     rec = eng.step_record().cpu()                                          # (K, B, r, h, w)
-    err = _rel_live(got, e['out'], pm)
+    err = P.rel_live(got, e['out'], pm)
     agree = float((rec == e['record']).float().mean())
     print(f'SCORE-PRIOR {name}[{vid}]/{kind}: max-rel {err:.2e} (bar {REL:.0e}), decisions equal {agree:.4f}')
     assert torch.isfinite(got).all()
@@ -362,33 +308,6 @@ def test_engine_score_prior_methods(dev):
     assert torch.equal(heng.head_forward(feat, None).cpu(), _engine(c, dev).head_forward(feat, None).cpu()) and _guards_ok(heng)
 
 
-class _PoolBackbone(torch.nn.Module):
-    """a stand-in backbone whose feature map depends on the image it is given: the image pooled to (h, w) and spread over 256 channels
-    by a fixed seeded projection"""
-
-    def __init__(self, h, w):
-        super().__init__()
-        self.hw = (h, w)
-        self.register_buffer('proj', torch.randn(256, 3, generator=torch.Generator().manual_seed(17)))
-
-    def forward(self, img):
-        p = torch.nn.functional.adaptive_avg_pool2d(img, self.hw)
-        return [torch.einsum('oc,bchw->bohw', self.proj, p).contiguous()]
-
-
-def _seg_plugin(c, dev, sd, **kw):
-    import ddp_amd
-    from test_host_logic import ENCODER, seg_cfg
-    head = dict(seg_cfg()['decode_head'], num_classes=c['Kc'], encoder=dict(ENCODER, num_layers=c['L']))
-    model = ddp_amd.build_segmentor(seg_cfg(timesteps=c['K'], randsteps=c['r'], bit_scale=c['bit_scale'], accumulation=c['accumulation'],
-                                            diffusion=c['sampler'], sample_range=(0, 0.999), time_difference=c['td'], decode_head=head,
-                                            noise_seed=5, **kw))
-    model.load_state_dict(sd, strict=True)
-    model = model.to(dev).eval()
-    model.backbone = _PoolBackbone(c['h'], c['w']).to(dev)
-    return model
-
-
 @pytest.mark.parametrize('name', ['kc19_8x12_b2', 'ddpm_7x13'])
 def test_plugin_score_prior_is_the_engine_fed_the_resized_map(dev, name):
     """simple_test / forward / whole_inference / encode_decode with ``score_prior=`` in the frame of the image == the engine (seeded with
@@ -400,7 +319,7 @@ def test_plugin_score_prior_is_the_engine_fed_the_resized_map(dev, name):
     c = P.seeded(P.CASES[name], 'soft')
     B, h, w = c['B'], c['h'], c['w']
     sd = S.state_dict(c)
-    model = _seg_plugin(c, dev, sd)
+    model = support.seg_plugin(c, dev, sd, pool_backbone=True, noise_seed=5)
     H, W = 4 * h, 4 * w
     img = torch.randn(B, 3, H, W, generator=torch.Generator().manual_seed(23)).to(dev)
     meta = [dict(ori_shape=(H, W, 3), img_shape=(H, W, 3), pad_shape=(H, W, 3), flip=False)] * B
@@ -435,7 +354,7 @@ def test_plugin_score_prior_is_the_engine_fed_the_resized_map(dev, name):
 
 def test_plugin_self_aligned_predict(dev):
     import ddp_amd
-    from test_host_logic import ENCODER, seg_cfg
+    from support import ENCODER, seg_cfg
     c = P.seeded(P.CASES['kc19_7x13_b3'], 'soft')
     sd, (x, noise, _) = _state(c, dev)
     pm = P.prior_map(c, 'soft')

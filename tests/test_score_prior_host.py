@@ -18,6 +18,7 @@ import class_prior_cases as PC
 import config_space_cases as S
 import score_prior_cases as P
 from ddp_amd import _lib
+from support import refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -159,13 +160,7 @@ def test_both_priors_expectation_decides_with_margin(name):
     assert not torch.equal(alone['out'], e32['out'])                                        # the class rows are felt on top of the map
 
 
-def _rel_live(got, want, pm):
-    """max-rel over the entries the map leaves in (an excluded entry's score is -1e30 on both sides: it would be the whole scale)"""
-    live = P.clamp(pm) > -P.CLAMP
-    if not bool(live.any()):                                               # (one class, excluded everywhere: the uniform shift)
-        live = torch.ones_like(live)
-    d = (got.double() - want.double()).abs()[live].max()
-    return float(d / want.double()[live].abs().max())
+_rel_live = P.rel_live
 
 
 @pytest.mark.parametrize('name', list(P.CASES))
@@ -283,15 +278,6 @@ def test_caller_regions_tile_the_end_of_the_workspace():
     assert caller_regions(flagless, S.query(lib, flagless)[1]) == {}
 
 
-def _refused(lib, cfg, *words):
-    n = C.c_size_t(0)
-    for entry in (lib.ddp_query_workspace, lib.ddp_query_const_workspace):
-        assert entry(C.byref(cfg), C.byref(n)) == -1               # DDP_E_BADCFG
-        msg = lib.ddp_last_error()
-        for w in words:
-            assert w.encode() in msg, msg
-
-
 def test_refusals_carry_their_message():
     import prior_start_cases as PS
     import seeded_noise_util as U
@@ -300,7 +286,7 @@ def test_refusals_carry_their_message():
     for other in ('depth_9x14', 'depth_1x37_bins', 'bev_kc8_r1', 'bev_kc9_r2'):
         base = S.make_cfg(PS.CASES[other])
         assert S.query(lib, base)[0] == 0
-        _refused(lib, _with(base, _lib.FLAG_SCORE_PRIOR), 'DDP_FLAG_SCORE_PRIOR exists for the segmentation sampler only')
+        refused(lib, _with(base, _lib.FLAG_SCORE_PRIOR), 'DDP_FLAG_SCORE_PRIOR exists for the segmentation sampler only')
     n = C.c_size_t(0)
     for case in ('fcn_ddim', 'fcn_ddpm'):
         for flags in (0, _lib.FLAG_SEEDED_NOISE, _lib.FLAG_STEP_RECORD):
@@ -317,7 +303,7 @@ def test_refusals_carry_their_message():
     # the bits nobody defines stay refused, with and without the new flag
     for bit in (8192, 32768, 262144, 1 << 19, 1 << 21, 1 << 30):
         for extra in (bit, bit | _lib.FLAG_SCORE_PRIOR):
-            _refused(lib, _with(S.make_cfg(seg), extra), 'unknown flags')
+            refused(lib, _with(S.make_cfg(seg), extra), 'unknown flags')
     # what combines: every other flag of ddp_sample, 256 classes included
     for name, c in P.CASES.items():
         c = dict(c, seed=1)
@@ -443,7 +429,7 @@ def test_plugin_surface_without_a_device():
 
 def test_fcn_head_segmentor_raises():
     import ddp_amd
-    from test_host_logic import seg_cfg
+    from support import seg_cfg
     head = dict(type='FCNHeadWithTime', in_channels=256, channels=256, in_index=0, num_convs=1, num_classes=19, dropout_ratio=0.,
                 norm_cfg=None, align_corners=False)
     model = ddp_amd.build_segmentor(seg_cfg(decode_head=head))

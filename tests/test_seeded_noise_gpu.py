@@ -23,34 +23,16 @@ import torch
 
 import config_space_cases as S
 import seeded_noise_util as U
+import support
 from ddp_amd import _lib
-from test_config_space_gpu import GUARD, PATTERN, _assert_guards, _expected, _launch_counts
+from support import assert_guards, dev, guard, launch_counts  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SEED = U.SEED
 
 
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def _guard(eng):
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=eng.device)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    assert eng.workspace.data_ptr() % 256 == 0
-    return eng
-
-
 def _engine(c, dev, seeded, batch=None, gemm='bf16x3', **flags):
-    from ddp_amd.engine import DDPEngine
-    kw = S.engine_kwargs(c)
-    if batch is not None:
-        kw['batch'] = batch
-    return _guard(DDPEngine(S.state_dict(c), c['task'], device=dev, gemm=gemm, seeded_noise=seeded, **flags, **kw))
+    return support.engine(S.state_dict(c), c['task'], S.engine_kwargs(c), dev, gemm, batch, seeded_noise=seeded, **flags)
 
 
 _FCN_MODELS = {}
@@ -69,9 +51,9 @@ def _fcn_engine(c, dev, seeded, batch=None, sampler=None, record_steps=False):
         model.load_state_dict(synthetic.make_fcn_segmentor_state_dict(c['num_convs'], c['Kc'], True, False, seed=31), strict=True)
         _FCN_MODELS[key] = model.to(dev).eval()
     model = _FCN_MODELS[key]
-    return _guard(FcnSamplerEngine(model.hot_path_state_dict(), model.decode_head, h=c['h'], w=c['w'], batch=batch or c['B'],
-                                   randsteps=c['r'], timesteps=c['K'], num_classes=c['Kc'], bit_scale=0.01, accumulation=True,
-                                   sampler=sampler or c['sampler'], device=dev, seeded_noise=seeded, record_steps=record_steps))
+    return guard(FcnSamplerEngine(model.hot_path_state_dict(), model.decode_head, h=c['h'], w=c['w'], batch=batch or c['B'],
+                                  randsteps=c['r'], timesteps=c['K'], num_classes=c['Kc'], bit_scale=0.01, accumulation=True,
+                                  sampler=sampler or c['sampler'], device=dev, seeded_noise=seeded, record_steps=record_steps))
 
 
 def _x(c, dev):
@@ -99,7 +81,7 @@ def _run(name, dev):
             eng.last_noise()
         out = eng.sample(x, seed=SEED, image_base=5, call=2)
         torch.cuda.synchronize()
-        _assert_guards(eng, name)
+        assert_guards(eng, name)
         _RUNS[name] = dict(out=out.cpu(), noise=eng.last_noise().clone(), eng=eng, x=x, c=c)
     return _RUNS[name]
 
@@ -143,7 +125,7 @@ def test_seeded_call_equals_unseeded_call_fed_the_generated_noise(dev, name):
         plain = _engine(r['c'], dev, False, **U.CASES[name][1])
     out = plain.sample(r['x'], r['noise'].clone())
     torch.cuda.synchronize()
-    _assert_guards(plain, name)
+    assert_guards(plain, name)
     assert torch.equal(out.cpu(), r['out'])
     with pytest.raises(_lib.DdpError, match='seed'):
         r['eng'].sample(r['x'], r['noise'])                       # noise= on a seeded engine
@@ -174,7 +156,7 @@ def test_ddpm_equals_unseeded_ddpm_fed_the_rebuilt_step_noise(dev, name):
     plain = make(False)
     out = plain.sample(r['x'], r['noise'].clone(), stack)
     torch.cuda.synchronize()
-    _assert_guards(plain, name)
+    assert_guards(plain, name)
     assert torch.equal(out.cpu(), r['out'])
     assert not torch.equal(plain.sample(r['x'], r['noise'].clone(), torch.zeros_like(stack)).cpu(), r['out'])    # the step noise does count
 
@@ -188,7 +170,7 @@ def test_batched_call_equals_single_image_calls(dev, name):
     one = _fcn_engine(c, dev, True, batch=1) if name in U.FCN_CASES else _engine(c, dev, True, batch=1, **U.CASES[name][1])
     for b in range(3):
         o = one.sample(r['x'][b:b + 1].clone(), seed=SEED, image_base=5 + b, call=2).cpu()
-        _assert_guards(one, name)
+        assert_guards(one, name)
         assert torch.equal(one.last_noise()[0], r['noise'][b]), f'{name}: noise of image {b}'
         assert torch.equal(o[0], r['out'][b]), f'{name}: output of image {b}'
 
@@ -208,7 +190,7 @@ def test_key_words_change_the_noise(dev, name):
     if r['c']['B'] > 1:                                             # image_base 6 is image_base 5 shifted by one image
         eng.sample(r['x'], seed=SEED, image_base=6, call=2)
         assert torch.equal(eng.last_noise()[:-1], base[1:])
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
 
 
 # ---- 5. graph -----------------------------------------------------------------------------------------------------------------
@@ -233,18 +215,18 @@ def test_graph_replay_picks_up_a_new_key(dev, name):
     assert torch.equal(out, want_b)
     with pytest.raises(_lib.DdpError, match='seed'):
         graph.replay(noise=noise_b)
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
 
 
 # ---- 6. / 7. fence and launch counts ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('name', sorted(U.PATHS))
 def test_launch_records_with_the_flag_clear_and_set(dev, name):
     c, flags = U.CASES[name]
-    want = _expected(U.PATHS[name], c['K'], c['L'])
+    want = S.expected_launches(U.PATHS[name], c['K'], c['L'])
     r = _run(name, dev)
     plain = _engine(c, dev, False, **flags)
-    got = _launch_counts(plain, r['x'], r['noise'].clone())
-    _assert_guards(plain, name)
+    got = launch_counts(plain, r['x'], r['noise'].clone())
+    assert_guards(plain, name)
     assert {t: got[t] for t in want} == want and got[0] == 0, (name, got)
     eng = r['eng']
     eng.prepare()
@@ -292,7 +274,7 @@ def test_record_and_noise_buffers_coexist(dev):
     out = both.sample(r['x'], seed=SEED, image_base=5, call=2)
     want = rec_only.sample(r['x'], r['noise'].clone())
     torch.cuda.synchronize()
-    _assert_guards(both, 'both')
+    assert_guards(both, 'both')
     assert torch.equal(out.cpu(), r['out']) and torch.equal(want.cpu(), r['out'])
     assert torch.equal(both.last_noise(), r['noise'])
     assert torch.equal(both.step_record(), rec_only.step_record()) and torch.equal(both.step_disagreement(), rec_only.step_disagreement())
@@ -306,7 +288,7 @@ def test_record_and_noise_buffers_coexist(dev):
 def _seg_plugin(dev, noise_seed, test_cfg=None):
     import ddp_amd
     from ddp_amd.utils import synthetic
-    from test_host_logic import ENCODER, seg_cfg
+    from support import ENCODER, seg_cfg
     cfg = seg_cfg(noise_seed=noise_seed, test_cfg=test_cfg or dict(mode='whole'),
                   decode_head=dict(seg_cfg()['decode_head'], num_classes=20, encoder=dict(ENCODER, num_layers=2)))
     model = ddp_amd.build_segmentor(cfg)
@@ -380,10 +362,9 @@ def test_plugin_aug_test_uses_one_call_value_per_augmentation(dev):
 
 def test_plugin_depther_and_bev_take_the_seed(dev):
     import ddp_amd
-    import test_plugin_gpu as P
     from ddp_amd.utils import synthetic
     sd = synthetic.make_state_dict('depth', 1, 6, 256, seed=2)
-    model = P._depth_model(dict(timesteps=2), sd)
+    model = support.depth_model(dict(timesteps=2), sd)
     model.noise_seed = 7
     g = torch.Generator().manual_seed(5)
     x = torch.randn((3, 256, 5, 9), generator=g).to(dev)
@@ -392,15 +373,8 @@ def test_plugin_depther_and_bev_take_the_seed(dev):
         assert torch.equal(model.sample(x[i:i + 1].contiguous(), image_base=2 + i)[0], whole[i])
     assert not torch.equal(model.sample(x, image_base=2, call=1), whole)
     c = U.CASES['bev_chain'][0]
-    sd = S.state_dict(c)
-    from test_host_logic import ENCODER, POSENC
-    scopes = S.bev_scopes(c)
-    head = ddp_amd.BEVDeformableHeadWithTime(num_feature_levels=1, encoder=dict(ENCODER, num_layers=c['L']), positional_encoding=POSENC,
-                                             classes=list('abcdef'), loss='focal', grid_transform=scopes)
-    bev = ddp_amd.BEVDDP(bit_scale=c['bit_scale'], timesteps=c['K'], randsteps=c['r'], feat_channels=c['Cx'], noise_seed=SEED)
-    bev.load_state_dict({k: v for k, v in sd.items() if not k.startswith('decode_head.')}, strict=True)
-    head.load_state_dict({k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, strict=True)
-    bev, head = bev.to(dev).eval(), head.to(dev).eval()
+    bev, head = support.bev_plugin(S.state_dict(c), dev, c['L'], S.bev_scopes(c), bit_scale=c['bit_scale'], timesteps=c['K'],
+                                   randsteps=c['r'], feat_channels=c['Cx'], noise_seed=SEED)
     r = _run('bev_chain', dev)
     assert torch.equal(bev.ddim_sample([r['x']], head, image_base=5, call=2).cpu(), r['out'])
 

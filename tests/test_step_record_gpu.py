@@ -28,11 +28,11 @@ import torch
 
 import bev_head_util as BU
 import config_space_cases as S
+import support
 from ddp_amd import _lib
 from golden_util import max_rel
 from oracle import ddp_oracle as O
-from test_config_space_gpu import GUARD, PATTERN, _assert_guards, _expected, _launch_counts
-from test_hip_parity import REL
+from support import REL, assert_guards, dev, guard, launch_counts, ref_disagreement  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -72,28 +72,8 @@ PATHS = {'seg_fused': 'seg_head7', 'seg_r2_cx96': 'seg_prologue', 'seg_unfused_t
 BEV_FIXTURES = ['prescale_05', 'seg3_r4', 'seg3_prescale_2_fusion', 'prescale_15_odd']
 
 
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def _guard(eng):
-    """move the engine onto a guarded workspace filled with the NaN pattern"""
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=eng.device)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    assert eng.workspace.data_ptr() % 256 == 0
-    return eng
-
-
 def _engine(c, dev, record, batch=None, gemm='bf16x3', **flags):
-    from ddp_amd.engine import DDPEngine
-    kw = S.engine_kwargs(c)
-    if batch is not None:
-        kw['batch'] = batch
-    return _guard(DDPEngine(S.state_dict(c), c['task'], device=dev, gemm=gemm, record_steps=record, **flags, **kw))
+    return support.engine(S.state_dict(c), c['task'], S.engine_kwargs(c), dev, gemm, batch, record_steps=record, **flags)
 
 
 _RUNS = {}
@@ -107,7 +87,7 @@ def _run(name, dev):
         args = (x.to(dev), noise.to(dev), sn.to(dev) if sn is not None else None)
         plain_eng = _engine(c, dev, False, **flags)
         plain = plain_eng.sample(*args).cpu()
-        _assert_guards(plain_eng, name)
+        assert_guards(plain_eng, name)
         eng = _engine(c, dev, True, **flags)
         with pytest.raises(_lib.DdpError, match='sample'):
             eng.step_record()
@@ -115,7 +95,7 @@ def _run(name, dev):
             eng.step_disagreement()
         out = eng.sample(*args)
         torch.cuda.synchronize()
-        _assert_guards(eng, name)
+        assert_guards(eng, name)
         _RUNS[name] = dict(out=out.cpu(), rec=eng.step_record().cpu(), map=eng.step_disagreement().cpu(), plain=plain, eng=eng, args=args)
     return _RUNS[name]
 
@@ -124,22 +104,6 @@ def _shapes(c):
     hh, wh = S.head_grid(c)
     dtype = dict(seg=torch.uint8, depth=torch.float32, bev=torch.int32)[c['task']]
     return (c['K'], c['B'], c['r'], hh, wh), dtype, (c['B'], hh, wh)
-
-
-def ref_disagreement(task, rec, out, threshold=0.5):
-    """the three definitions of include/ddp_mi355x.h in NumPy: rec (K,B,r,H,W), out (B,C,H,W) -> (B,H,W); depth in fp64"""
-    rec, out = rec.numpy(), out.numpy()
-    K, B, r, H, W = rec.shape
-    flat = rec.transpose(1, 0, 2, 3, 4).reshape(B, K * r, H, W)
-    if task == 'seg':
-        final = out.argmax(1)                                             # first maximum wins
-        return ((flat != final[:, None]).sum(1).astype(np.float32) / np.float32(K * r)).astype(np.float32)
-    if task == 'bev':
-        Kc = out.shape[1]
-        fin = out > np.float32(threshold)                                 # (B,Kc,H,W)
-        bits = ((flat.astype(np.int64)[:, :, None] >> np.arange(Kc)[None, None, :, None, None]) & 1).astype(bool)
-        return ((bits != fin[:, None]).sum((1, 2)).astype(np.float32) / np.float32(K * r * Kc)).astype(np.float32)
-    return flat.astype(np.float64).std(axis=1)                            # population form
 
 
 def _assert_map(task, rec, out, got, threshold=0.5):
@@ -175,12 +139,12 @@ def test_launch_records_with_the_flag_clear_and_set(dev, name):
     the record's own kernels carry no tag"""
     c, flags = CASES[name]
     x, noise, sn = S.inputs(c)
-    want = _expected(PATHS[name], c['K'], c['L'])
+    want = S.expected_launches(PATHS[name], c['K'], c['L'])
     extra = {}
     for record in (False, True):
         eng = _engine(c, dev, record, **flags)
-        got = _launch_counts(eng, x.to(dev), noise.to(dev), sn.to(dev) if sn is not None else None)
-        _assert_guards(eng, name)
+        got = launch_counts(eng, x.to(dev), noise.to(dev), sn.to(dev) if sn is not None else None)
+        assert_guards(eng, name)
         assert {t: got[t] for t in want} == want, (name, record, got)
         extra[record] = got[0]
     # the launches the flag adds (tag 0, which no launch of ddp_sample otherwise carries): k_step_disagreement once per call; bev
@@ -222,11 +186,11 @@ def test_seg_record_is_the_record_x0_trace(dev, name):
     c, flags = CASES[name]
     r = _run(name, dev)
     for record in (False, True):
-        eng = _guard(DDPEngine(S.state_dict(c), 'seg', device=dev, record_x0=True, record_steps=record,
-                               **dict(dict(gemm='bf16x3'), **flags), **S.engine_kwargs(c)))
+        eng = guard(DDPEngine(S.state_dict(c), 'seg', device=dev, record_x0=True, record_steps=record,
+                              **dict(dict(gemm='bf16x3'), **flags), **S.engine_kwargs(c)))
         out = eng.sample(*r['args'])
         torch.cuda.synchronize()
-        _assert_guards(eng, name)
+        assert_guards(eng, name)
         assert torch.equal(out.cpu(), r['out'])
         trace = eng.x0_trace().cpu()                                      # (K, B*r, h, w)
         assert torch.equal(trace.reshape(r['rec'].shape), r['rec'])
@@ -278,10 +242,10 @@ def test_bev_record_matches_the_reference_fixtures(dev, name, route):
     assert float(g['thr_margin']) >= 1e-3
     kw = dict(gemm='f32') if route == 'f32' else dict(gemm='bf16x3', fused_tail=route != 'unfused-tail')
     args = (x.to(dev), noise.unsqueeze(0).contiguous().to(dev))
-    plain = _guard(DDPEngine(sd, 'bev', device=dev, **kw, **BU.engine_kwargs(cfg))).sample(*args).cpu()
-    eng = _guard(DDPEngine(sd, 'bev', device=dev, record_steps=True, **kw, **BU.engine_kwargs(cfg)))
+    plain = guard(DDPEngine(sd, 'bev', device=dev, **kw, **BU.engine_kwargs(cfg))).sample(*args).cpu()
+    eng = guard(DDPEngine(sd, 'bev', device=dev, record_steps=True, **kw, **BU.engine_kwargs(cfg)))
     out = eng.sample(*args).cpu()
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
     assert torch.equal(out, plain)
     rec, dmap = eng.step_record().cpu(), eng.step_disagreement().cpu()
     want = g['prob_steps'] > thr                                          # (K,r,6,H,W)
@@ -299,17 +263,16 @@ def test_bev_record_above_eight_classes_matches_the_restatement(dev, name, route
     """9 .. 32 classes (and 8 on the separate kernels): k_bev_record thresholds the logits rows itself - bit c of every step and
     replica against prob_c > threshold of the restatement's per-step head outputs, c up to 31.  Cases and seeds are those of
     tests/test_bev_head_gpu.py (every probability of every step >= 1e-3 off the threshold; _oracle asserts it)"""
-    import test_bev_head_gpu as T
     from ddp_amd.engine import DDPEngine
-    cfg = T.ORACLE_CASES[name]
-    sd, x, noise, _ = T._oracle(cfg)
-    trace = T._REF[(name, 1)][4]
+    cfg = BU.ORACLE_CASES[name]
+    sd, x, noise, _ = BU.oracle(cfg)
+    trace = BU.ORACLE_REF[(name, 1)][4]
     assert min(t['margin'] for t in trace) >= 1e-3
     thr, Kc = cfg.get('threshold', 0.5), cfg.get('num_classes', 6)
     kw = dict(gemm='f32') if route == 'f32' else dict(gemm='bf16x3', fused_tail=route != 'unfused-tail')
-    eng = _guard(DDPEngine(sd, 'bev', device=dev, record_steps=True, **kw, **BU.engine_kwargs(cfg)))
+    eng = guard(DDPEngine(sd, 'bev', device=dev, record_steps=True, **kw, **BU.engine_kwargs(cfg)))
     out = eng.sample(x.to(dev), noise.contiguous().to(dev)).cpu()
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
     rec, dmap = eng.step_record().cpu(), eng.step_disagreement().cpu()
     want = torch.stack([t['prob'] > thr for t in trace])                 # (K,r,Kc,H,W)
     assert tuple(rec.shape) == (cfg['timesteps'], 1, cfg['randsteps']) + tuple(want.shape[3:])
@@ -336,7 +299,7 @@ def test_single_record_gives_zeros(dev, task):
     x, noise, _ = S.inputs(c)
     eng = _engine(c, dev, True)
     out = eng.sample(x.to(dev), noise.to(dev)).cpu()
-    _assert_guards(eng, c['name'])
+    assert_guards(eng, c['name'])
     dmap = eng.step_disagreement().cpu()
     if task != 'bev':                      # (bev: out is the step's probability, so its own threshold bits agree as well)
         assert torch.equal(dmap, torch.zeros_like(dmap))
@@ -353,7 +316,7 @@ def test_batched_call_equals_single_image_calls(dev, name):
     one = _engine(c, dev, True, batch=1, **flags)
     for b in range(c['B']):
         o = one.sample(x[b:b + 1].clone().to(dev), noise[b:b + 1].clone().to(dev)).cpu()
-        _assert_guards(one, name)
+        assert_guards(one, name)
         assert torch.equal(o[0], r['out'][b])
         assert torch.equal(one.step_record().cpu()[:, 0], r['rec'][:, b]), f'{name}: record of image {b}'
         assert torch.equal(one.step_disagreement().cpu()[0], r['map'][b]), f'{name}: map of image {b}'
@@ -378,7 +341,7 @@ def test_graph_replay_refreshes_record_and_map(dev, name):
     torch.cuda.synchronize()
     assert torch.equal(out.cpu(), want2)
     assert torch.equal(eng.step_record().cpu(), rec2) and torch.equal(eng.step_disagreement().cpu(), map2)
-    _assert_guards(eng, name)
+    assert_guards(eng, name)
 
 
 # ---- 5. plugin classes ----------------------------------------------------------------------------------------------------------
@@ -404,10 +367,9 @@ def _check_plugin(model, call, task, threshold=0.5):
 
 
 def test_plugin_segmentor_return_steps(dev):
-    import test_plugin_gpu as P
     from golden_util import load_case
     cfg, sd, x, noise, _, g = load_case('seg_ade_k3')
-    model = P._seg_model(cfg)
+    model = support.seg_model(cfg)
     model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval()
     dx, dn = x.to(dev), noise.unsqueeze(0).to(dev)
@@ -417,10 +379,9 @@ def test_plugin_segmentor_return_steps(dev):
 
 
 def test_plugin_segmentor_ddpm_return_steps(dev):
-    import test_plugin_gpu as P
     from golden_util import load_case
     cfg, sd, x, noise, step_noise, g = load_case('seg_ddpm')
-    model = P._seg_model(cfg)
+    model = support.seg_model(cfg)
     model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval()
     kw = dict(noise=noise.unsqueeze(0).to(dev), step_noise=step_noise.unsqueeze(1).to(dev))
@@ -457,39 +418,28 @@ def test_plugin_fcn_loop_return_steps(dev):
         if cfg['accumulation'] is False:                                   # the output is the last step's scores: its argmax is recorded
             if cfg['randsteps'] == 1:
                 assert torch.equal(rec[-1, 0, 0].long(), out[0].argmax(0))
-        n = eng.workspace.numel()
-        buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-        buf.view(torch.int32).fill_(PATTERN)
-        eng.guarded, eng.workspace, eng._prepared = buf, buf[GUARD:GUARD + n], False
+        guard(eng)._prepared = False
         again = eng.sample(dx, dn, dsn)
         torch.cuda.synchronize()
-        _assert_guards(eng, name)
+        assert_guards(eng, name)
         assert torch.equal(again, out) and torch.equal(eng.step_record(), rec) and torch.equal(eng.step_disagreement(), dmap)
 
 
 def test_plugin_depther_return_steps(dev):
-    import test_plugin_gpu as P
     from golden_util import load_case
     cfg, sd, x, noise, _, g = load_case('depth_k3_r2')
-    model = P._depth_model(cfg, sd)
+    model = support.depth_model(cfg, sd)
     dx, dn = x.to(dev), noise.unsqueeze(0).to(dev)
     _check_plugin(model, lambda rs: model.sample(dx, None, noise=dn, return_steps=rs) if rs else model.sample(dx, None, noise=dn), 'depth')
     assert max_rel(model.sample(dx, None, noise=dn).cpu(), g['out']) < REL
 
 
 def test_plugin_bev_return_steps(dev):
-    import ddp_amd
     from golden_util import load_case
-    from test_host_logic import ENCODER, POSENC
     cfg, sd, x, noise, _, g = load_case('bev_fusion')
-    head = ddp_amd.BEVDeformableHeadWithTime(
-        num_feature_levels=1, encoder=dict(ENCODER, num_layers=cfg['num_layers']), positional_encoding=POSENC,
-        classes=list('abcdef'), loss='focal', grid_transform=dict(input_scope=cfg['input_scope'], output_scope=cfg['output_scope']))
-    model = ddp_amd.BEVDDP(bit_scale=cfg['bit_scale'], timesteps=cfg['timesteps'], randsteps=cfg['randsteps'],
-                           feat_channels=cfg['feat_channels'])
-    model.load_state_dict({k: v for k, v in sd.items() if not k.startswith('decode_head.')}, strict=True)
-    head.load_state_dict({k[len('decode_head.'):]: v for k, v in sd.items() if k.startswith('decode_head.')}, strict=True)
-    model, head = model.to(dev).eval(), head.to(dev).eval()
+    model, head = support.bev_plugin(sd, dev, cfg['num_layers'], dict(input_scope=cfg['input_scope'], output_scope=cfg['output_scope']),
+                                     bit_scale=cfg['bit_scale'], timesteps=cfg['timesteps'], randsteps=cfg['randsteps'],
+                                     feat_channels=cfg['feat_channels'])
     dx, dn = [x.to(dev)], noise.unsqueeze(0).to(dev)
     _check_plugin(model, lambda rs: model.ddim_sample(dx, head, noise=dn, return_steps=rs) if rs else model.ddim_sample(dx, head, noise=dn),
                   'bev', model.threshold)

@@ -15,6 +15,7 @@ import pytest
 import config_space_cases as S
 from ddp_amd import _lib
 from ddp_amd.engine import step_record_sizes
+from support import lib, round256  # noqa: F401
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'step_record', 'parent_workspace_bytes.json')
 VARIANTS = {'bf16x3': ('bf16x3', {}), 'f32': ('f32', {}), 'unfused-layer': ('bf16x3', dict(fused_layer=False)),
@@ -23,18 +24,9 @@ FCN_HEADS = ((0, 1), (2, 1), (1, 2))            # (num_convs, dilation)
 
 
 @pytest.fixture(scope='module')
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope='module')
 def golden():
     with open(GOLDEN) as f:
         return json.load(f)
-
-
-def round256(n):
-    return (n + 255) // 256 * 256
 
 
 def with_flags(cfg, extra):

@@ -27,25 +27,16 @@ import torch
 
 import fcn_gn_cases as G
 import next_rows_cases as N
-import test_fcn_gn_gpu as TG
-import test_hip_parity as TP
-import test_next_rows_gpu as TN
+import support
 import workspace_history_cases as W
 from ddp_amd import _lib
 from golden_util import load_case, max_rel
-from test_config_space_gpu import GUARD, PATTERN, _assert_guards
-from test_hip_parity import REL
-from test_next_rows_gpu import Guarded
+from support import PATTERN, REL, Guarded, assert_guards as _assert_guards, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 MSDA_BAR = 1e-5          # the literal of tests/test_hip_parity.py::test_msda_forward_lds (it has no name there)
 NAN = W.FILLS['nan']
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -54,7 +45,7 @@ def _release_what_the_module_holds():
     collected after this one start from the allocator and the memory they would have found without it"""
     yield
     import gc
-    for d in (_PW, _IN, _FRESH, _LOOP_FRESH, _ENTRY, _ENTRY_FRESH, TN._NECK_DEV, W._OwnNoise._cache):
+    for d in (_PW, _IN, _FRESH, _LOOP_FRESH, _ENTRY, _ENTRY_FRESH, N.NECK_DEV, W._OwnNoise._cache):
         d.clear()
     gc.collect()
     torch.cuda.synchronize()
@@ -85,10 +76,7 @@ _PW, _IN, _FRESH = {}, {}, {}
 
 
 def _guarded(n, dev, word):
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    ws = buf[GUARD:GUARD + n]
-    assert ws.data_ptr() % 256 == 0
+    buf, ws = support.guarded_buffer(n, dev)
     _fill(ws, word)
     return buf, ws
 
@@ -302,8 +290,8 @@ _LOOP_FRESH = {}
 def _loop(name, dev, batch=None):
     src, c = W.LOOPS[name]
     if src == 'next_rows_cases':
-        return TN._Loop(c, dev, 'bf16x3', batch)
-    return TG._Loop(c, G.loop_state(c), dev, batch)
+        return N.device_loop(c, dev, 'bf16x3', batch)
+    return G.device_loop(c, G.loop_state(c), dev, batch)
 
 
 def _loop_inputs(name, dev, other=False, batch=None):
@@ -410,10 +398,10 @@ class _Entry:
             sdf, sdm = _roll(sdf), _roll(sdm)
         xs, lv = [x * scale for x in xs], [x * scale for x in lv]
         if self.kind == 'neck_fpn':
-            return TN._run_fpn(c, self.dev, sdf, xs, flags, g)[0]
+            return N.run_fpn(c, self.dev, sdf, xs, flags, g)[0]
         if self.kind == 'neck_msm':
-            return [TN._run_msm(c, self.dev, sdm, lv, False, flags, g)[0]]
-        return [TN._run_chain(c, self.dev, sdf, sdm, xs, False, flags, g)[0]]
+            return [N.run_msm(c, self.dev, sdm, lv, False, flags, g)[0]]
+        return [N.run_chain(c, self.dev, sdf, sdm, xs, False, flags, g)[0]]
 
     # FCN heads
     def _fcn(self, other):
@@ -435,7 +423,7 @@ class _Entry:
                 sd = _roll(sd)
             feat, temb = N.fcn_inputs(c) if bn else G.head_inputs(c)
             if bn:
-                head = TN._fcn_head(c, sd, self.dev)
+                head = N.fcn_head(c, sd, self.dev)
                 arr, keep = head.conv_array()
                 keep = (keep, head)
             else:
@@ -448,7 +436,7 @@ class _Entry:
         out = torch.full((c['maps'], c['classes'], c['h'], c['w']), float('nan'), device=self.dev)
         _lib.check(self.lib.ddp_fcn_head_forward(arr, c['num_convs'], c['dilation'], wseg.data_ptr(), bseg.data_ptr(), c['classes'],
                                                  feat.data_ptr(), temb.data_ptr() if temb is not None else None, c['maps'], c['h'], c['w'],
-                                                 out.data_ptr(), g.ptr(), TN._stream(self.dev)), self.lib)
+                                                 out.data_ptr(), g.ptr(), support.stream(self.dev)), self.lib)
         return [out]
 
     # the LDS gather
@@ -468,7 +456,7 @@ class _Entry:
         value = (value * scale).contiguous()
         out = torch.full((r * h * w, 256), float('nan'), device=self.dev)
         _lib.check(self.lib.ddp_msda_forward_lds(value.data_ptr(), samp.data_ptr(), mean.data_ptr() if self.guess else None, out.data_ptr(),
-                                                 r * h * w, h, w, g.ptr(), TN._stream(self.dev)), self.lib)
+                                                 r * h * w, h, w, g.ptr(), support.stream(self.dev)), self.lib)
         return [out]
 
     # the bf16x3 stream GEMM
@@ -482,7 +470,7 @@ class _Entry:
         a, w, b = self.t[other]
         a = (a * scale).contiguous()
         out = torch.full((m, n), float('nan'), device=self.dev)
-        _lib.check(self.lib.ddp_linear_b3(a.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k, g.ptr(), TN._stream(self.dev)),
+        _lib.check(self.lib.ddp_linear_b3(a.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k, g.ptr(), support.stream(self.dev)),
                    self.lib)
         return [out]
 
@@ -490,7 +478,7 @@ class _Entry:
     def _init_head_forward(self):
         from oracle import ddp_oracle as O
         cfg, sd, _, _, _, gold = load_case(W.HEAD_FORWARD_CASE)
-        self.eng = TP._engine(cfg, sd, self.dev)
+        self.eng = support.fixture_engine(cfg, sd, self.dev)
         self.feat = gold['feat_step0'].to(self.dev).contiguous()
         self.temb = O.time_mlp(O.alpha_cosine_log_snr(torch.tensor([1.0])), sd).to(self.dev)
         self.ref = gold['logits_steps'][0]

@@ -10,18 +10,13 @@ import pytest
 import torch
 
 import config_space_cases as S
-import test_config_space_gpu as TC
+import support
 import workspace_history_cases as W
-from ddp_amd import _lib
-
-
-@pytest.fixture(scope='module')
-def lib():
-    return _lib.load()
+from support import lib  # noqa: F401
 
 
 def test_fills_hold_the_suite_pattern():
-    assert W.PATTERN == TC.PATTERN == 0x7FC0BEEF and W.FILLS['nan'] == TC.PATTERN
+    assert W.PATTERN == support.PATTERN == 0x7FC0BEEF and W.FILLS['nan'] == support.PATTERN
     assert sorted(W.FILLS.values()) == sorted([0x7FC0BEEF, 0x00000000, 0x3F800000, 0x7F800000, 0xFF7FFFFF, 0x41414141])
     as_float = {k: float(np.array([v], dtype=np.uint32).view(np.float32)[0]) for k, v in W.FILLS.items()}
     assert np.isnan(as_float['nan']) and as_float['zero'] == 0.0 and as_float['one'] == 1.0 and as_float['inf'] == float('inf')

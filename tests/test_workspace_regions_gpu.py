@@ -10,15 +10,12 @@ import pytest
 import torch
 
 import config_space_cases as S
+import support
 from ddp_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
-SHAPE = dict(B=2, r=2, h=3, w=5, K=2, L=1)
-CASES = {'seg': dict(S.CASES['seg_L12'], name='regions_seg', Kc=19, **SHAPE),
-         'depth': dict(S.CASES['depth_K1'], name='regions_depth', **SHAPE)}
+CASES = S.REGION_CASES
 # one byte per caller-written view.  seg: 0xA5 / 0x5A are >= num_classes (a free pixel / the ignore row); depth: 0x41414141 = 12.08 and
 # 0x40404040 = 3.004 are depths inside the range; 0x3C3C3C3C = 0.0115 is an ordinary class prior
 FILL = dict(hints={'seg': 0xA5, 'depth': 0x41}, prior={'seg': 0x5A, 'depth': 0x40}, class_prior={'seg': 0x3C})
@@ -39,10 +36,7 @@ def test_all_caller_regions_in_one_engine(task):
     want = _lib.FLAG_STEP_RECORD | _lib.FLAG_SEEDED_NOISE | _lib.FLAG_X0_HINTS | _lib.FLAG_PRIOR_START
     want |= _lib.FLAG_CLASS_PRIOR if seg else 0
     assert eng.cfg.flags & want == want
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.workspace = buf[GUARD:GUARD + n]
+    n = support.guard(eng).workspace.numel()
     written = dict(hints=eng.hints_view(), prior=eng.prior_view())
     if seg:
         written['class_prior'] = eng.class_prior_view()
@@ -51,8 +45,7 @@ def test_all_caller_regions_in_one_engine(task):
     x = S.inputs(c)[0].to(dev)
     out = eng.sample(x, seed=2024)
     torch.cuda.synchronize()
-    bits = buf.view(torch.int32)
-    assert int((bits[:GUARD] != PATTERN).sum()) == 0 and int((bits[-GUARD:] != PATTERN).sum()) == 0, 'workspace guards overwritten'
+    assert support.guards_ok(eng), 'workspace guards overwritten'
     assert bool(torch.isfinite(out).all())
     for k, v in written.items():
         assert bool((_bytes(v) == FILL[k][task]).all()), f'{task}: the {k} view lost its pattern'

@@ -7,11 +7,10 @@ test_class_prior_host.py; GPU companion: tests/test_workspace_regions_gpu.py.)""
 import ctypes as C
 import itertools
 
-import pytest
-
 import config_space_cases as S
 from ddp_amd import _lib
 from ddp_amd.engine import caller_regions, class_prior_places, prior_start_places, step_record_sizes
+from support import lib, round256  # noqa: F401
 
 TAIL = (_lib.FLAG_CLASS_PRIOR, _lib.FLAG_PRIOR_START, _lib.FLAG_X0_HINTS, _lib.FLAG_SEEDED_NOISE, _lib.FLAG_STEP_RECORD)
 TAIL_MASK = sum(TAIL)
@@ -24,15 +23,6 @@ NAMES = {_lib.FLAG_CLASS_PRIOR: ('cprior_rows', 'cprior_table'), _lib.FLAG_PRIOR
          _lib.FLAG_STEP_RECORD: ('step_rec', 'step_map')}
 FAKE_BASE = 1 << 40             # 256-aligned, never dereferenced: ddp_x0_trace only carves
 FCN_HEADS = ((0, 1), (2, 1), (1, 2))            # (num_convs, dilation)
-
-
-@pytest.fixture(scope='module')
-def lib():
-    return _lib.load()
-
-
-def round256(n):
-    return (n + 255) // 256 * 256
 
 
 def expected_names(flags):

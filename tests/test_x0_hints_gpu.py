@@ -15,77 +15,28 @@ cases, hint maps and the hinted expectation: tests/x0_hint_cases.py.)
 
 Every engine samples through a workspace that is filled with a NaN pattern and has 4 KiB guards at both ends (the carve of the two
 new buffers; a kernel that reads hint bytes nobody wrote shows: the pattern's bytes are classes < 150 and a NaN)."""
-import ctypes as C
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 import config_space_cases as S
+import support
 import x0_hint_cases as H
 from ddp_amd import _lib
 from ddpm_chain_cases import CHAIN_VS_CLEAR
 from oracle import ddp_oracle as O
-from test_hip_parity import REL
+from support import PATTERN, REL, FixedBackbone as _Backbone, dev, guards_ok as _guards_ok  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 1024
-PATTERN = 0x7FC0BEEF
-
-
-@pytest.fixture(scope='module')
-def dev():
-    return torch.device('cuda:0')
-
-
-def routes(c):
-    """(id, gemm, flags): both engines and every flag that selects another route for the case (tests/test_config_space_gpu.py)"""
-    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False)),
-         ('unfused-prologue', 'bf16x3', dict(fused_prologue=False))]
-    if c['task'] == 'seg' and c['sampler'] == 'ddim':
-        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
-        if c['r'] == 1:
-            v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
-    if c['task'] == 'seg' and c['sampler'] == 'ddpm':
-        v += [('chain', 'bf16x3', dict(ddpm_chain=True)), ('chain-unfused-tail', 'bf16x3', dict(ddpm_chain=True, fused_tail=False)),
-              ('chain-sb-head', 'bf16x3', dict(ddpm_chain=True, nchw_head=False))]
-    if c['task'] == 'depth' and not c['n_bins']:
-        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
-    return v
-
-
-ROUTES = {(n, vid): (gemm, fl) for n, c in H.CASES.items() for vid, gemm, fl in routes(c)}
-_SD, _IN = {}, {}
-
-
-def _state(c, dev):
-    if c['name'] not in _SD:
-        _SD[c['name']] = S.state_dict(c)
-        _IN[c['name']] = tuple(None if t is None else t.to(dev) for t in S.inputs(c))
-    return _SD[c['name']], _IN[c['name']]
+ROUTES = {(n, vid): (gemm, fl) for n, c in H.CASES.items() for vid, gemm, fl in H.routes(c)}
+_state = support.state_cache(S.state_dict, S.inputs)
 
 
 def _engine(c, dev, gemm='bf16x3', batch=None, **kw):
     """DDPEngine of the case on a guarded, NaN-patterned workspace.  The hint map of an x0_hints engine holds the PATTERN afterwards:
     the caller sets or clears the hints, as the library's contract says."""
-    from ddp_amd.engine import DDPEngine
-    sd, _ = _state(c, dev)
-    ekw = S.engine_kwargs(c)
-    if batch is not None:
-        ekw['batch'] = batch
-    eng = DDPEngine(sd, c['task'], device=dev, gemm=gemm, **kw, **ekw)
-    n = eng.workspace.numel()
-    buf = torch.empty(n + 2 * GUARD, dtype=torch.float32, device=dev)
-    buf.view(torch.int32).fill_(PATTERN)
-    eng.guarded = buf
-    eng.workspace = buf[GUARD:GUARD + n]
-    return eng
-
-
-def _guards_ok(eng):
-    bits = eng.guarded.view(torch.int32)
-    return int((bits[:GUARD] != PATTERN).sum()) == 0 and int((bits[-GUARD:] != PATTERN).sum()) == 0
+    return support.engine(_state(c, dev)[0], c['task'], S.engine_kwargs(c), dev, gemm, batch, **kw)
 
 
 def _sample(eng, c, dev, hints=None, sl=None):
@@ -103,22 +54,7 @@ def _sample(eng, c, dev, hints=None, sl=None):
 
 
 def _counts(eng, c, dev):
-    lib = eng.lib
-    _, (x, noise, sn) = _state(c, dev)
-    ms, n = C.c_float(0), C.c_int(0)
-    torch.cuda.synchronize()
-    _lib.check(lib.ddp_profile_begin(255), lib)
-    try:
-        eng.sample(x, noise, sn)
-        torch.cuda.synchronize()
-    finally:
-        rc = lib.ddp_profile_end(C.byref(ms), C.byref(n))
-    _lib.check(rc, lib)
-    counts = {}
-    for tag in range(11):
-        _lib.check(lib.ddp_profile_read(tag, C.byref(ms), C.byref(n)), lib)
-        counts[tag] = n.value
-    return counts
+    return support.launch_counts(eng, *_state(c, dev)[1])
 
 
 def _rel(a, b):
@@ -328,15 +264,6 @@ def test_engine_hint_methods(dev):
 
 
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------
-class _Backbone(torch.nn.Module):
-    def __init__(self, x):
-        super().__init__()
-        self.x = x
-
-    def forward(self, img):
-        return [self.x]
-
-
 def _image_frame_hints(c, hints_map, ratio=(3.5, 2.75)):
     """hints in the frame of a network input whose size is a NON-integer multiple of the map: every map pixel's value is written to
     the image pixels that F.interpolate(mode='nearest') reads for it - floor(dst * in / out) - and everything else is poison (seg:
@@ -355,23 +282,13 @@ def _image_frame_hints(c, hints_map, ratio=(3.5, 2.75)):
     return img
 
 
-def _seg_plugin(c, dev):
-    import ddp_amd
-    from test_host_logic import ENCODER, seg_cfg
-    head = dict(seg_cfg()['decode_head'], num_classes=c['Kc'], encoder=dict(ENCODER, num_layers=c['L']))
-    model = ddp_amd.build_segmentor(seg_cfg(timesteps=c['K'], randsteps=c['r'], bit_scale=c['bit_scale'], accumulation=c['accumulation'],
-                                            diffusion=c['sampler'], sample_range=(0, 0.999), time_difference=c['td'], decode_head=head))
-    model.load_state_dict(S.state_dict(c), strict=True)
-    return model.to(dev).eval()
-
-
 @pytest.mark.parametrize('name', ['seg_kc19_7x13', 'seg_kc255_5x10_r2', 'seg_ddpm_7x13'])
 def test_plugin_seg_hints(dev, name):
     c = H.CASES[name]
     _, (x, noise, sn) = _state(c, dev)
     hints = H.partial_hints(c)
     img_hints = _image_frame_hints(c, hints).to(dev)
-    model = _seg_plugin(c, dev)
+    model = support.seg_plugin(c, dev, S.state_dict(c))
     want, _ = H.expected(c, 'partial')
     if c['sampler'] == 'ddim':
         out = model.ddim_sample(x, None, noise=noise, hints=img_hints)
@@ -413,21 +330,11 @@ def test_plugin_seg_hints(dev, name):
 
 @pytest.mark.parametrize('name', ['depth_9x14', 'depth_5x10_r2', 'depth_1x37_bins'])
 def test_plugin_depth_hints(dev, name):
-    import ddp_amd
-    from test_host_logic import ENCODER, POSENC
     c = H.CASES[name]
     _, (x, noise, _) = _state(c, dev)
     hints = H.partial_hints(c)
     img_hints = _image_frame_hints(c, hints).to(dev)
-    head = dict(type='DeformableHeadWithTime', in_channels=[256], channels=256, in_index=[0], dropout_ratio=0., scale_up=False,
-                min_depth=c['min_depth'], max_depth=c['max_depth'], use_eps=True, align_corners=False, num_feature_levels=1,
-                encoder=dict(ENCODER, num_layers=c['L']), positional_encoding=POSENC)
-    if c['n_bins']:
-        head.update(classify=True, n_bins=c['n_bins'], bins_strategy='UD', norm_strategy=c['norm'])
-    model = ddp_amd.build_depther(dict(type='DDP', bit_scale=c['bit_scale'], timesteps=c['K'], randsteps=c['r'], time_difference=c['td'],
-                                       min_depth=c['min_depth'], max_depth=c['max_depth'], test_cfg=dict(mode='whole'), decode_head=head))
-    model.load_state_dict(S.state_dict(c), strict=True)
-    model = model.to(dev).eval()
+    model = support.depth_plugin(c, dev, S.state_dict(c))
     want, rec_want = H.expected(c, 'partial')
     out, rec, _ = model.sample(x, None, noise=noise, hints=img_hints, return_steps=True)
     e, e_rec = _rel(out.cpu(), want), _rel(rec.cpu(), rec_want)

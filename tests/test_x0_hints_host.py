@@ -17,6 +17,7 @@ import config_space_cases as S
 import x0_hint_cases as H
 from ddp_amd import _lib
 from oracle import ddp_oracle as O
+from support import refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -174,15 +175,6 @@ def test_flag_clear_gives_the_parents_workspace_sizes():
     assert seen > 60
 
 
-def _refused(lib, cfg, *words):
-    n = C.c_size_t(0)
-    for entry in (lib.ddp_query_workspace, lib.ddp_query_const_workspace):
-        assert entry(C.byref(cfg), C.byref(n)) == -1               # DDP_E_BADCFG
-        msg = lib.ddp_last_error()
-        for w in words:
-            assert w.encode() in msg, msg
-
-
 def test_refusals_carry_their_message():
     lib = _lib.load()
     # bev
@@ -190,15 +182,15 @@ def test_refusals_carry_their_message():
         for gemm in ('bf16x3', 'f32'):
             cfg = S.make_cfg(S.CASES[name], gemm)
             assert S.query(lib, cfg)[0] == 0
-            _refused(lib, _with(cfg, _lib.FLAG_X0_HINTS), 'DDP_FLAG_X0_HINTS', 'bev')
+            refused(lib, _with(cfg, _lib.FLAG_X0_HINTS), 'DDP_FLAG_X0_HINTS', 'bev')
     # together with teacher forcing
     cfg = S.make_cfg(H.CASES['seg_kc19_7x13'])
     assert S.query(lib, _with(cfg, _lib.FLAG_FORCE_X0))[0] == 0
-    _refused(lib, _with(cfg, _lib.FLAG_X0_HINTS | _lib.FLAG_FORCE_X0), 'DDP_FLAG_X0_HINTS', 'DDP_FLAG_FORCE_X0')
+    refused(lib, _with(cfg, _lib.FLAG_X0_HINTS | _lib.FLAG_FORCE_X0), 'DDP_FLAG_X0_HINTS', 'DDP_FLAG_FORCE_X0')
     # seg with 256 classes: accepted without the flag, and 255 with it
     c256 = dict(H.CASES['seg_kc255_5x10_r2'], Kc=256)
     assert S.query(lib, S.make_cfg(c256))[0] == 0
-    _refused(lib, _with(S.make_cfg(c256), _lib.FLAG_X0_HINTS), 'DDP_FLAG_X0_HINTS', '256')
+    refused(lib, _with(S.make_cfg(c256), _lib.FLAG_X0_HINTS), 'DDP_FLAG_X0_HINTS', '256')
     assert S.query(lib, _with(S.make_cfg(H.CASES['seg_kc255_5x10_r2']), _lib.FLAG_X0_HINTS))[0] == 0
     # depth does not look at num_classes
     assert S.query(lib, _with(S.make_cfg(dict(H.CASES['depth_9x14'], Kc=256)), _lib.FLAG_X0_HINTS))[0] == 0
@@ -217,8 +209,8 @@ def test_refusals_carry_their_message():
             assert b'sample_fcn: DDP_FLAG_X0_HINTS' in lib.ddp_last_error(), lib.ddp_last_error()
     # bit 8192 is still a bit nobody defines
     for extra in (8192, 8192 | _lib.FLAG_X0_HINTS):
-        _refused(lib, _with(S.make_cfg(H.CASES['seg_kc19_7x13']), extra), 'unknown flags')
-    _refused(lib, _with(S.make_cfg(H.CASES['depth_9x14']), 32768), 'unknown flags')
+        refused(lib, _with(S.make_cfg(H.CASES['seg_kc19_7x13']), extra), 'unknown flags')
+    refused(lib, _with(S.make_cfg(H.CASES['depth_9x14']), 32768), 'unknown flags')
 
 
 def test_engine_and_plugin_surface():

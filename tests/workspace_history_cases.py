@@ -31,19 +31,11 @@ import next_rows_cases as N
 import prior_start_cases as PS
 import score_prior_cases as SP
 import seeded_noise_util as U
-import test_class_prior_gpu as TPC
-import test_config_space_gpu as TC
-import test_ddpm_chain_gpu as TD
-import test_prior_start_gpu as TPS
-import test_score_prior_gpu as TSP
-import test_workspace_regions_gpu as TR
-import test_x0_hints_gpu as TH
 import x0_hint_cases as H
 from ddp_amd import _lib
 from ddp_amd.utils import synthetic
 from golden_util import max_rel
-from test_config_space_gpu import PATTERN
-from test_hip_parity import REL
+from support import PATTERN, REL
 
 FILLS = {'nan': PATTERN,              # the suite's quiet NaN
          'zero': 0x00000000,
@@ -160,7 +152,7 @@ class _Plain(Target):
         return S.oracle_batch(self.c)
 
     def check(self, o, label):
-        TC._check_against_oracle(self.c, o['out'], label)
+        S.check_against_oracle(self.c, o['out'], label)
 
 
 class _Chain(Target):
@@ -168,7 +160,7 @@ class _Chain(Target):
         return D.oracle_batch(self.c)
 
     def check(self, o, label):
-        TD._check_against_oracle(self.c, o['out'], label)
+        D.check_against_oracle(self.c, o['out'], label)
 
 
 class _Hints(Target):
@@ -213,7 +205,7 @@ class _ClassPrior(Target):
 
     def check(self, o, label):
         e = self.expectation()
-        err = TPC._rel_live(o['out'], e['out'], PC.rows(self.c, 'soft'))
+        err = PC.rel_live(o['out'], e['out'], PC.rows(self.c, 'soft'))
         agree = float((o['step_record'] == e['record']).float().mean())
         print(f'WS-HISTORY oracle {label}: max-rel {err:.3e} (bar {REL:.0e}), decisions equal {agree:.4f} at every step')
         assert torch.isfinite(o['out']).all() and err < REL and agree > 0.999
@@ -236,7 +228,7 @@ class _ScorePrior(Target):
         if self.kind == 'both':
             err = SP.max_rel(o['out'], e['out'])
         else:
-            err = TSP._rel_live(o['out'], e['out'], SP.prior_map(self.c, 'soft'))
+            err = SP.rel_live(o['out'], e['out'], SP.prior_map(self.c, 'soft'))
         agree = float((o['step_record'] == e['record']).float().mean())
         print(f'WS-HISTORY oracle {label}: max-rel {err:.3e} (bar {REL:.0e}), decisions equal {agree:.4f} at every step')
         assert torch.isfinite(o['out']).all() and err < REL and agree > 0.999
@@ -298,43 +290,43 @@ def _put(t):
 
 
 for _path, _n in sorted(smallest_per_path().items()):
-    _put(_Plain('cs-' + _n, 'config_space_cases', _path, S.CASES[_n], TC.variants(S.CASES[_n])))
+    _put(_Plain('cs-' + _n, 'config_space_cases', _path, S.CASES[_n], S.variants(S.CASES[_n])))
 for _row, _n in BY_NAME:
-    _put(_Plain('cs-' + _n, 'config_space_cases', _row, S.CASES[_n], TC.variants(S.CASES[_n])))
+    _put(_Plain('cs-' + _n, 'config_space_cases', _row, S.CASES[_n], S.variants(S.CASES[_n])))
 for _n in ('seg_kc19_7x13', 'depth_9x14'):
     _c = H.CASES[_n]
-    _put(_Hints('x0-' + _n, 'x0_hint_cases', 'x0_hints_' + _c['task'], _c, TH.routes(_c),
+    _put(_Hints('x0-' + _n, 'x0_hint_cases', 'x0_hints_' + _c['task'], _c, H.routes(_c),
                 dict(x0_hints=True, **(dict(record_x0=True) if _c['task'] == 'seg' else dict(record_steps=True)))))
 for _n in ('seg_kc19_7x13', 'depth_5x10_r2', 'bev_kc8_r1'):
     _c = PS.CASES[_n]
-    _put(_Prior('ps-' + _n, 'prior_start_cases', 'prior_start_' + _c['task'], _c, TPS.routes(_c),
+    _put(_Prior('ps-' + _n, 'prior_start_cases', 'prior_start_' + _c['task'], _c, PS.routes(_c),
                 dict(prior_start=True, t_start=_c['t_start'], **(dict(record_x0=True) if _c['task'] == 'seg' else {})), state=PS.state_dict))
 _c = PC.seeded(PC.CASES['kc19_8x12_b2'], 'soft')
-_put(_ClassPrior('cp-kc19_8x12_b2', 'class_prior_cases', 'class_prior', _c, TPC.routes(_c), dict(class_prior=True, record_steps=True)))
+_put(_ClassPrior('cp-kc19_8x12_b2', 'class_prior_cases', 'class_prior', _c, PC.routes(_c), dict(class_prior=True, record_steps=True)))
 _c = SP.seeded(SP.CASES['kc19_8x12_b2'], 'soft')
-_put(_ScorePrior('sp-kc19_8x12_b2', 'score_prior_cases', 'score_prior', _c, TSP.routes(_c), dict(score_prior=True, record_steps=True)))
+_put(_ScorePrior('sp-kc19_8x12_b2', 'score_prior_cases', 'score_prior', _c, SP.routes(_c), dict(score_prior=True, record_steps=True)))
 _c = SP.seeded(SP.CASES['kc19_7x13_b3'], 'both')
 _put(_BothPriors('sp-both-kc19_7x13_b3', 'score_prior_cases', 'score_and_class_prior', _c,
-                 [r for r in TSP.routes(_c) if r[0] in ('bf16x3', 'f32', 'unfused-layer', 'unfused-tail')],     # test_both_priors_add's
+                 [r for r in SP.routes(_c) if r[0] in ('bf16x3', 'f32', 'unfused-layer', 'unfused-tail')],     # test_both_priors_add's
                  dict(score_prior=True, class_prior=True, record_steps=True)))
 _c = D.ALL['dc_15tok']
-_put(_Chain('dc-dc_15tok', 'ddpm_chain_cases', 'ddpm_chain', _c, [(v, 'bf16x3', fl) for v, fl in sorted(TD.VIDS.items())],
+_put(_Chain('dc-dc_15tok', 'ddpm_chain_cases', 'ddpm_chain', _c, [(v, 'bf16x3', fl) for v, fl in sorted(D.VIDS.items())],
             dict(ddpm_chain=True), engine_kwargs=D.engine_kwargs))
 for _n in ('seg_fused', 'depth_chain_1x37'):
     _c, _fl = U.CASES[_n]
     _fl = dict(_fl)
     _put(_OwnNoise('sn-' + _n, 'seeded_noise_util', 'step_record_seeded_' + _c['task'], _c, [(_n, _fl.pop('gemm', 'bf16x3'), _fl)],
                    dict(seeded_noise=True, record_steps=True), seed=U.SEED))
-for _task, _c in TR.CASES.items():
+for _task, _c in S.REGION_CASES.items():
     _put(_AllFlags('all-' + _task, 'test_workspace_regions_gpu', 'all_flags_' + _task, _c, [('bf16x3', 'bf16x3', {})],
                    dict(record_steps=True, seeded_noise=True, x0_hints=True, prior_start=True, class_prior=_task == 'seg'), seed=2024))
 
-ROUTE_TABLES = {'config_space_cases': lambda t: {(v, g) for v, g, _ in TC.variants(t.c)},
-                'x0_hint_cases': lambda t: {(v, g) for v, g, _ in TH.routes(t.c)},
-                'prior_start_cases': lambda t: {(v, g) for v, g, _ in TPS.routes(t.c)},
-                'class_prior_cases': lambda t: {(v, g) for v, g, _ in TPC.routes(t.c)},
-                'score_prior_cases': lambda t: {(v, g) for v, g, _ in TSP.routes(t.c)},
-                'ddpm_chain_cases': lambda t: {(v, 'bf16x3') for v in TD.VIDS},
+ROUTE_TABLES = {'config_space_cases': lambda t: {(v, g) for v, g, _ in S.variants(t.c)},
+                'x0_hint_cases': lambda t: {(v, g) for v, g, _ in H.routes(t.c)},
+                'prior_start_cases': lambda t: {(v, g) for v, g, _ in PS.routes(t.c)},
+                'class_prior_cases': lambda t: {(v, g) for v, g, _ in PC.routes(t.c)},
+                'score_prior_cases': lambda t: {(v, g) for v, g, _ in SP.routes(t.c)},
+                'ddpm_chain_cases': lambda t: {(v, 'bf16x3') for v in D.VIDS},
                 'seeded_noise_util': lambda t: {(n, fl.get('gemm', 'bf16x3')) for n, (_, fl) in U.CASES.items()},
                 'test_workspace_regions_gpu': lambda t: {('bf16x3', 'bf16x3')}}
 

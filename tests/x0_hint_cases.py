@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 import config_space_cases as CS
 from oracle import ddp_oracle as O
+from support import max_rel64 as max_rel, round256  # noqa: F401  (the float64 measure: H.max_rel at every call site)
 
 REL = CS.REL
 COND = CS.COND
@@ -239,13 +240,20 @@ def expected(c, kind, dtype=torch.float32):
     return _EXPECT[key]
 
 
-def max_rel(a, b):
-    """the parity measure of tests/test_hip_parity.py: largest absolute difference over the largest magnitude of the expectation"""
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max())
-
-
-def round256(n):
-    return (n + 255) // 256 * 256
+def routes(c):
+    """(id, gemm, flags): both engines and every flag that selects another route for the case (tests/test_config_space_gpu.py)"""
+    v = [('bf16x3', 'bf16x3', {}), ('f32', 'f32', {}), ('unfused-layer', 'bf16x3', dict(fused_layer=False)),
+         ('unfused-prologue', 'bf16x3', dict(fused_prologue=False))]
+    if c['task'] == 'seg' and c['sampler'] == 'ddim':
+        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
+        if c['r'] == 1:
+            v.append(('sb-head', 'bf16x3', dict(nchw_head=False)))
+    if c['task'] == 'seg' and c['sampler'] == 'ddpm':
+        v += [('chain', 'bf16x3', dict(ddpm_chain=True)), ('chain-unfused-tail', 'bf16x3', dict(ddpm_chain=True, fused_tail=False)),
+              ('chain-sb-head', 'bf16x3', dict(ddpm_chain=True, nchw_head=False))]
+    if c['task'] == 'depth' and not c['n_bins']:
+        v.append(('unfused-tail', 'bf16x3', dict(fused_tail=False)))
+    return v
 
 
 def hint_bytes(c):
