@@ -42,16 +42,14 @@ def _to_device(data, device):
 
 
 def _run_batch(model, data, device, batch_indices=None, **kwargs):
+    from .engine import CALLER_INPUTS
     data = dict(data)
     data['img'] = _to_device(data['img'], device)
-    if data.get('hints') is not None:      # x0 hints (DDP.forward(hints=)): in the frame of img, on its device; passed through with **data
-        data['hints'] = _to_device(data['hints'], device)
-    if data.get('prior') is not None:      # prior start (DDP.forward(prior=, t_start=)): likewise
-        data['prior'] = _to_device(data['prior'], device)
-    if data.get('class_prior') is not None:    # class prior (DDP.forward(class_prior=)): (b, num_classes), no frame
-        data['class_prior'] = _to_device(data['class_prior'], device)
-    if data.get('score_prior') is not None:    # score prior (DDP.forward(score_prior=)): (b, num_classes, H, W), likewise
-        data['score_prior'] = _to_device(data['score_prior'], device)
+    # the conditioning entries of the batch (DDP.forward(hints=, prior=, class_prior=, score_prior=)): on the device of img, passed
+    # through with **data
+    for row in CALLER_INPUTS:
+        if data.get(row.name) is not None:
+            data[row.name] = _to_device(data[row.name], device)
     # seeded noise (model.noise_seed set): image i of the batch draws the noise of dataset index batch_indices[0] + i, whatever
     # samples_per_gpu is and whichever rank the batch landed on (a batch_sampler of a sequential or strided sampler hands out
     # increasing indices; the first one names the batch)

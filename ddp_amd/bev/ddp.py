@@ -119,10 +119,6 @@ class DDP(nn.Module, _SamplerMixin):
         hkey = (id(head), repr(gt['input_scope']), repr(gt['output_scope']), getattr(head, 'prescale_factor', 1.0),
                 getattr(head, 'seg_conv_kernel', 1), bool(return_steps), seeded, prior is not None, ts)
         eng = self._get_engine((b, c, h, w, str(x0.device), self.timesteps, self.randsteps, ver) + hkey, factory)
-        if prior is not None:
-            eng.set_prior(self._prior_map(prior, b, h, w, torch.int32).to(x0.device))
-        if seeded:
-            out = eng.sample(x0.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
-        else:
-            out = eng.sample(x0.contiguous().float(), noise.contiguous().float())
-        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
+        # (resampled behind the engine, as ever: what is wrong with the engine is said first)
+        _, maps = self._conditioning(b, h, w, x0.device, torch.int32, prior=prior, t_start=t_start)
+        return self._run(eng, maps, x0, noise, None, return_steps, image_base, call)

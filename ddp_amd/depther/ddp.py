@@ -146,15 +146,9 @@ class DDP(nn.Module, _SamplerMixin):
         eng = self._get_engine(('depth', str(x.device), self.timesteps, self.randsteps, self.bit_scale, self.time_difference,
                                 self.min_depth, self.max_depth, su, ue, hmin, hmax, bins_key, bool(return_steps), seeded,
                                 hints is not None, prior is not None, ts), factory, geometry=(b, h, w))
-        if hints is not None:
-            eng.set_hints(self._hint_map(hints, b, h, w, torch.float32).to(x.device))
-        if prior is not None:
-            eng.set_prior(self._prior_map(prior, b, h, w, torch.float32).to(x.device))
-        if seeded:
-            out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
-        else:
-            out = eng.sample(x.contiguous().float(), noise.contiguous().float())
-        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
+        # (resampled behind the engine, as ever: what is wrong with the engine is said first)
+        _, maps = self._conditioning(b, h, w, x.device, torch.float32, hints=hints, prior=prior, t_start=t_start)
+        return self._run(eng, maps, x, noise, None, return_steps, image_base, call)
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)
@@ -183,8 +177,7 @@ class DDP(nn.Module, _SamplerMixin):
 
     def _low_res(self, img, img_metas, image_base=0, call=0, hints=None, prior=None, t_start=None):
         """backbone + neck + the K-step loop: the (b,1,h/4,w/4) map every epilogue below starts from."""
-        return self.sample(self.extract_feat(img)[0], img_metas, **self._seed_kw(image_base, call),
-                           **({} if hints is None else {'hints': hints}), **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
+        return self.sample(self.extract_feat(img)[0], img_metas, **self._given(image_base, call, hints=hints, prior=prior, t_start=t_start))
 
     def _post(self, maps, flips, size):
         from ..engine import depth_postprocess
@@ -197,12 +190,12 @@ class DDP(nn.Module, _SamplerMixin):
     def encode_decode(self, img, img_metas=None, rescale=False, image_base=0, call=0):
         """depther/ddp.py:95-109: clamp to the head's depth range, resize to the network input when ``rescale`` - one fused
         kernel (``ddp_depth_postprocess``), no intermediate (b,1,h,w) clamp result."""
-        d = self._low_res(img, img_metas, **self._seed_kw(image_base, call))
+        d = self._low_res(img, img_metas, **self._given(image_base, call))
         return self._post([d], [None], img.shape[2:] if rescale else d.shape[2:])
 
     def whole_inference(self, img, img_meta, rescale, image_base=0, call=0):
         """encoder_decoder.py:160-166."""
-        return self.encode_decode(img, img_meta, rescale, **self._seed_kw(image_base, call))
+        return self.encode_decode(img, img_meta, rescale, **self._given(image_base, call))
 
     @staticmethod
     def _flip_of(img_meta):
@@ -220,8 +213,7 @@ class DDP(nn.Module, _SamplerMixin):
         if img_meta:
             ori_shape = img_meta[0]['ori_shape']
             assert all(m['ori_shape'] == ori_shape for m in img_meta)
-        d = self._low_res(img, img_meta, **self._seed_kw(image_base, call), **({} if hints is None else {'hints': hints}),
-                          **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
+        d = self._low_res(img, img_meta, **self._given(image_base, call, hints=hints, prior=prior, t_start=t_start))
         return self._post([d], [self._flip_of(img_meta)], img.shape[2:] if rescale else d.shape[2:])
 
     def simple_test(self, img, img_meta, rescale=True, image_base=0, hints=None, prior=None, t_start=None, on_device=False):
@@ -230,8 +222,7 @@ class DDP(nn.Module, _SamplerMixin):
         encoder_decoder.py:198-209: list (batch) of (1,H,W) float32 arrays.  ``img`` may hold b >= 1 images (independent
         noise per image; the reference's sampler is b = 1 only, depther/ddp.py:232).  ``hints`` (b,Hh,Wh) float32, ``prior`` (b,Hp,Wp)
         float32 with ``t_start``: see ``sample``."""
-        out = self.inference(img, img_meta, rescale, **self._seed_kw(image_base),
-                             **({} if hints is None else {'hints': hints}), **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}))
+        out = self.inference(img, img_meta, rescale, **self._given(image_base, 0, hints=hints, prior=prior, t_start=t_start))
         return list(out) if on_device else list(out.cpu().numpy())
 
     def aug_test(self, imgs, img_metas, rescale=True, image_base=0, hints=None, prior=None, t_start=None, on_device=False):
@@ -240,10 +231,7 @@ class DDP(nn.Module, _SamplerMixin):
         encoder_decoder.py:210-229: mean over the augmentations (KITTI / NYU test pipelines: plain + horizontal flip,
         depth/configs/_base_/datasets/kitti.py:30-33).  Every augmentation runs the full sampling loop with its own noise; only the
         LOW-RESOLUTION maps are kept and ONE kernel does clamp -> resize -> flip-undo -> running sum -> / n per output pixel."""
-        if hints is not None:
-            raise ValueError('hints are not built for aug_test (every augmentation has its own frame)')
-        if prior is not None or t_start is not None:
-            raise ValueError('prior / t_start are not built for aug_test (every augmentation has its own frame)')
+        self._refuse_frame_bound('aug_test', hints, prior, t_start)
         assert rescale, 'aug_test rescales every augmentation back to the network input'
         self._check_mode()
         sizes = {tuple(img.shape[2:]) for img in imgs}
@@ -255,7 +243,7 @@ class DDP(nn.Module, _SamplerMixin):
             if meta:
                 ori_shape = meta[0]['ori_shape']
                 assert all(m['ori_shape'] == ori_shape for m in meta)
-            maps.append(self._low_res(img, meta, **self._seed_kw(image_base, a)))      # (seeded noise: the augmentation index is the `call`)
+            maps.append(self._low_res(img, meta, **self._given(image_base, a)))      # (seeded noise: the augmentation index is the `call`)
             flips.append(self._flip_of(meta))
         out = self._post(maps, flips, imgs[0].shape[2:])
         return list(out) if on_device else list(out.cpu().numpy())

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it allocates device memory (weights blob, workspace, i
 provides the current HIP stream; every FLOP of the loop runs in libddp_mi355x.so.
 """
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -329,24 +330,18 @@ class DDPEngine(_SeededNoise):
             if task != 'seg' or sampler != 'ddpm':
                 raise ValueError(f"ddpm_chain is a route of the segmentation ddpm sampler (task {task!r}, sampler {sampler!r})")
             cfg.flags |= _lib.FLAG_DDPM_CHAIN
-        if x0_hints:
-            if task == 'bev':
-                raise ValueError('x0_hints is built for the seg and depth samplers (DDP_FLAG_X0_HINTS): the bev sampler takes no hints')
-            if force_x0:
+        asked = dict(x0_hints=x0_hints, prior_start=prior_start, class_prior=class_prior, score_prior=score_prior)
+        for row in reversed(CALLER_INPUTS):      # (hints first: the order these refusals have had since each was added)
+            if not asked[row.kwarg]:
+                continue
+            if cfg.task not in row.dtypes:
+                raise ValueError(f'{row.kwarg} is built for the {row.built_for} ({row.flag_name}): '
+                                 + row.wrong_task.format(task=task))
+            if row.name == 'hints' and force_x0:
                 raise ValueError('x0_hints cannot be combined with force_x0 (DDP_FLAG_X0_HINTS / DDP_FLAG_FORCE_X0)')
-            cfg.flags |= _lib.FLAG_X0_HINTS
-        if prior_start:
-            if task == 'bev' and num_classes > 32:
+            if row.name == 'prior' and task == 'bev' and num_classes > 32:
                 raise ValueError('prior_start: a bev prior is one 32-bit word per pixel (DDP_FLAG_PRIOR_START, num_classes <= 32)')
-            cfg.flags |= _lib.FLAG_PRIOR_START
-        if class_prior:
-            if task != 'seg':
-                raise ValueError(f'class_prior is built for the segmentation sampler (DDP_FLAG_CLASS_PRIOR): task {task!r} takes none')
-            cfg.flags |= _lib.FLAG_CLASS_PRIOR
-        if score_prior:
-            if task != 'seg':
-                raise ValueError(f'score_prior is built for the segmentation sampler (DDP_FLAG_SCORE_PRIOR): task {task!r} takes none')
-            cfg.flags |= _lib.FLAG_SCORE_PRIOR
+            cfg.flags |= row.flag
         self.t_start = float(t_start)
         self.fused_layer = bool(fused_layer)
         cfg.accumulation = int(bool(accumulation))
@@ -368,50 +363,58 @@ class DDPEngine(_SeededNoise):
         self._sampled = False
         self.geometry_changes = 0
         self._init_key()
-        self.clear_hints(_if_any=True)
-        self.clear_prior(_if_any=True)
-        self.clear_class_prior(_if_any=True)
-        self.clear_score_prior(_if_any=True)
+        for row in CALLER_INPUTS:
+            self._clear_input(row, _if_any=True)
 
     def _workspace_bytes(self):
         nbytes = C.c_size_t(0)
         _lib.check(self.lib.ddp_query_workspace(C.byref(self.cfg), C.byref(nbytes)), self.lib)
         return nbytes.value
 
+    # ---- the caller-written inputs: every method below is its row of CALLER_INPUTS ---------------
+    def _input_view(self, row):
+        """VIEW of the row's caller-written region inside the workspace, in the dtype of the engine's task"""
+        c = self.cfg
+        if not c.flags & row.flag:
+            raise _lib.DdpError(f'{row.needs} an engine built with {row.kwarg}=True')
+        return self._region(row.region, row.dtypes[c.task], row.shape(c))
+
+    def _write_input(self, row, src):
+        """the checks and the stream-ordered copy of every set_*: ``src`` must be a tensor of the dtype the row accepts (the view's,
+        or any 'floating-point' one) with the shape of the slice the row writes, on the engine's device"""
+        dst = row.dst(self._input_view(row), self.cfg)
+        kind = row.accepts or dst.dtype
+        ok = isinstance(src, torch.Tensor) and (src.dtype.is_floating_point if kind == 'floating-point' else src.dtype == kind)
+        if not ok:
+            raise _lib.DdpError(f'{row.name} must be a {kind} tensor, got {getattr(src, "dtype", type(src))}')
+        if tuple(src.shape) != tuple(dst.shape):
+            raise _lib.DdpError(f'{row.name} must have shape {tuple(dst.shape)} ({row.dims}), got {tuple(src.shape)}')
+        if src.device != self.device:
+            raise _lib.DdpError(f'engine lives on {self.device}: {row.where} on {src.device}')
+        with torch.cuda.device(self.device):
+            dst.copy_(src, non_blocking=True)
+
+    def _clear_input(self, row, _if_any=False):
+        """the row's "nothing given" value over the whole region; ``_if_any``: only where the engine has the region"""
+        if _if_any and not self.cfg.flags & row.flag:
+            return
+        v = self._input_view(row)
+        with torch.cuda.device(self.device):
+            v.fill_(row.clear[v.dtype])
+
     # ---- DDP_FLAG_X0_HINTS ---------------------------------------------------------------------
     def hints_view(self):
         """(B, h, w) VIEW of the caller-written hint map inside the workspace - uint8 (seg) or float32 (depth); the kernels read it
         when they run (a captured graph picks up what it holds at replay).  Place: include/ddp_mi355x.h, "x0 hints"."""
-        c = self.cfg
-        if not c.flags & _lib.FLAG_X0_HINTS:
-            raise _lib.DdpError('hints need an engine built with x0_hints=True')
-        return self._region('hint_map', torch.uint8 if c.task == _lib.TASK_SEG else torch.float32, (c.batch, c.h, c.w))
-
-    def _write_region(self, dst, src, name, kind, dims, where):
-        """the checks and the stream-ordered copy of set_hints / set_prior / set_class_prior: ``src`` must be a tensor of dtype
-        ``kind`` (or any 'floating-point' one) with the shape of ``dst``, on the engine's device"""
-        ok = isinstance(src, torch.Tensor) and (src.dtype.is_floating_point if kind == 'floating-point' else src.dtype == kind)
-        if not ok:
-            raise _lib.DdpError(f'{name} must be a {kind} tensor, got {getattr(src, "dtype", type(src))}')
-        if tuple(src.shape) != tuple(dst.shape):
-            raise _lib.DdpError(f'{name} must have shape {tuple(dst.shape)} ({dims}), got {tuple(src.shape)}')
-        if src.device != self.device:
-            raise _lib.DdpError(f'engine lives on {self.device}: {where} on {src.device}')
-        with torch.cuda.device(self.device):
-            dst.copy_(src, non_blocking=True)
+        return self._input_view(_ROW['hints'])
 
     def set_hints(self, hints):
         """copy ``hints`` (B, h, w) - uint8 for seg, float32 for depth, on the engine's device - into the hint map (stream-ordered)"""
-        v = self.hints_view()
-        self._write_region(v, hints, 'hints', v.dtype, 'batch, h, w', 'hints are')
+        self._write_input(_ROW['hints'], hints)
 
     def clear_hints(self, _if_any=False):
         """every pixel free (seg: 255, depth: 0)"""
-        if _if_any and not self.cfg.flags & _lib.FLAG_X0_HINTS:
-            return
-        v = self.hints_view()
-        with torch.cuda.device(self.device):
-            v.fill_(255 if v.dtype == torch.uint8 else 0)
+        self._clear_input(_ROW['hints'], _if_any)
 
     # ---- DDP_FLAG_PRIOR_START ------------------------------------------------------------------
     def _prior_places(self):
@@ -424,24 +427,16 @@ class DDPEngine(_SeededNoise):
         """(B, h, w) VIEW of the caller-written prior map inside the workspace - uint8 (seg), float32 (depth) or int32 bit words
         (bev; the C side's uint32); the kernel reads it when it runs (a captured graph picks up what it holds at replay).  Place:
         include/ddp_mi355x.h, "prior start"."""
-        c = self.cfg
-        self._prior_places()
-        dtype = {_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32}[c.task]
-        return self._region('prior_map', dtype, (c.batch, c.h, c.w))
+        return self._input_view(_ROW['prior'])
 
     def set_prior(self, prior):
         """copy ``prior`` (B, h, w) - uint8 for seg, float32 for depth, int32 for bev, on the engine's device - into the prior map
         (stream-ordered)"""
-        v = self.prior_view()
-        self._write_region(v, prior, 'prior', v.dtype, 'batch, h, w', 'the prior is')
+        self._write_input(_ROW['prior'], prior)
 
     def clear_prior(self, _if_any=False):
         """no prior knowledge anywhere: seg 255 (the ignore row), depth 0 (the middle of the range), bev 0 (no class present)"""
-        if _if_any and not self.cfg.flags & _lib.FLAG_PRIOR_START:
-            return
-        v = self.prior_view()
-        with torch.cuda.device(self.device):
-            v.fill_(255 if v.dtype == torch.uint8 else 0)
+        self._clear_input(_ROW['prior'], _if_any)
 
     def last_start(self):
         """(B, r, Cm, h, w) float32 VIEW of the start map the LAST sample() call (or graph replay) formed from the prior and its
@@ -458,45 +453,29 @@ class DDPEngine(_SeededNoise):
         """(B, 256) float32 VIEW of the caller-written class prior table inside the workspace; columns >= num_classes are ignored.
         The library reads it when ddp_sample runs (a captured graph picks up what it holds at replay).  Place:
         include/ddp_mi355x.h, "class prior"."""
-        c = self.cfg
-        if not c.flags & _lib.FLAG_CLASS_PRIOR:
-            raise _lib.DdpError('the class prior needs an engine built with class_prior=True')
-        return self._region('cprior_table', torch.float32, (c.batch, 256))
+        return self._input_view(_ROW['class_prior'])
 
     def set_class_prior(self, prior):
         """copy ``prior`` (B, num_classes) - a floating-point tensor on the engine's device - into the table (stream-ordered)"""
-        v = self.class_prior_view()
-        self._write_region(v[:, :self.cfg.num_classes], prior, 'class_prior', 'floating-point', 'batch, num_classes', 'the class prior is')
+        self._write_input(_ROW['class_prior'], prior)
 
     def clear_class_prior(self, _if_any=False):
         """no prior: every entry 0 (the bits of the flag-clear call)"""
-        if _if_any and not self.cfg.flags & _lib.FLAG_CLASS_PRIOR:
-            return
-        v = self.class_prior_view()
-        with torch.cuda.device(self.device):
-            v.zero_()
+        self._clear_input(_ROW['class_prior'], _if_any)
 
     # ---- DDP_FLAG_SCORE_PRIOR ------------------------------------------------------------------
     def score_prior_view(self):
         """(B, num_classes, h, w) float32 VIEW of the caller-written score prior map inside the workspace.  The library reads it when
         ddp_sample runs (a captured graph picks up what it holds at replay).  Place: include/ddp_mi355x.h, "score prior"."""
-        c = self.cfg
-        if not c.flags & _lib.FLAG_SCORE_PRIOR:
-            raise _lib.DdpError('the score prior needs an engine built with score_prior=True')
-        return self._region('sprior_map', torch.float32, (c.batch, c.num_classes, c.h, c.w))
+        return self._input_view(_ROW['score_prior'])
 
     def set_score_prior(self, prior):
         """copy ``prior`` (B, num_classes, h, w) - a floating-point tensor on the engine's device - into the map (stream-ordered)"""
-        v = self.score_prior_view()
-        self._write_region(v, prior, 'score_prior', 'floating-point', 'batch, num_classes, h, w', 'the score prior is')
+        self._write_input(_ROW['score_prior'], prior)
 
     def clear_score_prior(self, _if_any=False):
         """no prior: every entry 0 (the bits of the flag-clear call)"""
-        if _if_any and not self.cfg.flags & _lib.FLAG_SCORE_PRIOR:
-            return
-        v = self.score_prior_view()
-        with torch.cuda.device(self.device):
-            v.zero_()
+        self._clear_input(_ROW['score_prior'], _if_any)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -539,10 +518,8 @@ class DDPEngine(_SeededNoise):
         self.geometry_changes += 1
         self._x0_set = False       # force_x0: the decisions buffer belongs to the geometry region
         self._sampled = False      # (so do the step record and the disagreement map)
-        self.clear_hints(_if_any=True)   # (and the hint map: another geometry or another buffer - unset hints are no hints)
-        self.clear_prior(_if_any=True)   # (and the prior map)
-        self.clear_class_prior(_if_any=True)   # (and the class prior table)
-        self.clear_score_prior(_if_any=True)   # (and the score prior map)
+        for row in CALLER_INPUTS:  # (and the caller-written inputs: another geometry or another buffer - an unset input is none)
+            self._clear_input(row, _if_any=True)
         return self
 
     def out_shape(self):
@@ -725,6 +702,64 @@ def caller_regions(cfg, workspace_bytes):
     return dict(reversed(out))
 
 
+CallerInput = namedtuple('CallerInput', 'name kwarg flag flag_name region dtypes shape dst accepts clear '
+                                        'needs dims where built_for wrong_task fcn')
+CallerInput.__doc__ = """One input the caller writes into the workspace in front of a sampler call: what ``DDPEngine`` (views, setters,
+clears, the constructor's task check), ``SampleGraph.replay`` and ``FcnSamplerEngine`` know about it.
+``name``: the public name (``<name>_view`` / ``set_<name>`` / ``clear_<name>``, ``replay(<name>=)``); ``kwarg``: the constructor's keyword;
+``flag`` / ``flag_name``: the bit and how the header spells it; ``region``: the caller-written buffer of ``caller_regions``; ``dtypes``:
+{task: the view's dtype} - its keys are the tasks the input exists for; ``shape(cfg)``: the view's; ``dst(view, cfg)``: the slice
+``set_<name>`` writes; ``accepts``: 'floating-point', or None for exactly the view's dtype; ``clear``: {dtype: the value that says "nothing
+given"}.  The phrases of its messages: ``needs`` (view / set / clear on a flag-clear engine), ``dims`` and ``where`` (a wrong shape, a
+wrong device), ``built_for`` and ``wrong_task`` (the constructor, for a task outside ``dtypes``), ``fcn`` (the FCN-head loop)."""
+
+
+def _whole(view, cfg):
+    return view
+
+
+def _class_columns(view, cfg):
+    return view[:, :cfg.num_classes]
+
+
+def _bhw(cfg):
+    return (cfg.batch, cfg.h, cfg.w)
+
+
+def _bkhw(cfg):
+    return (cfg.batch, cfg.num_classes, cfg.h, cfg.w)
+
+
+def _b256(cfg):
+    return (cfg.batch, 256)
+
+
+# the rows of caller_regions that the caller writes, in its order
+CALLER_INPUTS = (
+    CallerInput(name='score_prior', kwarg='score_prior', flag=_lib.FLAG_SCORE_PRIOR, flag_name='DDP_FLAG_SCORE_PRIOR',
+                region='sprior_map', dtypes={_lib.TASK_SEG: torch.float32}, shape=_bkhw, dst=_whole,
+                accepts='floating-point', clear={torch.float32: 0},
+                needs='the score prior needs', dims='batch, num_classes, h, w', where='the score prior is',
+                built_for='segmentation sampler', wrong_task='task {task!r} takes none', fcn='takes no score prior'),
+    CallerInput(name='class_prior', kwarg='class_prior', flag=_lib.FLAG_CLASS_PRIOR, flag_name='DDP_FLAG_CLASS_PRIOR',
+                region='cprior_table', dtypes={_lib.TASK_SEG: torch.float32}, shape=_b256, dst=_class_columns,
+                accepts='floating-point', clear={torch.float32: 0},
+                needs='the class prior needs', dims='batch, num_classes', where='the class prior is',
+                built_for='segmentation sampler', wrong_task='task {task!r} takes none', fcn='takes no class prior'),
+    CallerInput(name='prior', kwarg='prior_start', flag=_lib.FLAG_PRIOR_START, flag_name='DDP_FLAG_PRIOR_START',
+                region='prior_map', dtypes={_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32, _lib.TASK_BEV: torch.int32},
+                shape=_bhw, dst=_whole, accepts=None, clear={torch.uint8: 255, torch.float32: 0, torch.int32: 0},
+                needs='the prior map and last_start() need', dims='batch, h, w', where='the prior is',
+                built_for='seg, depth and bev samplers', wrong_task='task {task!r} takes none', fcn='starts from noise'),
+    CallerInput(name='hints', kwarg='x0_hints', flag=_lib.FLAG_X0_HINTS, flag_name='DDP_FLAG_X0_HINTS',
+                region='hint_map', dtypes={_lib.TASK_SEG: torch.uint8, _lib.TASK_DEPTH: torch.float32},
+                shape=_bhw, dst=_whole, accepts=None, clear={torch.uint8: 255, torch.float32: 0},
+                needs='hints need', dims='batch, h, w', where='hints are',
+                built_for='seg and depth samplers', wrong_task='the {task} sampler takes no hints', fcn='takes no hints'),
+)
+_ROW = {row.name: row for row in CALLER_INPUTS}
+
+
 def prior_start_places(cfg, workspace_bytes):
     """(prior_offset, prior_bytes, start_offset, start_bytes) of include/ddp_mi355x.h ("prior start"), in bytes from the start of a
     workspace of ``workspace_bytes`` = ddp_query_workspace(cfg).  With DDP_FLAG_SEEDED_NOISE the start map is the seeded-noise buffer."""
@@ -814,14 +849,10 @@ class SampleGraph:
             self.step_noise.copy_(step_noise.reshape(self.step_noise.shape), non_blocking=True)
         if seed is not None or image_base is not None or call is not None:
             eng._write_key(seed, image_base, None, call)
-        if hints is not None:
-            eng.set_hints(hints)
-        if prior is not None:
-            eng.set_prior(prior)
-        if class_prior is not None:
-            eng.set_class_prior(class_prior)
-        if score_prior is not None:
-            eng.set_score_prior(score_prior)
+        given = dict(hints=hints, prior=prior, class_prior=class_prior, score_prior=score_prior)
+        for row in CALLER_INPUTS:
+            if given[row.name] is not None:
+                eng._write_input(row, given[row.name])
         self.graph.replay()
         return self.out
 
@@ -834,14 +865,10 @@ class FcnSamplerEngine(_SeededNoise):
                  time_difference=1, sample_range0=0.0, noise_schedule='cosine', sampler='ddim', accumulation=False,
                  device=None, head_prefix='decode_head.', lib_path=None, record_steps=False, seeded_noise=False, x0_hints=False,
                  prior_start=False, class_prior=False, score_prior=False):
-        if score_prior:
-            raise ValueError('score_prior is built for ddp_sample only (DDP_FLAG_SCORE_PRIOR): the FCN-head loop takes no score prior')
-        if class_prior:
-            raise ValueError('class_prior is built for ddp_sample only (DDP_FLAG_CLASS_PRIOR): the FCN-head loop takes no class prior')
-        if prior_start:
-            raise ValueError('prior_start is built for ddp_sample only (DDP_FLAG_PRIOR_START): the FCN-head loop starts from noise')
-        if x0_hints:
-            raise ValueError('x0_hints is built for ddp_sample only (DDP_FLAG_X0_HINTS): the FCN-head loop takes no hints')
+        asked = dict(x0_hints=x0_hints, prior_start=prior_start, class_prior=class_prior, score_prior=score_prior)
+        for row in CALLER_INPUTS:
+            if asked[row.kwarg]:
+                raise ValueError(f'{row.kwarg} is built for ddp_sample only ({row.flag_name}): the FCN-head loop {row.fcn}')
         self.lib = _lib.load(lib_path)
         if not torch.cuda.is_available():
             raise _lib.DdpError('no HIP device visible: ddp_amd has no CPU path')

@@ -65,12 +65,37 @@ class _SamplerMixin:
             cache[key] = hit
         return hit[1]
 
-    def _seed_kw(self, image_base=0, call=0):
-        """the keyword arguments that carry the noise key down the call chain - none without ``noise_seed``, so that an unseeded
-        model calls its (possibly replaced) members exactly as before"""
-        if getattr(self, 'noise_seed', None) is None:
-            return {}
-        return dict(image_base=image_base, call=call)
+    def _given(self, image_base=None, call=None, *, hints=None, prior=None, t_start=None, class_prior=None, score_prior=None,
+               on_device=False):
+        """the keyword arguments that were given, to be handed down the call chain - a None produces no key, so that a model without
+        conditioning and without ``noise_seed`` calls its (possibly replaced) members with the reference's positional arguments and
+        nothing else.  ``image_base`` / ``call`` (the noise key) travel only with ``noise_seed``; ``prior`` and ``t_start`` travel
+        together whenever either is given; ``on_device`` only when true."""
+        kw = dict(hints=hints, class_prior=class_prior, score_prior=score_prior)
+        if getattr(self, 'noise_seed', None) is not None:
+            kw.update(image_base=image_base, call=call)
+        kw = {k: v for k, v in kw.items() if v is not None}
+        if prior is not None or t_start is not None:
+            kw.update(prior=prior, t_start=t_start)
+        if on_device:
+            kw['on_device'] = True
+        return kw
+
+    # what cannot be given per slide window or per augmentation, in the order each entry has always refused it: who, its one buffer
+    _FRAME_BOUND = {'score_prior': ('score_prior is', 'score prior map'), 'prior': ('prior / t_start are', 'prior map'),
+                    'hints': ('hints are', 'hint map')}
+    _FRAMES = {'slide inference': ('one {} per sampler call, not per window', ('score_prior', 'prior', 'hints')),
+               'aug_test': ('every augmentation has its own frame', ('score_prior', 'hints', 'prior'))}
+
+    @classmethod
+    def _refuse_frame_bound(cls, where, hints=None, prior=None, t_start=None, score_prior=None):
+        """ValueError for an input that lives in the frame of one sampler call, given to ``where`` = 'slide inference' | 'aug_test'"""
+        why, order = cls._FRAMES[where]
+        given = dict(score_prior=score_prior, prior=prior if prior is not None else t_start, hints=hints)
+        for name in order:
+            if given[name] is not None:
+                who, buffer = cls._FRAME_BOUND[name]
+                raise ValueError(f'{who} not built for {where} ({why.format(buffer)})')
 
     @staticmethod
     def _hint_map(hints, b, h, w, dtype):
@@ -120,12 +145,6 @@ class _SamplerMixin:
         t = class_prior.to(device=device, dtype=torch.float32)
         return (t.repeat(repeat, 1) if repeat > 1 else t).contiguous()
 
-    @staticmethod
-    def _cp_kw(class_prior):
-        """the keyword that carries a class prior down the call chain - none without one, so that a model without a prior calls its
-        (possibly replaced) members exactly as before"""
-        return {} if class_prior is None else dict(class_prior=class_prior)
-
     def _score_prior_map(self, score_prior, b, h, w, device):
         """``score_prior`` (b, num_classes, H, W) float -> the float32 NCHW map of the engine (DDP_FLAG_SCORE_PRIOR) on ``device``: a map
         that is not at the map resolution (h, w) is resized there as the scores are resized on the way out,
@@ -141,14 +160,40 @@ class _SamplerMixin:
         return t.contiguous()
 
     @staticmethod
-    def _sp_kw(score_prior):
-        """the keyword that carries a score prior down the call chain - none without one (as ``_cp_kw``)"""
-        return {} if score_prior is None else dict(score_prior=score_prior)
-
-    @staticmethod
     def _check_t_start(prior, t_start):
         if prior is not None and t_start is None:
             raise ValueError('prior= needs t_start= (the time the prior map is noised to; 1.0 drowns it in noise)')
+
+    def _conditioning(self, b, h, w, device, dtype, hints=None, prior=None, t_start=None, class_prior=None, score_prior=None):
+        """the call-time inputs of one sampler call on a (b, h, w) map -> (what they ask of the engine: True per input given, ``prior``
+        and ``t_start`` together whenever either is; {engine input: its tensor, resampled to the map, on ``device``}).  ``dtype``: the
+        task's hint / prior map dtype."""
+        self._check_t_start(prior, t_start)
+        maps = {}
+        if hints is not None:
+            maps['hints'] = self._hint_map(hints, b, h, w, dtype).to(device)
+        if prior is not None:
+            maps['prior'] = self._prior_map(prior, b, h, w, dtype).to(device)
+        if class_prior is not None:
+            maps['class_prior'] = self._class_prior_table(class_prior, b, device)
+        if score_prior is not None:
+            maps['score_prior'] = self._score_prior_map(score_prior, b, h, w, device)
+        asks = dict.fromkeys(maps, True)
+        if prior is not None or t_start is not None:
+            asks.update(prior=prior is not None, t_start=t_start)
+        return asks, maps
+
+    def _run(self, eng, maps, x, noise=None, step_noise=None, return_steps=False, image_base=0, call=0):
+        """write ``maps`` (of ``_conditioning``) to the engine and sample: on ``noise`` (and ``step_noise``), or - None - on the noise
+        of (noise_seed, image_base, call); -> out, or with ``return_steps`` (out, step record, step disagreement)"""
+        for name, t in maps.items():
+            getattr(eng, 'set_' + name)(t)
+        x = x.contiguous().float()
+        if noise is None:
+            out = eng.sample(x, seed=self.noise_seed, image_base=image_base, call=call)
+        else:
+            out = eng.sample(x, noise.contiguous().float(), None if step_noise is None else step_noise.contiguous().float())
+        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
 
     def _get_engine(self, key, factory, geometry=None):
         cache = self.__dict__.setdefault('_engine_cache', {})
@@ -304,90 +349,30 @@ class DDP(nn.Module, _SamplerMixin):
         ``return_steps``: -> (out, record (K,b,r,h,w) uint8 - every step's argmax class, the reference's ``outs`` as decisions -,
         disagreement (b,h,w) - the fraction of them that differ from the output's argmax)."""
         self._check_feature(x)
+        return self._sample_with('ddim', x, noise, None, return_steps, image_base, call, hints=hints, prior=prior, t_start=t_start,
+                                 class_prior=class_prior, score_prior=score_prior)
+
+    def _sample_with(self, sampler, x, noise, step_noise, return_steps, image_base, call, **given):
+        """the one body of ``ddim_sample`` and ``ddpm_sample``: the engine of (sampler, what is given), conditioned, run on the noise
+        given, on the noise of ``noise_seed``, or on noise drawn here as the reference draws it"""
         b, c, h, w = x.shape
-        self._check_t_start(prior, t_start)
-        hk = {} if hints is None else dict(hints=True)
-        if prior is not None or t_start is not None:
-            hk.update(prior=prior is not None, t_start=t_start)
-        hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
-        pmap = None if prior is None else self._prior_map(prior, b, h, w, torch.uint8).to(x.device)
-        cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
-        if cp is not None:
-            hk.update(class_prior=True)
-        sp = None if score_prior is None else self._score_prior_map(score_prior, b, h, w, x.device)
-        if sp is not None:
-            hk.update(score_prior=True)
-        if noise is None and self.noise_seed is not None:
-            eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, seeded=True, **hk)
-            if hmap is not None:
-                eng.set_hints(hmap)
-            if pmap is not None:
-                eng.set_prior(pmap)
-            if cp is not None:
-                eng.set_class_prior(cp)
-            if sp is not None:
-                eng.set_score_prior(sp)
-            out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
-            return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
-        if noise is None:
-            noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
-        eng = self._engine_for(b, h, w, x.device, 'ddim', record_steps=return_steps, **hk)
-        if hmap is not None:
-            eng.set_hints(hmap)
-        if pmap is not None:
-            eng.set_prior(pmap)
-        if cp is not None:
-            eng.set_class_prior(cp)
-        if sp is not None:
-            eng.set_score_prior(sp)
-        out = eng.sample(x.contiguous().float(), noise.contiguous().float())
-        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
+        asks, maps = self._conditioning(b, h, w, x.device, torch.uint8, **given)
+        seeded = noise is None and step_noise is None and self.noise_seed is not None
+        if not seeded:
+            if noise is None:
+                noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
+            if step_noise is None and sampler == 'ddpm':
+                step_noise = torch.randn((self.timesteps, b, self.randsteps, c, h, w), device=x.device)
+        eng = self._engine_for(b, h, w, x.device, sampler, record_steps=return_steps, seeded=seeded, **asks)
+        return self._run(eng, maps, x, noise, step_noise, return_steps, image_base, call)
 
     @torch.no_grad()
     def ddpm_sample(self, x, img_metas=None, noise=None, step_noise=None, return_steps=False, image_base=0, call=0, hints=None,
                     prior=None, t_start=None, class_prior=None, score_prior=None):
         """``hints``, ``prior``, ``t_start``, ``class_prior``, ``score_prior``: as ``ddim_sample``"""
         self._check_feature(x)
-        b, c, h, w = x.shape
-        self._check_t_start(prior, t_start)
-        hk = {} if hints is None else dict(hints=True)
-        if prior is not None or t_start is not None:
-            hk.update(prior=prior is not None, t_start=t_start)
-        hmap = None if hints is None else self._hint_map(hints, b, h, w, torch.uint8).to(x.device)
-        pmap = None if prior is None else self._prior_map(prior, b, h, w, torch.uint8).to(x.device)
-        cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
-        if cp is not None:
-            hk.update(class_prior=True)
-        sp = None if score_prior is None else self._score_prior_map(score_prior, b, h, w, x.device)
-        if sp is not None:
-            hk.update(score_prior=True)
-        if noise is None and step_noise is None and self.noise_seed is not None:
-            eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, seeded=True, **hk)
-            if hmap is not None:
-                eng.set_hints(hmap)
-            if pmap is not None:
-                eng.set_prior(pmap)
-            if cp is not None:
-                eng.set_class_prior(cp)
-            if sp is not None:
-                eng.set_score_prior(sp)
-            out = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
-            return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
-        if noise is None:
-            noise = torch.randn((b, self.randsteps, c, h, w), device=x.device)
-        if step_noise is None:
-            step_noise = torch.randn((self.timesteps, b, self.randsteps, c, h, w), device=x.device)
-        eng = self._engine_for(b, h, w, x.device, 'ddpm', record_steps=return_steps, **hk)
-        if hmap is not None:
-            eng.set_hints(hmap)
-        if pmap is not None:
-            eng.set_prior(pmap)
-        if cp is not None:
-            eng.set_class_prior(cp)
-        if sp is not None:
-            eng.set_score_prior(sp)
-        out = eng.sample(x.contiguous().float(), noise.contiguous().float(), step_noise.contiguous().float())
-        return (out, eng.step_record(), eng.step_disagreement()) if return_steps else out
+        return self._sample_with('ddpm', x, noise, step_noise, return_steps, image_base, call, hints=hints, prior=prior, t_start=t_start,
+                                 class_prior=class_prior, score_prior=score_prior)
 
     def _decode_head_forward_test(self, x, t, img_metas=None):
         return self.decode_head.forward_test(x, t, img_metas, self.test_cfg)
@@ -395,18 +380,18 @@ class DDP(nn.Module, _SamplerMixin):
     def encode_decode(self, img, img_metas=None, image_base=0, call=0, class_prior=None, score_prior=None):
         """ddp.py:114-129.  ``score_prior``: see ``ddim_sample``."""
         x = self.extract_feat(img)[0]
+        kw = self._given(image_base, call, class_prior=class_prior, score_prior=score_prior)
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior), **self._sp_kw(score_prior))
+            out = self.ddim_sample(x, img_metas, **kw)
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_metas, **self._seed_kw(image_base, call), **self._cp_kw(class_prior), **self._sp_kw(score_prior))
+            out = self.ddpm_sample(x, img_metas, **kw)
         else:
             raise NotImplementedError
         return F.interpolate(out, size=img.shape[2:], mode='bilinear', align_corners=self.align_corners)
 
     def whole_inference(self, img, img_meta=None, rescale=False, image_base=0, call=0, class_prior=None, score_prior=None):
         """encoder_decoder.py:229-248: crop to img_shape and resize to ori_shape when rescale.  ``score_prior``: see ``ddim_sample``."""
-        seg_logit = self.encode_decode(img, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior),
-                                       **self._sp_kw(score_prior))
+        seg_logit = self.encode_decode(img, img_meta, **self._given(image_base, call, class_prior=class_prior, score_prior=score_prior))
         if rescale and img_meta:
             rs = img_meta[0]['img_shape'][:2]
             seg_logit = seg_logit[:, :, :rs[0], :rs[1]]
@@ -424,10 +409,11 @@ class DDP(nn.Module, _SamplerMixin):
         return mode or 'whole'
 
     def _sample(self, x, img_meta=None, image_base=0, call=0, class_prior=None):
+        kw = self._given(image_base, call, class_prior=class_prior)
         if self.diffusion == 'ddim':
-            return self.ddim_sample(x, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+            return self.ddim_sample(x, img_meta, **kw)
         if self.diffusion == 'ddpm':
-            return self.ddpm_sample(x, img_meta, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+            return self.ddpm_sample(x, img_meta, **kw)
         raise NotImplementedError
 
     SLIDE_WINDOWS_PER_CALL = 16          # windows x images sampled in one call of the loop (memory bound of the workspace)
@@ -454,8 +440,9 @@ class DDP(nn.Module, _SamplerMixin):
             chunk = crops[i:i + per]
             x = self.extract_feat(torch.cat(chunk, dim=0))[0]
             # (a class prior is image-level: every window of image i gets row i - the chunk's maps are window-major)
-            cpk = {} if class_prior is None else dict(class_prior=self._class_prior_table(class_prior, b, x.device, repeat=len(chunk)))
-            lows.append(self._sample(x, img_meta, **self._seed_kw(image_base, call + i // per), **cpk).reshape(len(chunk), b, self.num_classes, x.shape[2], x.shape[3]))
+            rows = None if class_prior is None else self._class_prior_table(class_prior, b, x.device, repeat=len(chunk))
+            low = self._sample(x, img_meta, **self._given(image_base, call + i // per, class_prior=rows))
+            lows.append(low.reshape(len(chunk), b, self.num_classes, x.shape[2], x.shape[3]))
         scores = torch.cat(lows, dim=0)
         keep = out = None
         if rescale and img_meta:
@@ -468,13 +455,8 @@ class DDP(nn.Module, _SamplerMixin):
         """``class_prior`` (b, num_classes): every window of image i samples with row i (see ``ddim_sample``).
         ``score_prior`` is not built for slide inference (ValueError).
         encoder_decoder.py:180-227: the window-averaged scores (b,K,H,W) (at ori_shape when ``rescale``)."""
-        if score_prior is not None:
-            raise ValueError('score_prior is not built for slide inference (one score prior map per sampler call, not per window)')
-        if prior is not None or t_start is not None:
-            raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
-        if hints is not None:
-            raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
-        return self._slide(img, img_meta, rescale, 'scores', **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
+        self._refuse_frame_bound('slide inference', hints, prior, t_start, score_prior)
+        return self._slide(img, img_meta, rescale, 'scores', **self._given(image_base, call, class_prior=class_prior))
 
     def inference(self, img, img_meta, rescale, image_base=0, call=0, class_prior=None):
         """``class_prior`` (b, num_classes): see ``ddim_sample``.
@@ -482,6 +464,7 @@ class DDP(nn.Module, _SamplerMixin):
         the test-time flip undone - the building block of ``aug_test``.  ``simple_test`` does not go through here: its
         fused epilogue never materialises these (B,K,H,W) tensors."""
         mode = self._mode()
+        kw = self._given(image_base, call, class_prior=class_prior)
         if img_meta:
             ori_shape = img_meta[0]['ori_shape']
             assert all(m['ori_shape'] == ori_shape for m in img_meta)
@@ -490,8 +473,8 @@ class DDP(nn.Module, _SamplerMixin):
             if img_meta and img_meta[0].get('flip', False):
                 fl = img_meta[0].get('flip_direction', 'horizontal')
                 assert fl in ('horizontal', 'vertical')
-            return self._slide(img, img_meta, rescale, 'prob', fl, **self._seed_kw(image_base, call), **self._cp_kw(class_prior))
-        output = F.softmax(self.whole_inference(img, img_meta, rescale, **self._seed_kw(image_base, call), **self._cp_kw(class_prior)), dim=1)
+            return self._slide(img, img_meta, rescale, 'prob', fl, **kw)
+        output = F.softmax(self.whole_inference(img, img_meta, rescale, **kw), dim=1)
         if img_meta and img_meta[0].get('flip', False):
             direction = img_meta[0].get('flip_direction', 'horizontal')
             assert direction in ('horizontal', 'vertical')
@@ -521,34 +504,23 @@ class DDP(nn.Module, _SamplerMixin):
         softmax -> flip-undo for all of them, the mean and the argmax per output pixel: the (1,K,H,W) tensors ``inference``
         materialises per augmentation and the running sum at ori_shape never exist."""
         from ..engine import seg_aug_postprocess
-        if score_prior is not None:
-            raise ValueError('score_prior is not built for aug_test (every augmentation has its own frame)')
-        if hints is not None:
-            raise ValueError('hints are not built for aug_test (every augmentation has its own frame)')
-        if prior is not None or t_start is not None:
-            raise ValueError('prior / t_start are not built for aug_test (every augmentation has its own frame)')
+        self._refuse_frame_bound('aug_test', hints, prior, t_start, score_prior)
         assert rescale, 'aug_test rescales every augmentation back to ori_shape'
         if len(imgs) != len(img_metas):
             raise ValueError(f'num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})')
         if self._mode() == 'slide':
             # no shipped config combines sliding windows with test-time augmentation: the reference's own composition
             # (running mean of ``inference``, encoder_decoder.py:306-331) over the fused per-augmentation slide epilogue
-            prob = self.inference(imgs[0], img_metas[0], rescale, **self._seed_kw(image_base, 0), **self._cp_kw(class_prior))
+            prob = self.inference(imgs[0], img_metas[0], rescale, **self._given(image_base, 0, class_prior=class_prior))
             for a, (img, meta) in enumerate(zip(imgs[1:], img_metas[1:]), 1):
-                prob += self.inference(img, meta, rescale, **self._seed_kw(image_base, a * self.AUG_CALL_STRIDE), **self._cp_kw(class_prior))
+                prob += self.inference(img, meta, rescale, **self._given(image_base, a * self.AUG_CALL_STRIDE, class_prior=class_prior))
             prob /= len(imgs)
             return self._deliver(prob.argmax(dim=1), on_device)
         ori_shape = tuple(img_metas[0][0]['ori_shape'][:2])
         scores, metas = [], []
         for a, (img, meta) in enumerate(zip(imgs, img_metas)):
             assert all(tuple(m['ori_shape'][:2]) == ori_shape for m in meta)
-            x = self.extract_feat(img)[0]
-            if self.diffusion == 'ddim':
-                scores.append(self.ddim_sample(x, meta, **self._seed_kw(image_base, a), **self._cp_kw(class_prior)))
-            elif self.diffusion == 'ddpm':
-                scores.append(self.ddpm_sample(x, meta, **self._seed_kw(image_base, a), **self._cp_kw(class_prior)))
-            else:
-                raise NotImplementedError
+            scores.append(self._sample(self.extract_feat(img)[0], meta, **self._given(image_base, a, class_prior=class_prior)))
             metas.append(dict(img_size=tuple(img.shape[2:]), crop_size=tuple(meta[0]['img_shape'][:2]),
                               flip=meta[0].get('flip_direction', 'horizontal') if meta[0].get('flip', False) else None))
         seg = seg_aug_postprocess(scores, metas, ori_shape, self.align_corners)
@@ -579,18 +551,8 @@ class DDP(nn.Module, _SamplerMixin):
         b >= 1 images (§8 f4): the loop runs once on the whole batch with independent noise per image, and every
         image gets the crop / rescale / flip of its OWN ``img_meta`` entry (one epilogue launch per distinct geometry)."""
         from ..engine import seg_postprocess
-        hk = {} if hints is None else dict(hints=hints)
-        if prior is not None or t_start is not None:
-            hk.update(prior=prior, t_start=t_start)
-        hk.update(self._cp_kw(class_prior))
-        hk.update(self._sp_kw(score_prior))
         if self._mode() == 'slide':
-            if score_prior is not None:
-                raise ValueError('score_prior is not built for slide inference (one score prior map per sampler call, not per window)')
-            if prior is not None or t_start is not None:
-                raise ValueError('prior / t_start are not built for slide inference (one prior map per sampler call, not per window)')
-            if hints is not None:
-                raise ValueError('hints are not built for slide inference (one hint map per sampler call, not per window)')
+            self._refuse_frame_bound('slide inference', hints, prior, t_start, score_prior)
             if img_meta and any(self._epilogue_args(m, rescale) != self._epilogue_args(img_meta[0], rescale) for m in img_meta):
                 raise ValueError('slide inference: the images of a batch must share img_shape / ori_shape / flip')
             fl = self._epilogue_args(img_meta[0], rescale)[2] if img_meta else None
@@ -598,12 +560,13 @@ class DDP(nn.Module, _SamplerMixin):
             # softmax is monotone, so the two agree except where fp32 rounding of exp / the division makes two probabilities EQUAL
             # that came from different scores - the reference then returns the lower class index, this path the class with the
             # larger score.  test_slide_epilogue_golden bounds it: identical wherever the reference's top-2 margin exceeds 1e-5.)
-            return self._deliver(self._slide(img, img_meta, rescale, 'seg', fl, **self._seed_kw(image_base), **self._cp_kw(class_prior)), on_device)
+            return self._deliver(self._slide(img, img_meta, rescale, 'seg', fl, **self._given(image_base, 0, class_prior=class_prior)), on_device)
+        kw = self._given(image_base, 0, hints=hints, prior=prior, t_start=t_start, class_prior=class_prior, score_prior=score_prior)
         x = self.extract_feat(img)[0]
         if self.diffusion == 'ddim':
-            out = self.ddim_sample(x, img_meta, **self._seed_kw(image_base), **hk)
+            out = self.ddim_sample(x, img_meta, **kw)
         elif self.diffusion == 'ddpm':
-            out = self.ddpm_sample(x, img_meta, **self._seed_kw(image_base), **hk)
+            out = self.ddpm_sample(x, img_meta, **kw)
         else:
             raise NotImplementedError
         b = out.shape[0]
@@ -630,21 +593,17 @@ class DDP(nn.Module, _SamplerMixin):
         augmentation lists the test pipeline produces."""
         if return_loss:
             raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
+        kw = self._given(image_base, hints=hints, prior=prior, t_start=t_start, class_prior=class_prior, score_prior=score_prior,
+                         on_device=on_device)
         if isinstance(img, (list, tuple)):
             if len(img) != 1:
                 if img_metas is None or len(img_metas) != len(img):
                     raise ValueError(f'num of augmentations ({len(img)}) != num of image meta ({0 if img_metas is None else len(img_metas)})')
-                return self.aug_test(list(img), list(img_metas), rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
-                                     **({} if hints is None else {'hints': hints}),
-                                     **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
-                                     **self._cp_kw(class_prior), **self._sp_kw(score_prior), **({'on_device': True} if on_device else {}))
+                return self.aug_test(list(img), list(img_metas), rescale, **kw)
             img = img[0]
             if img_metas is not None:
                 img_metas = img_metas[0]
-        return self.simple_test(img, img_metas, rescale, **({'image_base': image_base} if self.noise_seed is not None else {}),
-                                **({} if hints is None else {'hints': hints}),
-                                **({} if prior is None and t_start is None else {'prior': prior, 't_start': t_start}),
-                                **self._cp_kw(class_prior), **self._sp_kw(score_prior), **({'on_device': True} if on_device else {}))
+        return self.simple_test(img, img_metas, rescale, **kw)
 
     def forward_train(self, *a, **k):
         raise NotImplementedError('training is out of scope of ddp_amd (SURVEY.md §8)')
@@ -673,29 +632,14 @@ class SelfAlignedDDP(DDP):
         from .. import _lib
         self._check_feature(x)
         b, c, h, w = x.shape
-        cp = None if class_prior is None else self._class_prior_table(class_prior, b, x.device)
-        ck = {} if cp is None else dict(class_prior=True)
-        sp = None if score_prior is None else self._score_prior_map(score_prior, b, h, w, x.device)
-        if sp is not None:
-            ck.update(score_prior=True)
+        asks, maps = self._conditioning(b, h, w, x.device, torch.uint8, class_prior=class_prior, score_prior=score_prior)
+        seeded = noise is None and self.noise_seed is not None
+        if noise is None and not seeded:
+            noise = torch.randn_like(x)
         # the head dispatch of _engine_for (the reference's pre-pass goes through the generic _decode_head_forward_test)
-        if noise is None and self.noise_seed is not None:
-            eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned',
-                                   seeded=True, **ck)
-            if cp is not None:
-                eng.set_class_prior(cp)
-            if sp is not None:
-                eng.set_score_prior(sp)
-            logits = eng.sample(x.contiguous().float(), seed=self.noise_seed, image_base=image_base, call=call)
-        else:
-            if noise is None:
-                noise = torch.randn_like(x)
-            eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned', **ck)
-            if cp is not None:
-                eng.set_class_prior(cp)
-            if sp is not None:
-                eng.set_score_prior(sp)
-            logits = eng.sample(x.contiguous().float(), noise.reshape(b, 1, c, h, w).contiguous().float())
+        eng = self._engine_for(b, h, w, x.device, 'ddim', timesteps=1, randsteps=1, accumulation=False, kind='self_aligned',
+                               seeded=seeded, **asks)
+        logits = self._run(eng, maps, x, None if seeded else noise.reshape(b, 1, c, h, w), image_base=image_base, call=call)
         preds = torch.empty((b, 256, h, w), dtype=torch.float32, device=x.device)
         emb = self.embedding_table.weight.detach().float().contiguous()
         with torch.cuda.device(x.device):

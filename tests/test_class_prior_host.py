@@ -391,7 +391,11 @@ def test_plugin_surface_without_a_device():
     for bad in (torch.zeros(2, 4), torch.zeros(3, 5), torch.zeros(5), torch.zeros(2, 5, dtype=torch.int64), [torch.zeros(2, 5)], 'x'):
         with pytest.raises(ValueError, match='class_prior'):
             DDP._class_prior_table(m, bad, 2, torch.device('cpu'))
-    assert DDP._cp_kw(None) == {} and list(DDP._cp_kw(rows)) == ['class_prior']
+    # the one forwarding helper: a None gives no key, a value exactly its key (prior and t_start travel together)
+    assert m._given() == {} and m._given(0, 0) == {}
+    for k, keys in (('hints', ['hints']), ('prior', ['prior', 't_start']), ('t_start', ['prior', 't_start']),
+                    ('class_prior', ['class_prior']), ('score_prior', ['score_prior'])):
+        assert list(m._given(**{k: rows})) == keys and all(v is rows or v is None for v in m._given(**{k: rows}).values()), k
     seen = {}
 
     class _M(torch.nn.Module):

@@ -368,8 +368,17 @@ def test_engine_surface():
     with pytest.raises(ValueError, match='score_prior is built for ddp_sample only'):
         FcnSamplerEngine({}, None, h=4, w=4, score_prior=True)
     assert callable(score_prior_places)
-    src = inspect.getsource(engine.caller_regions)
-    assert src.index("'sprior_rows'") < src.index("'sprior_map'") < src.index("'cprior_rows'")
+    every = S.make_cfg(dict(P.CASES['kc19_7x13_b3'], seed=1))
+    every.flags |= _lib.FLAG_SCORE_PRIOR | _lib.FLAG_CLASS_PRIOR | _lib.FLAG_PRIOR_START | _lib.FLAG_X0_HINTS
+    names = list(engine.caller_regions(every, 1 << 24))
+    assert names.index('sprior_rows') < names.index('sprior_map') < names.index('cprior_rows')
+    assert [row.region for row in engine.CALLER_INPUTS] == [n for n in names if n in ('sprior_map', 'cprior_table', 'prior_map', 'hint_map')]
+    assert [row.name for row in engine.CALLER_INPUTS] == ['score_prior', 'class_prior', 'prior', 'hints']
+    # ... and is, field for field, the literal rows the conditioning tests run on
+    import conditioning_cases as CC
+    tasks = {_lib.TASK_SEG: 'seg', _lib.TASK_DEPTH: 'depth', _lib.TASK_BEV: 'bev'}
+    assert [(r.name, r.kwarg, r.flag, r.flag_name, r.region, tuple(tasks[t] for t in r.dtypes)) for r in engine.CALLER_INPUTS] == \
+        [(name, kwarg, getattr(_lib, flag), 'DDP_' + flag, region, on) for name, kwarg, flag, region, on, _, _ in CC.ROWS]
     # a flag-clear engine has no map
     eng = object.__new__(DDPEngine)
     eng.cfg = S.make_cfg(dict(P.CASES['kc19_7x13_b3'], seed=1))
@@ -407,7 +416,11 @@ def test_plugin_surface_without_a_device():
                 [torch.zeros(2, 5, 3, 4)], 'x'):
         with pytest.raises(ValueError, match='score_prior must be a float'):
             DDP._score_prior_map(m, bad, 2, 3, 4, dev)
-    assert DDP._sp_kw(None) == {} and list(DDP._sp_kw(same)) == ['score_prior']
+    # the one forwarding helper: a None gives no key, a value exactly its key (prior and t_start travel together)
+    assert m._given() == {} and m._given(0, 0) == {}
+    for k, keys in (('hints', ['hints']), ('prior', ['prior', 't_start']), ('t_start', ['prior', 't_start']),
+                    ('class_prior', ['class_prior']), ('score_prior', ['score_prior'])):
+        assert list(m._given(**{k: same})) == keys and all(v is same or v is None for v in m._given(**{k: same}).values()), k
     # the refusals come before anything touches a device
     m.test_cfg = dict(mode='slide', crop_size=(8, 8), stride=(4, 4))
     img = torch.zeros(1, 3, 16, 16)
