@@ -1,4 +1,5 @@
-"""What the ctypes bindings of the side libraries (``build.SIDE``: ``_eval_lib``, ``_cm_lib``, ``_lss_lib``, ``_dlss_lib``) share:
+"""What the ctypes bindings of the side libraries (``build.SIDE``: ``_eval_lib``, ``_cm_lib``, ``_lss_lib``, ``_dlss_lib``;
+``build.LATER``: ``_vox_lib``) share:
 load once per path, refuse a missing, stale or other-ABI library, turn a return code into an exception.
 
 Like ``_lib``: NO fallback.  A missing or stale library raises; build it with ``python -m ddp_amd.build``.  A binding file holds
@@ -9,7 +10,7 @@ import os
 
 
 class SideLibError(RuntimeError):
-    """base of DdpEvalError, DdpCmError, DdpLssError, DdpDlssError: ``code`` is the library's return code (None: raised on loading)"""
+    """base of DdpEvalError, DdpCmError, DdpLssError, DdpDlssError, DdpVoxError: ``code`` is the library's return code (None: raised on loading)"""
 
     def __init__(self, msg, code=None):
         super().__init__(msg)
@@ -17,7 +18,7 @@ class SideLibError(RuntimeError):
 
 
 class Binding:
-    """``side``: the library's ``build.SIDE`` entry, which names it (libddp_<name>.so, symbols ddp_<name>_*); ``argtypes``: {symbol:
+    """``side``: the library's ``build.SIDE`` or ``build.LATER`` entry, which names it (libddp_<name>.so, symbols ddp_<name>_*); ``argtypes``: {symbol:
     argument types} of its entry points, which all return an int code, beside ``ddp_<name>_last_error`` and ``ddp_<name>_abi_version``;
     ``module``: the public module the messages name; ``error``: the binding's SideLibError; ``badcfg``: the return code that means a
     refused configuration and raises ValueError (None: ``error``, like every other code)."""

@@ -231,3 +231,30 @@ def register_depth_vtransform_into_mmdet3d():
     from .bev.depth_lss import DepthLSSTransform
     MV.register_module(name='DepthLSSTransform', force=True, module=DepthLSSTransform)
     return ['mmdet3d.VTRANSFORMS']
+
+
+def use_device_voxelization(model, reduce=None):
+    """Put the lidar branch's voxelisation of a BEVFusion-style ``model`` on the device: ``model.encoders['lidar']['voxelize']`` (the
+    reference's ``Voxelization``, bev/mmdet3d/ops/voxel/voxelize.py) is replaced by the device class built from its members, and
+    ``model.voxelize`` (bevfusion.py:135-163) is bound to the batched path of libddp_vox.so: one call for the whole batch ->
+    ``feats, coords, sizes``.  ``reduce``: the mean of a voxel's points as ``feats`` (default: the model's ``voxelize_reduce``).
+    Returns the module it replaced."""
+    import types
+    from .bev.voxelize import Voxelization
+    encoders = getattr(model, 'encoders', None)
+    if encoders is None or 'lidar' not in encoders or 'voxelize' not in encoders['lidar']:
+        raise ValueError("the model has no lidar encoder: model.encoders['lidar']['voxelize'] is what use_device_voxelization replaces")
+    old = encoders['lidar']['voxelize']
+    if int(old.max_num_points) <= 0:
+        raise NotImplementedError(f'max_num_points = {old.max_num_points}: only hard voxelisation is built (the dynamic path, '
+                                  f'DynamicScatter, is not)')
+    new = Voxelization(old.voxel_size, old.point_cloud_range, old.max_num_points, tuple(old.max_voxels), getattr(old, 'deterministic', True))
+    new.train(getattr(old, 'training', False))
+    encoders['lidar']['voxelize'] = new
+    reduce = bool(getattr(model, 'voxelize_reduce', True)) if reduce is None else bool(reduce)
+
+    def voxelize(self, points):
+        vox = self.encoders['lidar']['voxelize']
+        return tuple(t.clone() for t in vox.engine().voxelize_batch([p.float() for p in points], reduce=reduce))
+    model.voxelize = types.MethodType(voxelize, model)
+    return old
