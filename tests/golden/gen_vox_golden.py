@@ -1,6 +1,7 @@
-"""Fixtures of the device-side hard voxelisation: the cases ``vox_cases.FIXTURES`` run through the REFERENCE's own code on the CPU.
+"""Fixtures of the device-side hard voxelisation: the cases ``vox_cases.FIXTURES`` and ``vox_edge_cases.FIXTURES`` run through the
+REFERENCE's own code on the CPU.
 
-    python tests/golden/gen_vox_golden.py          (by hand, where the reference tree is present)
+    python tests/golden/gen_vox_golden.py [out_dir [case ...]]         (by hand, where the reference tree is present)
 
 What is the reference's: ``hard_voxelize_cpu`` (bev/mmdet3d/ops/voxel/src/voxelization_cpu.cpp, compiled here by
 ``torch.utils.cpp_extension.load`` together with a binding of a few lines that this file writes, into a directory OUTSIDE the
@@ -32,6 +33,7 @@ REF = os.environ.get('DDP_REFERENCE_ROOT', '/root/reference')
 VOXEL = os.path.join(REF, 'bev', 'mmdet3d', 'ops', 'voxel')
 
 import vox_cases as VC  # noqa: E402
+import vox_edge_cases as VE  # noqa: E402
 
 BINDING = '''#include <torch/extension.h>
 #include <vector>
@@ -101,13 +103,14 @@ def load_reference():
     return voxelize.Voxelization, fusion.BEVFusion
 
 
-def gen():
+def gen(names=None, out=OUT):
+    """``names``: the cases to run (default: every committed fixture); ``out``: where the files go"""
     torch.set_num_threads(1)
     Voxelization, BEVFusion = load_reference()
-    os.makedirs(OUT, exist_ok=True)
+    os.makedirs(out, exist_ok=True)
     sizes = {}
-    for name in VC.FIXTURES:
-        c = VC.case(name)
+    for name in VC.FIXTURES + VE.FIXTURES if names is None else names:
+        c = VC.case(name) if name in VC.NAMES else VE.case(name)
         assert c['grid'][0] == c['grid'][2], name
         module = Voxelization(c['voxel_size'], c['range'], c['T'], (c['max_voxels'] + 1000, c['max_voxels'])).eval()
         assert [int(v) for v in module.grid_size] == c['grid']
@@ -123,7 +126,7 @@ def gen():
             feats, coords, sz = BEVFusion.voxelize(model, points)
             arrays[key] = feats.numpy()
         arrays.update(coords=coords.numpy(), sizes=sz.numpy() if torch.is_tensor(sz) else np.zeros(0, np.int32))
-        path = os.path.join(OUT, f'vox_{name}.npz')
+        path = os.path.join(out, f'vox_{name}.npz')
         np.savez_compressed(path, **arrays)
         sizes[os.path.basename(path)] = os.path.getsize(path)
         assert sizes[os.path.basename(path)] <= 128 * 1024, (path, sizes)
@@ -131,5 +134,5 @@ def gen():
 
 
 if __name__ == '__main__':
-    for k, v in gen().items():
+    for k, v in gen(sys.argv[2:] or None, *sys.argv[1:2]).items():
         print(k, v, 'bytes')
